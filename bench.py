@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native MambaXray-VL hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM.
-Rank 0 prints ONE JSON line (contract in the task statement): whole-job images/sec, plus
+Rank 0 prints ONE JSON line (contract in the task statement): whole-job images/sec and ms_per_step.
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.  --full adds what the
+headline figure does not need, as separate measurements of the same process:
   "roofline":     algorithmic HBM bytes of the dominant kernel / its mean launch duration (HIP events
-                  on the launch stream, inside the timed region) against the 8 TB/s HBM3E peak;
+                  on the launch stream, inside the timed region) against the 8 TB/s HBM3E peak (the
+                  training-step workloads; the others derive theirs from the timed steps in every run);
   "cpu_baseline": the CPU oracle (oracle/mxvl_oracle.c, a restatement of the reference's
-                  selective_scan_ref) timed on this box's host cores on a bounded sample (rank 0, N=1).
+                  selective_scan_ref) timed on this box's host cores on a bounded sample (rank 0, N=1);
+  the default workload's north-star scan leg and report-decode leg ("north_star_kernel", "secondary").
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy in float32 /
+float64: the loss and a fixed seeded sample of the updated weights for a training step, the tokens
+of a decode, the scan's outputs (seeded samples of the large ones), at most 64 MB in all.  Inputs and
+initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workloads (BASELINE.json configs):
   arm_pretrain_large_1024  configs[2]: MambaXray-VL-Large stage-1 pre-training step (forward + backward + clip +
@@ -79,6 +87,57 @@ def pmc_traffic(workload):
             return {"bytes": rec["bytes"], "source": os.path.basename(path), "fetch_kb": rec["fetch_kb"], "write_kb": rec["write_kb"],
                     "kernel": rec.get("kernel")}
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all arrays of one run together
+DUMP_SAMPLE = 1 << 20            # elements kept of an output array larger than this (a seeded sample)
+DUMP_PARAM_SAMPLE = 4 << 20      # elements kept of a model's updated weights, drawn across every parameter
+
+
+def _seeded_index(numel, k, seed):
+    """k sorted indices into a flat tensor of numel elements, from a CPU generator of its own: the same on every run and build."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(numel, (k,), generator=g).sort().values
+
+
+def sample_output(t, seed=0, k=DUMP_SAMPLE):
+    """The whole tensor when it has at most k elements, else k of its elements at seeded positions (flat)."""
+    t = t.detach()
+    if t.numel() <= k:
+        return t
+    flat = t.reshape(-1)
+    return flat[_seeded_index(flat.numel(), k, seed).to(flat.device)]
+
+
+def sample_params(params, k=DUMP_PARAM_SAMPLE, seed=0):
+    """A seeded sample of a model's weights, one flat array: every parameter contributes in proportion to its size (at least
+    one element, all of them when the model has at most k), in the order the model lists them."""
+    params = [p.detach() for p in params]
+    total = sum(p.numel() for p in params)
+    parts = []
+    for i, p in enumerate(params):
+        flat = p.reshape(-1)
+        n = flat.numel() if total <= k else min(flat.numel(), max(1, flat.numel() * k // total))
+        parts.append((flat if n == flat.numel() else flat[_seeded_index(flat.numel(), n, seed + i).to(flat.device)]).float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every tensor of `arrays` (None entries skipped): float64 stays float64, everything else becomes
+    float32 (integer tokens included: they are exact there below 2**24)."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach().cpu()
+        out[name] = t.double().numpy() if t.dtype == torch.float64 else t.float().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {nbytes} bytes > the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _dp_label(world):
@@ -267,10 +326,10 @@ def _decode_kernel_text(layers, heads, B, beams, fused_norm):
             "the time per token includes the prompt prefill's share")
 
 
-def measure_decode(workload, steps, warmup, rank, world, dev, dist):
+def measure_decode(workload, steps, warmup, rank, world, dev, dist, dump_dir=None):
     """Autoregressive report decoding: one 'step' = one full generate() of `new_tokens` tokens per sample.
     Replicas only across GPUs (the reference decodes on a single device, MambaXrayVL_DownStream.py:407).
-    Returns the result dict on rank 0 (None elsewhere)."""
+    Returns the result dict on rank 0 (None elsewhere).  dump_dir: the tokens of the last timed generate() go there."""
     from medical_image_analysis_amd.report_decoder import ReportDecoder
     vocab, hidden, inter, layers, heads, kvh, plen, new, beams, B, desc = DECODE_WORKLOADS[workload]
     dt_name, dt = _decode_dtype(workload)
@@ -311,6 +370,8 @@ def measure_decode(workload, steps, warmup, rank, world, dev, dist):
     torch.cuda.empty_cache()
     if rank != 0:
         return None
+    if dump_dir:
+        dump_outputs(dump_dir, {"tokens": out})
     tokens = B * world * steps * n_out
     n_params -= vocab * hidden                              # the embedding table is looked up (rows x hidden), not streamed
     wbytes = 2 * n_params                                   # every decode step streams the 16-bit weights once
@@ -386,7 +447,7 @@ def cpu_baseline_decode(workload):
 def run_decode(args, rank, world, dev, dist):
     steps = args.steps if args.steps > 0 else 3
     warmup = args.warmup if args.warmup >= 0 else 1
-    res = measure_decode(args.workload, steps, warmup, rank, world, dev, dist)
+    res = measure_decode(args.workload, steps, warmup, rank, world, dev, dist, dump_dir=args.dump_outputs)
     if res is not None:
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_decode(args.workload)
@@ -516,10 +577,10 @@ def _graph_kw(args, world):
     return {"use_graph": True}
 
 
-def _timed_steps(eng, batches, steps, warmup, ssi, dist):
-    """W warm-up steps, then exactly K timed steps between barrier + synchronize pairs.  Eager engine: the scan launches of the timed steps
-    are bracketed by HIP events (ssi.KERNEL_TIMERS) for the roofline object.  Graph engine: the timed steps are graph launches (nothing in
-    Python to bracket), the kernel events come from two more EAGER steps behind the timed region."""
+def _timed_steps(eng, batches, steps, warmup, ssi, dist, kernel_timers=True):
+    """W warm-up steps, then exactly K timed steps between barrier + synchronize pairs.  kernel_timers (--full) -- eager engine: the scan
+    launches of the timed steps are bracketed by HIP events (ssi.KERNEL_TIMERS) for the roofline object; graph engine: the timed steps are
+    graph launches (nothing in Python to bracket), the kernel events come from two more EAGER steps behind the timed region."""
     graph = getattr(eng, "use_graph", False)
     if graph:
         warmup = max(warmup, eng.graph_warmup + 2)          # the capture and the first replay belong to the warm-up
@@ -530,7 +591,7 @@ def _timed_steps(eng, batches, steps, warmup, ssi, dist):
         dist.barrier()
     torch.cuda.synchronize()
     timers = []
-    if not graph:
+    if not graph and kernel_timers:
         ssi.KERNEL_TIMERS = timers
     t0 = time.perf_counter()
     for i in range(steps):
@@ -542,7 +603,7 @@ def _timed_steps(eng, batches, steps, warmup, ssi, dist):
     wall = time.perf_counter() - t0
     ssi.KERNEL_TIMERS = None
     loss = loss.clone()
-    if graph:
+    if graph and kernel_timers:
         ssi.KERNEL_TIMERS = timers
         for i in range(2):
             eng._eager_step(batches[i % 2])
@@ -577,13 +638,15 @@ def run_pretrain(args, rank, world, dev, dist):
     g = torch.Generator(device="cpu").manual_seed(1000 + rank)
     batches = [torch.randn(B, 3, img, img, generator=g).to(dev) for _ in range(2)]
     steps = args.steps
-    loss, wall, timers, warmup = _timed_steps(eng, batches, steps, args.warmup, ssi, dist)
+    loss, wall, timers, warmup = _timed_steps(eng, batches, steps, args.warmup, ssi, dist, kernel_timers=args.full)
     timer_steps = eng.timer_steps
     if dist is not None:
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t[0])
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "params_sample": sample_params(eng.raw_model.parameters())})
     cpu_sd = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items()}
@@ -599,15 +662,6 @@ def run_pretrain(args, rank, world, dev, dist):
             secondary["cpu_baseline"] = cpu_baseline_decode("decode_llama7b_128")
     if rank != 0:
         return
-    stats = _kernel_stats(timers)
-    mfma_obj = _mfma_kernel_object(stats, timer_steps, wall / steps * 1e3)
-    # dominant hand-written kernel of the step = the timed kernel with the largest total time.  At this shape the weight-gradient MFMA
-    # kernel (priced against the matrix cores) and the scan backward (priced against HBM, as the contract asks) are within a few
-    # per cent of each other: whichever leads on this box is `roofline`, the other one is reported beside it (`mfma_kernel` / `hbm_kernel`)
-    dominant = max(stats, key=lambda k: stats[k][0])
-    kind = max((k for k in stats if k not in MFMA_KINDS), key=lambda k: stats[k][0])
-    tot_ms, calls, tot_bytes = stats[kind]
-    achieved = tot_bytes / (tot_ms * 1e-3) / 1e9
     L = (img // patch) ** 2 - 16
     out = {
         "metric": "pre-training images/sec (forward + backward + grad-clip + AdamW)",
@@ -619,13 +673,25 @@ def run_pretrain(args, rank, world, dev, dist):
                    "final_loss": final_loss,
                    "timed_step": "forward + backward (DDP bucketed grad all-reduce overlapped) + loss all-reduce + clip + fused AdamW",
                    "launch": "one hipGraph launch per step (PretrainEngine use_graph)" if getattr(args, "graph", False) else "eager launches"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": kind,
-                     "kernel_ms": tot_ms / calls, "launches_timed": calls,
-                     "algorithmic_bytes_per_launch": tot_bytes // calls,
-                     "step_share": {k: round(v[0] / timer_steps / (wall / steps * 1e3), 4) for k, v in stats.items()},
-                     "limited_by": "VALU issue rate of the fp32 recurrence (5 VALU + 1 v_exp per step and state), not HBM traffic (DESIGN.md 4.1 / 4.3); the HBM fraction is what the contract asks for"},
     }
+    if not args.full:
+        print(json.dumps(out))
+        return
+    stats = _kernel_stats(timers)
+    mfma_obj = _mfma_kernel_object(stats, timer_steps, wall / steps * 1e3)
+    # dominant hand-written kernel of the step = the timed kernel with the largest total time.  At this shape the weight-gradient MFMA
+    # kernel (priced against the matrix cores) and the scan backward (priced against HBM, as the contract asks) are within a few
+    # per cent of each other: whichever leads on this box is `roofline`, the other one is reported beside it (`mfma_kernel` / `hbm_kernel`)
+    dominant = max(stats, key=lambda k: stats[k][0])
+    kind = max((k for k in stats if k not in MFMA_KINDS), key=lambda k: stats[k][0])
+    tot_ms, calls, tot_bytes = stats[kind]
+    achieved = tot_bytes / (tot_ms * 1e-3) / 1e9
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": kind,
+                       "kernel_ms": tot_ms / calls, "launches_timed": calls,
+                       "algorithmic_bytes_per_launch": tot_bytes // calls,
+                       "step_share": {k: round(v[0] / timer_steps / (wall / steps * 1e3), 4) for k, v in stats.items()},
+                       "limited_by": "VALU issue rate of the fp32 recurrence (5 VALU + 1 v_exp per step and state), not HBM traffic (DESIGN.md 4.1 / 4.3); the HBM fraction is what the contract asks for"}
     attach_traffic(out["roofline"], "scan_bwd_pretrain" if (kind == "scan_bwd" and args.workload == DEFAULT_WORKLOAD and B == 16)
                    else args.workload)
     if secondary is not None:
@@ -749,6 +815,8 @@ def run_finetune(args, rank, world, dev, dist):
         wall = float(t[0])
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "params_sample": sample_params(trainable)})
     with torch.no_grad():
         seq = model._prefix(batches[0])[0].shape[1] + 100
     # model flops of a step: the frozen LLM's forward + activation-gradient backward (2 + 2 flops per weight and token, no weight
@@ -822,6 +890,8 @@ def run_mae(args, rank, world, dev, dist):
         wall = float(t[0])
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "params_sample": sample_params(model.parameters())})
     net = model.net
     enc = sum(p.numel() for n, p in net.named_parameters() if n.startswith("blocks."))
     dec = sum(p.numel() for n, p in net.named_parameters() if n.startswith("decoder_blocks.") or n.startswith("decoder_pred") or n.startswith("decoder_embed"))
@@ -885,13 +955,26 @@ def run_vmamba(args, rank, world, dev, dist):
     g = torch.Generator(device="cpu").manual_seed(1000 + rank)
     batches = [torch.randn(B, 3, 224, 224, generator=g).to(dev) for _ in range(2)]
     steps = args.steps
-    loss, wall, timers, warmup = _timed_steps(eng, batches, steps, args.warmup, ssi, dist)
+    loss, wall, timers, warmup = _timed_steps(eng, batches, steps, args.warmup, ssi, dist, kernel_timers=args.full)
     timer_steps = eng.timer_steps
     if dist is not None:
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t[0])
     if rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "params_sample": sample_params(eng.raw_model.parameters())})
+    line = {
+        "metric": "encoder training images/sec (forward + backward + grad-clip + AdamW)", "value": B * world * steps / wall,
+        "unit": "images/sec", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": wall / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
+        "data": "synthetic N(0,1) images (seed 1000+rank), random-init weights (seed 0)",
+        "config": {"workload": f"{args.workload}: {desc}", "per_gpu_batch": B, "global_batch": B * world, "params": n_params,
+                   "parallelism": _dp_label(world), "final_loss": float(loss.mean()),
+                   "launch": "one hipGraph launch per step (PretrainEngine use_graph)" if getattr(args, "graph", False) else "eager launches"}}
+    if not args.full:
+        print(json.dumps(line))
         return
     stats = _kernel_stats(timers)
     mfma_obj = _mfma_kernel_object(stats, timer_steps, wall / steps * 1e3)
@@ -905,13 +988,7 @@ def run_vmamba(args, rank, world, dev, dist):
     print(json.dumps({
         **({"cpu_baseline": cpu_b} if cpu_b is not None else {}),
         **({"mfma_kernel": mfma_obj} if mfma_obj is not None else {}),
-        "metric": "encoder training images/sec (forward + backward + grad-clip + AdamW)", "value": B * world * steps / wall,
-        "unit": "images/sec", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": wall / steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
-        "data": "synthetic N(0,1) images (seed 1000+rank), random-init weights (seed 0)",
-        "config": {"workload": f"{args.workload}: {desc}", "per_gpu_batch": B, "global_batch": B * world, "params": n_params,
-                   "parallelism": _dp_label(world), "final_loss": float(loss.mean()),
-                   "launch": "one hipGraph launch per step (PretrainEngine use_graph)" if getattr(args, "graph", False) else "eager launches"},
+        **line,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": None, "kernel": kind + (" (4 directions stacked: one launch, n_groups 4, L = 197)" if args.workload.startswith("arm_")
                                                          else " (all SS2D stages: L = 3136 / 784 / 196 / 49, 4 direction groups, d_state 1)"),
@@ -919,8 +996,9 @@ def run_vmamba(args, rank, world, dev, dist):
                      "step_share": {k: round(v[0] / timer_steps / (wall / steps * 1e3), 4) for k, v in stats.items()}}}))
 
 
-def measure_scan(workload, steps, warmup, rank, world, dev, dist, no_cpu_baseline=False, one_gpu=False):
-    """One selective-scan micro-benchmark line (the kernel alone, inputs resident in HBM); returns the dict on rank 0."""
+def measure_scan(workload, steps, warmup, rank, world, dev, dist, no_cpu_baseline=False, one_gpu=False, dump_dir=None):
+    """One selective-scan micro-benchmark line (the kernel alone, inputs resident in HBM); returns the dict on rank 0.  dump_dir: the
+    arrays the last timed call returned (seeded samples of the large ones) go there (--dump-outputs)."""
     from medical_image_analysis_amd import _abi
     from medical_image_analysis_amd.selective_scan_interface import scan_fwd_raw
     B, D, L, N, dtname, desc = WORKLOADS[workload]
@@ -944,7 +1022,7 @@ def measure_scan(workload, steps, warmup, rank, world, dev, dist, no_cpu_baselin
     t0 = time.perf_counter()
     e0.record()
     for _ in range(steps):
-        step()
+        res = step()
     e1.record()
     torch.cuda.synchronize()
     if dist is not None:
@@ -956,6 +1034,9 @@ def measure_scan(workload, steps, warmup, rank, world, dev, dist, no_cpu_baselin
         t = torch.tensor([wall, kern_ms], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, kern_ms = float(t[0]), float(t[1])
+    if dump_dir and rank == 0:
+        names = ("du", "ddelta", "dA", "dB", "dC", "dD", "dz", "ddelta_bias") if backward else ("out", "last_state", "ckpt")
+        dump_outputs(dump_dir, {n: (None if r is None else sample_output(r, seed=i)) for i, (n, r) in enumerate(zip(names, res))})
 
     if rank == 0:
         images = B * world * steps
@@ -997,8 +1078,13 @@ def main():
                     choices=sorted(WORKLOADS) + sorted(PRETRAIN_WORKLOADS) + sorted(DECODE_WORKLOADS) + sorted(MAE_WORKLOADS) + sorted(VMAMBA_WORKLOADS)
                     + sorted(FINETUNE_WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override for the pre-training workloads")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the decode tokens/sec leg of the default workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, the default workload's north-star scan and decode "
+                         "legs, per-kernel roofline objects from HIP events inside the timed steps (off: set-up, warm-up, timed steps, result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the north-star scan and decode tokens/sec legs of the default workload")
     ap.add_argument("--graph", action="store_true", help="training-step workloads, one process: the whole step captured once into a hipGraph and "
                     "replayed (PretrainEngine(use_graph=True)); the launch-bound small-image steps gain, the 1024 x 1024 headline step is "
                     "GPU-bound either way -- off by default so that the N = 1 line is the same program as the N > 1 lines")
@@ -1024,6 +1110,9 @@ def main():
                     help="A/B switch of the decode step: RMSNorm fused into the consuming projection (default) or the round-4 path "
                          "(K-split o_proj / down_proj folded by explicit norm launches)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline figure only: the CPU baselines and the default workload's extra legs belong to --full
+        args.no_cpu_baseline = args.no_secondary = True
     if args.graph and (args.gpus > 1 or not (args.workload in PRETRAIN_WORKLOADS or args.workload in VMAMBA_WORKLOADS)):
         raise SystemExit("--graph: one process, a VisionMamba / ARM / VMamba training-step workload")
 
@@ -1101,7 +1190,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    out = measure_scan(args.workload, args.steps, args.warmup, rank, world, dev, dist, args.no_cpu_baseline, one_gpu)
+    out = measure_scan(args.workload, args.steps, args.warmup, rank, world, dev, dist, args.no_cpu_baseline, one_gpu, args.dump_outputs)
     if out is not None:
         print(json.dumps(out))
     if dist is not None:

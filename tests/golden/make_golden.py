@@ -1428,8 +1428,49 @@ def gen_qformer():
     save("qformer", query=np_(q), enc=np_(enc), atts=atts.numpy(), out=np_(out), out_nomask=np_(out_nomask), **arrs)
 
 
+def gen_dropin_reference():
+    """tests/golden/dropin_reference.json: the state_dict layout (names, shapes) of the modules tests/test_dropin_reference_import.py
+    compares the mirror with, built by the reference's own model files loaded on top of `dropin.install()` (as that test did at run
+    time while it read the reference checkout).  Run in a process of its own: the stubs of main() would shadow the drop-in."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    import medical_image_analysis_amd.dropin as dropin
+    dropin.install()
+    base = os.path.join(REF, "CXPMRG_Bench_MambaXray_VL")
+    layout = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
+
+    def load(rel, name, extra_path=None, fresh=()):
+        if extra_path:
+            sys.path.insert(0, extra_path)
+        for k in fresh:
+            sys.modules.pop(k, None)
+        return _load(os.path.join(base, rel), name)
+
+    rec = {"layouts": {}}
+    ft = load("arm/Finetuning/mamba_simple.py", "ref_ft_mamba_simple")
+    for bt in ("v2", "v3", "v4"):
+        rec["layouts"][f"finetuning_mamba_{bt}"] = layout(ft.Mamba(d_model=48, bimamba_type=bt))
+    pt = load("pretrain/mamba_simple.py", "ref_pt_mamba_simple")
+    rec["layouts"]["pretrain_mamba"] = layout(pt.Mamba(d_model=64, expand=1, bimamba_type="None"))
+    install_timm_stubs()
+    ft_dir, pt_dir = os.path.join(base, "arm/Finetuning"), os.path.join(base, "pretrain")
+    enc = load("arm/Finetuning/models_mamba.py", "ref_ft_models_mamba", ft_dir, ("mamba_simple", "rope")).arm_base_pz16("base")
+    rec["layouts"]["arm_encoder"] = layout(enc)
+    rec["arm_encoder"] = {"num_features": enc.num_features, "num_patches": enc.patch_embed.num_patches}
+    sys.path.remove(ft_dir)
+    rec["layouts"]["pretrain_model"] = layout(load("pretrain/models_pretrain.py", "ref_pt_models_pretrain", pt_dir,
+                                                   ("mamba_simple", "rope", "utils", "utils.pos_embed")).arm_base_pz16())
+    path = os.path.join(HERE, "dropin_reference.json")
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "lr_sched":
+    if len(sys.argv) > 1 and sys.argv[1] == "dropin_reference":
+        gen_dropin_reference()
+    elif len(sys.argv) > 1 and sys.argv[1] == "lr_sched":
         gen_lr_sched()
     elif len(sys.argv) > 1 and sys.argv[1] == "decode_batched":
         gen_decode_batched()

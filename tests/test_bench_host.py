@@ -59,3 +59,45 @@ def test_bench_help_renders():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "--workload" in r.stdout and "--decode-gemm" in r.stdout, r.stderr[-500:]
+
+
+def test_bench_help_lists_full_and_dump_outputs():
+    """A plain run measures the headline only; --full and --dump-outputs are the documented ways to ask for more."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-500:]
+
+
+def test_output_samples_are_seeded_and_bounded():
+    """The --dump-outputs samples: the same positions on every call, all of a small tensor, k elements of a large one, every
+    parameter represented in the weight sample."""
+    import torch
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float32).reshape(3, -1)
+    a, b = bench.sample_output(big, seed=3), bench.sample_output(big, seed=3)
+    assert a.shape == (bench.DUMP_SAMPLE,) and torch.equal(a, b)
+    assert not torch.equal(a, bench.sample_output(big, seed=4))
+    small = torch.randn(4, 5)
+    assert torch.equal(bench.sample_output(small), small)
+    params = [torch.randn(1000, 300), torch.randn(7), torch.randn(64, 64)]
+    s = bench.sample_params(params, k=5000)
+    assert s.dtype == torch.float32 and 5000 - len(params) <= s.numel() <= 5000 + len(params)
+    assert torch.equal(s, bench.sample_params(params, k=5000))
+    assert torch.isin(params[1], s).any()                       # the 7-element bias is not left out
+    whole = bench.sample_params(params, k=10 ** 6)              # a model below k: every weight, in order
+    assert torch.equal(whole, torch.cat([p.reshape(-1) for p in params]))
+
+
+def test_dump_outputs_writes_float_npy(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": torch.tensor([1.5], dtype=torch.bfloat16), "tokens": torch.tensor([[3, 151935]]),
+                                            "x64": torch.ones(3, dtype=torch.float64), "absent": None})
+    got = {p.name: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["loss.npy", "tokens.npy", "x64.npy"]
+    assert got["loss.npy"].dtype == np.float32 and got["loss.npy"][0] == 1.5
+    assert got["tokens.npy"].dtype == np.float32 and got["tokens.npy"].tolist() == [[3.0, 151935.0]]
+    assert got["x64.npy"].dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "e"), {"too_big": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "e").exists()

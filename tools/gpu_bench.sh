@@ -3,7 +3,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 TAG=${TAG:-bench}
-(timeout 900 python bench.py ${BENCH_ARGS:-} 2>&1 | tail -1) > $O/${TAG}_bench_default.json
+(timeout 900 python bench.py --full ${BENCH_ARGS:-} 2>&1 | tail -1) > $O/${TAG}_bench_default.json
 if [ "${PROF:-1}" = "1" ]; then
   cd /tmp && export TMPDIR=/tmp
   P=/tmp/prof_$TAG; mkdir -p $P

@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 TAG=${TAG:-r04}
 for W in ${WORKLOADS:-decode_llama7b_128 decode_llama7b_b6x3}; do
-  (timeout 600 python bench.py --workload $W --steps 3 --warmup 1 2>&1 | tail -1) > $O/${TAG}_bench_$W.json
+  (timeout 600 python bench.py --full --workload $W --steps 3 --warmup 1 2>&1 | tail -1) > $O/${TAG}_bench_$W.json
   cut -c1-420 $O/${TAG}_bench_$W.json; echo
 done
 if [ "${PROF:-1}" = "1" ]; then

@@ -34,9 +34,9 @@ rm -f $O/${TAG}_pmc_traffic.json
 python tools/pmc_traffic.py scan_bwd_pretrain scan_bwd_kernel $O/prof_${TAG}_bwd_fetch.txt $O/prof_${TAG}_bwd_write.txt $O/${TAG}_pmc_traffic.json > $O/${TAG}_pmc_traffic.log 2>&1
 python tools/pmc_traffic.py scan_fwd_target scan_fwd_stream_kernel $O/prof_${TAG}_fwd_fetch.txt $O/prof_${TAG}_fwd_write.txt $O/${TAG}_pmc_traffic.json >> $O/${TAG}_pmc_traffic.log 2>&1
 cp $O/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json     # bench.py reads the record from profiles/
-(timeout 900 python bench.py 2>&1 | tail -1) > $O/${TAG}_bench_default.json
+(timeout 900 python bench.py --full 2>&1 | tail -1) > $O/${TAG}_bench_default.json
 for w in ${WORKLOADS:-scan_bwd_pretrain scan_fwd_target scan_fwd_cfg2 scan_fwd_target_bf16 decode_llama7b_128 mae_vit_large_1280 arm_encoder_large_224 vmamba_base_224 arm_pretrain_base_192}; do
-  (timeout 600 python bench.py --workload $w 2>&1 | tail -1) > $O/${TAG}_bench_$w.json
+  (timeout 600 python bench.py --full --workload $w 2>&1 | tail -1) > $O/${TAG}_bench_$w.json
 done
 (timeout 300 python tools/scan_r03_bench.py all 2 2>&1 | grep -v amdgpu.ids) > $O/${TAG}_scan_variants.txt
 (timeout 300 python tools/gemm_swiglu_bench.py 3 2>&1 | grep -v amdgpu.ids) > $O/${TAG}_gemm_swiglu_bench.txt

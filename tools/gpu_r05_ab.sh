@@ -50,7 +50,7 @@ case "$1" in
   secondary)
     line decode_llama7b_128
     for n in 1 3 8; do
-      timeout 900 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --secondary-warmup $n 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('decode leg after the training leg, $n warm-up generate():', round(d['secondary']['value'],1), 'tok/s | images/s', round(d['value'],2))"
+      timeout 900 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --secondary-warmup $n 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('decode leg after the training leg, $n warm-up generate():', round(d['secondary']['value'],1), 'tok/s | images/s', round(d['value'],2))"
     done ;;
   timelines)
     P=/tmp/prof_ab; mkdir -p $P; R=$(pwd)

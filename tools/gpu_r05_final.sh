@@ -47,11 +47,11 @@ rm -f $O/${TAG}_pmc_traffic.json
 python tools/pmc_traffic.py scan_bwd_pretrain scan_bwd_kernel $O/prof_${TAG}_bwd_fetch.txt $O/prof_${TAG}_bwd_write.txt $O/${TAG}_pmc_traffic.json > $O/${TAG}_pmc_traffic.log 2>&1
 python tools/pmc_traffic.py scan_fwd_target scan_fwd_stream_kernel $O/prof_${TAG}_fwd_fetch.txt $O/prof_${TAG}_fwd_write.txt $O/${TAG}_pmc_traffic.json >> $O/${TAG}_pmc_traffic.log 2>&1
 cp $O/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json     # bench.py reads the record from profiles/
-(timeout 900 python bench.py 2>&1 | tail -1) > $O/${TAG}_bench_default.json
+(timeout 900 python bench.py --full 2>&1 | tail -1) > $O/${TAG}_bench_default.json
 fi
 [ $PARTS = decode ] && WORKLOADS=${WORKLOADS:-decode_llama7b_b6x3 decode_llama7b_b6x3_fp16 decode_llama7b_b8x3 decode_llama7b_b16x3 decode_llama7b_b16x5 decode_qwen1p8b_b16x5 decode_llama7b_128 decode_qwen1p8b_b1x5}
 for w in ${WORKLOADS:-scan_bwd_pretrain scan_fwd_target scan_fwd_cfg2 scan_fwd_target_bf16 decode_llama7b_128 decode_llama7b_128_fp16 decode_llama7b_b6x3 decode_llama7b_b6x3_fp16 decode_llama7b_b8x3 decode_llama7b_b16x3 decode_llama7b_b16x5 decode_qwen1p8b_b16x5 decode_qwen1p8b_b1x5 finetune_stage3_llama7b r2gencsr_step mae_vit_large_1280 arm_encoder_large_224 vmamba_base_224 arm_pretrain_base_192}; do
-  (timeout 600 python bench.py --workload $w 2>&1 | tail -1) > $O/${TAG}_bench_$w.json
+  (timeout 600 python bench.py --full --workload $w 2>&1 | tail -1) > $O/${TAG}_bench_$w.json
 done
 (timeout 300 python tools/decode_gemm_bench.py 3 18 24 48 80 2>&1 | grep -v amdgpu.ids) > $O/${TAG}_decode_gemm_bench.txt
 if [ $PARTS = all ]; then

@@ -27,7 +27,7 @@ for w in workloads:
     # MXVL_TUNE_BUDGET_S bounds one workload's session: at the deadline the child gets SIGINT, so the interpreter exits normally and
     # TunableOp still writes the shapes it has finished (a `timeout` SIGTERM around this script loses the whole session's results)
     child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--steps", "2", "--warmup", "1",
-                              "--no-cpu-baseline"] + batch, env=env, cwd=ROOT)
+                              "--full", "--no-cpu-baseline"] + batch, env=env, cwd=ROOT)
     try:
         rc = child.wait(timeout=float(os.environ.get("MXVL_TUNE_BUDGET_S", "1e9")))
         if rc != 0:
