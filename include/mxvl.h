@@ -773,7 +773,9 @@ int64_t mxvl_mamba_inner_bwd_workspace_bytes(const mxvl_mamba_inner_desc *fwd);
 int mxvl_mamba_inner_fwd(const mxvl_mamba_inner_desc *desc, void *hip_stream);
 int mxvl_mamba_inner_bwd(const mxvl_mamba_inner_bwd_desc *desc, void *hip_stream);
 
-/* last hipError_t observed by a failing launch on this thread (0 = hipSuccess) */
+/* last failing hipError_t of this thread (0 = none yet): every entry that returns MXVL_ERR_LAUNCH for a HIP failure -- a kernel
+ * launch, an LDS opt-in (hipFuncSetAttribute), an async memset -- records it here.  Sticky: a later success does not reset it.
+ * rocBLAS failures inside mxvl_mamba_inner_* are not HIP errors: they return MXVL_ERR_LAUNCH and record nothing. */
 int mxvl_last_hip_error(void);
 /* ---- DIAGNOSTICS (not part of the drop-in surface; no caller of the reference's interface needs them) -------------------------
  * They stay in the product library on purpose: the parity tests must run against the SAME .so the product loads (the driver records

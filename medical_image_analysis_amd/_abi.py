@@ -26,22 +26,7 @@ STATUS = {
     0: "MXVL_OK", -1: "MXVL_ERR_NULL", -2: "MXVL_ERR_DTYPE", -3: "MXVL_ERR_SHAPE", -4: "MXVL_ERR_DSTATE",
     -5: "MXVL_ERR_STRIDE", -6: "MXVL_ERR_LAUNCH", -7: "MXVL_ERR_UNSUPPORTED", -8: "MXVL_ERR_CHECKPOINT",
 }
-
-# every symbol include/mxvl.h declares (tests/test_abi.py checks the .so exports all of them)
-SYMBOLS = [
-    "mxvl_abi_version", "mxvl_scan_chunk_len", "mxvl_scan_n_chunks", "mxvl_scan_fold_ok", "mxvl_scan_fold_slots", "mxvl_scan_fwd", "mxvl_scan_bwd",
-    "mxvl_scan_bwd_workspace_bytes",
-    "mxvl_conv1d_fwd", "mxvl_conv1d_bwd", "mxvl_conv1d_update", "mxvl_state_update",
-    "mxvl_last_hip_error", "mxvl_set_scan_variant", "mxvl_last_scan_kernel", "mxvl_decode_gemv", "mxvl_decode_attn",
-    "mxvl_decode_cross_attn", "mxvl_decode_prologue", "mxvl_decode_rmsnorm",
-    "mxvl_cross_scan", "mxvl_cross_merge",
-    "mxvl_add_layernorm_fwd", "mxvl_add_layernorm_bwd", "mxvl_add_layernorm_partials", "mxvl_swiglu_fwd", "mxvl_swiglu_bwd",
-    "mxvl_swiglu_partials", "mxvl_swiglu_bwd_colsum", "mxvl_gemm_swiglu_fwd", "mxvl_gemm_swiglu_bwd", "mxvl_gemm_swiglu_bwd_partials", "mxvl_set_decode_gemm_wide", "mxvl_decode_gemm_plan", "mxvl_gemm_nt", "mxvl_gemm_tn", "mxvl_colsum", "mxvl_colsum_partials", "mxvl_row_gather", "mxvl_patch_loss", "mxvl_patch_cols", "mxvl_beam_workspace_bytes",
-    "mxvl_dwconv2d_fwd", "mxvl_dwconv2d_bwd", "mxvl_beam_step", "mxvl_dir_gather", "mxvl_dir_merge",
-    "mxvl_resample_ksize", "mxvl_resample_coeffs", "mxvl_image_preprocess", "mxvl_attn_fwd", "mxvl_attn_bwd", "mxvl_clip_loss",
-    "mxvl_rope", "mxvl_rmsnorm_train_fwd", "mxvl_rmsnorm_train_bwd", "mxvl_silu_mul",
-    "mxvl_window_cols", "mxvl_mamba_inner_fwd", "mxvl_mamba_inner_bwd", "mxvl_mamba_inner_workspace_bytes", "mxvl_mamba_inner_bwd_workspace_bytes",
-]
+MXVL_ERR_LAUNCH = -6
 
 
 class ScanDesc(ctypes.Structure):
@@ -276,6 +261,85 @@ class ImageDesc(ctypes.Structure):
     ]
 
 
+_P, _I, _I64 = c_void_p, c_int, c_int64
+_DESC = (_I, [_P, _P])        # (const mxvl_*_desc* desc, void* hip_stream)
+
+# every function include/mxvl.h declares: name -> (restype, argtypes).  load() applies it; tests/test_abi.py holds it to the header's
+# prototypes (arity and type class per parameter) and checks the .so exports every name
+SIGNATURES = {
+    "mxvl_abi_version": (_I, []),
+    "mxvl_last_hip_error": (_I, []),
+    # selective scan
+    "mxvl_scan_chunk_len": (_I, [_I, _I]),
+    "mxvl_scan_n_chunks": (_I, [_I, _I]),
+    "mxvl_scan_fold_ok": (_I, [_I, _I, _I]),
+    "mxvl_scan_fold_slots": (_I, [_I, _I, _I, _I]),
+    "mxvl_scan_fwd": _DESC,
+    "mxvl_scan_bwd": _DESC,
+    "mxvl_scan_bwd_workspace_bytes": (_I64, [_P]),
+    "mxvl_set_scan_variant": (None, [_I]),
+    "mxvl_last_scan_kernel": (ctypes.c_char_p, []),
+    "mxvl_state_update": (_I, [_P] * 10 + [_I] * 5 + [_P]),
+    # causal conv1d
+    "mxvl_conv1d_fwd": _DESC,
+    "mxvl_conv1d_bwd": _DESC,
+    "mxvl_conv1d_update": (_I, [_P] * 5 + [_I] * 5 + [_P]),
+    # fused Mamba inner block
+    "mxvl_mamba_inner_fwd": _DESC,
+    "mxvl_mamba_inner_bwd": _DESC,
+    "mxvl_mamba_inner_workspace_bytes": (_I64, [_P]),
+    "mxvl_mamba_inner_bwd_workspace_bytes": (_I64, [_P]),
+    # report decoder
+    "mxvl_decode_gemv": _DESC,
+    "mxvl_decode_gemm_plan": (_I, [ctypes.POINTER(GemvDesc), ctypes.POINTER(c_int32)]),
+    "mxvl_set_decode_gemm_wide": (_I, [_I]),
+    "mxvl_decode_attn": _DESC,
+    "mxvl_decode_cross_attn": _DESC,
+    "mxvl_decode_prologue": _DESC,
+    "mxvl_decode_rmsnorm": _DESC,
+    "mxvl_beam_step": _DESC,
+    "mxvl_beam_workspace_bytes": (_I64, [_I] * 3),
+    # VMamba / VisionMamba
+    "mxvl_cross_scan": (_I, [_P, _P] + [_I] * 5 + [_P]),
+    "mxvl_cross_merge": (_I, [_P, _P] + [_I] * 5 + [_P]),
+    "mxvl_dir_gather": _DESC,
+    "mxvl_dir_merge": _DESC,
+    "mxvl_dwconv2d_fwd": (_I, [_P] * 4 + [_I] * 7 + [_P]),
+    "mxvl_dwconv2d_bwd": (_I, [_P] * 7 + [_I] * 7 + [_P]),
+    "mxvl_window_cols": (_I, [_P] * 3 + [_I] * 8 + [_P]),
+    # norms, MLP, GEMMs
+    "mxvl_add_layernorm_fwd": _DESC,
+    "mxvl_add_layernorm_bwd": _DESC,
+    "mxvl_add_layernorm_partials": (_I, [_I]),
+    "mxvl_swiglu_fwd": (_I, [_P, _P, _I, _I, _I, _P]),
+    "mxvl_swiglu_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "mxvl_swiglu_partials": (_I, [_I, _I]),
+    "mxvl_swiglu_bwd_colsum": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "mxvl_gemm_swiglu_fwd": _DESC,
+    "mxvl_gemm_swiglu_bwd": _DESC,
+    "mxvl_gemm_swiglu_bwd_partials": (_I, [_I]),
+    "mxvl_gemm_nt": _DESC,
+    "mxvl_gemm_tn": _DESC,
+    "mxvl_colsum": (_I, [_P, _P, _I, _I, _I64, _I, _I, _P]),
+    "mxvl_colsum_partials": (_I, [_I, _I]),
+    "mxvl_rope": _DESC,
+    "mxvl_rmsnorm_train_fwd": _DESC,
+    "mxvl_rmsnorm_train_bwd": _DESC,
+    "mxvl_silu_mul": (_I, [_P] * 5 + [_I64, _I, _P]),
+    "mxvl_attn_fwd": _DESC,
+    "mxvl_attn_bwd": _DESC,
+    # pre-training and image input
+    "mxvl_row_gather": (_I, [_P] * 5 + [_I] * 4 + [_I64] * 2 + [_I] * 2 + [_P]),
+    "mxvl_patch_loss": (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    "mxvl_patch_cols": (_I, [_P] * 2 + [_I] * 7 + [_P]),
+    "mxvl_clip_loss": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mxvl_resample_ksize": (_I, [_I, _I, _I]),
+    "mxvl_resample_coeffs": (_I, [_I, _I, _I, _P, _P]),
+    "mxvl_image_preprocess": _DESC,
+}
+SYMBOLS = list(SIGNATURES)
+
+
 _lib = None
 
 
@@ -292,90 +356,9 @@ def load() -> ctypes.CDLL:
     lib.mxvl_abi_version.restype = c_int
     if lib.mxvl_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libmxvl.so ABI {lib.mxvl_abi_version()} != binding ABI {ABI_VERSION}: rebuild")
-    lib.mxvl_last_scan_kernel.restype = ctypes.c_char_p
-    lib.mxvl_scan_bwd_workspace_bytes.restype = c_int64
-    for name in ("mxvl_scan_fwd", "mxvl_scan_bwd", "mxvl_conv1d_fwd", "mxvl_conv1d_bwd", "mxvl_decode_gemv", "mxvl_decode_attn",
-                 "mxvl_decode_cross_attn", "mxvl_attn_fwd", "mxvl_attn_bwd", "mxvl_gemm_swiglu_fwd", "mxvl_gemm_swiglu_bwd", "mxvl_gemm_nt", "mxvl_gemm_tn"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    for name in ("mxvl_mamba_inner_fwd", "mxvl_mamba_inner_bwd"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    for name in ("mxvl_mamba_inner_workspace_bytes", "mxvl_mamba_inner_bwd_workspace_bytes"):
-        getattr(lib, name).restype = c_int64
-        getattr(lib, name).argtypes = [c_void_p]
-    lib.mxvl_conv1d_update.restype = c_int
-    lib.mxvl_conv1d_update.argtypes = [c_void_p] * 5 + [c_int] * 5 + [c_void_p]
-    lib.mxvl_state_update.restype = c_int
-    lib.mxvl_state_update.argtypes = [c_void_p] * 10 + [c_int] * 5 + [c_void_p]
-    for name in ("mxvl_dir_gather", "mxvl_dir_merge"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    lib.mxvl_beam_step.restype = c_int
-    lib.mxvl_beam_step.argtypes = [c_void_p, c_void_p]
-    for name in ("mxvl_decode_prologue", "mxvl_decode_rmsnorm"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    for name in ("mxvl_rope", "mxvl_rmsnorm_train_fwd", "mxvl_rmsnorm_train_bwd"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    lib.mxvl_silu_mul.restype = c_int
-    lib.mxvl_silu_mul.argtypes = [c_void_p] * 5 + [c_int64, c_int, c_void_p]
-    for name in ("mxvl_add_layernorm_fwd", "mxvl_add_layernorm_bwd"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p]
-    lib.mxvl_add_layernorm_partials.restype = c_int
-    lib.mxvl_add_layernorm_partials.argtypes = [c_int]
-    lib.mxvl_gemm_swiglu_bwd_partials.restype = c_int
-    lib.mxvl_gemm_swiglu_bwd_partials.argtypes = [c_int]
-    lib.mxvl_set_decode_gemm_wide.restype = c_int
-    lib.mxvl_set_decode_gemm_wide.argtypes = [c_int]
-    lib.mxvl_decode_gemm_plan.restype = c_int
-    lib.mxvl_decode_gemm_plan.argtypes = [ctypes.POINTER(GemvDesc), ctypes.POINTER(c_int32)]
-    lib.mxvl_swiglu_fwd.restype = c_int
-    lib.mxvl_swiglu_fwd.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-    lib.mxvl_swiglu_bwd.restype = c_int
-    lib.mxvl_swiglu_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-    lib.mxvl_swiglu_partials.restype = c_int
-    lib.mxvl_swiglu_partials.argtypes = [c_int, c_int]
-    lib.mxvl_colsum_partials.restype = c_int
-    lib.mxvl_colsum_partials.argtypes = [c_int, c_int]
-    lib.mxvl_colsum.restype = c_int
-    lib.mxvl_colsum.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p]
-    lib.mxvl_swiglu_bwd_colsum.restype = c_int
-    lib.mxvl_swiglu_bwd_colsum.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.mxvl_dwconv2d_fwd.restype = c_int
-    lib.mxvl_dwconv2d_fwd.argtypes = [c_void_p] * 4 + [c_int] * 7 + [c_void_p]
-    lib.mxvl_dwconv2d_bwd.restype = c_int
-    lib.mxvl_dwconv2d_bwd.argtypes = [c_void_p] * 7 + [c_int] * 7 + [c_void_p]
-    for name in ("mxvl_cross_scan", "mxvl_cross_merge"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]
-    lib.mxvl_resample_ksize.restype = c_int
-    lib.mxvl_resample_ksize.argtypes = [c_int, c_int, c_int]
-    lib.mxvl_resample_coeffs.restype = c_int
-    lib.mxvl_resample_coeffs.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.mxvl_image_preprocess.restype = c_int
-    lib.mxvl_image_preprocess.argtypes = [c_void_p, c_void_p]
-    lib.mxvl_clip_loss.restype = c_int
-    lib.mxvl_clip_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.mxvl_row_gather.restype = c_int
-    lib.mxvl_row_gather.argtypes = [c_void_p] * 5 + [c_int] * 4 + [c_int64] * 2 + [c_int] * 2 + [c_void_p]
-    lib.mxvl_patch_loss.restype = c_int
-    lib.mxvl_patch_loss.argtypes = [c_void_p] * 5 + [c_int] * 6 + [c_void_p]
-    lib.mxvl_beam_workspace_bytes.restype = c_int64
-    lib.mxvl_beam_workspace_bytes.argtypes = [c_int] * 3
-    lib.mxvl_window_cols.restype = c_int
-    lib.mxvl_window_cols.argtypes = [c_void_p] * 3 + [c_int] * 8 + [c_void_p]
-    lib.mxvl_patch_cols.restype = c_int
-    lib.mxvl_patch_cols.argtypes = [c_void_p] * 2 + [c_int] * 7 + [c_void_p]
-    lib.mxvl_scan_chunk_len.restype = c_int
-    lib.mxvl_scan_n_chunks.restype = c_int
-    lib.mxvl_scan_fold_ok.restype = c_int
-    lib.mxvl_scan_fold_ok.argtypes = [c_int, c_int, c_int]
-    lib.mxvl_scan_fold_slots.restype = c_int
-    lib.mxvl_scan_fold_slots.argtypes = [c_int, c_int, c_int, c_int]
-    lib.mxvl_set_scan_variant.argtypes = [c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -414,6 +397,6 @@ def require_gpu(*tensors) -> torch.device:
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        lib = load()
-        hip = lib.mxvl_last_hip_error()
-        raise RuntimeError(f"{what} failed: {STATUS.get(rc, rc)} (hipError {hip})")
+        # the thread's last hipError belongs to this call only when it failed a launch; a validation failure did not touch HIP
+        hip = f" (hipError {load().mxvl_last_hip_error()})" if rc == MXVL_ERR_LAUNCH else ""
+        raise RuntimeError(f"{what} failed: {STATUS.get(rc, rc)}{hip}")

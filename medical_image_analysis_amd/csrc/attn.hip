@@ -1184,19 +1184,11 @@ __global__ __launch_bounds__(NW * 64, (D >= 128 || sizeof(E) == 4) ? 1 : 2) void
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------
-static thread_local int g_attn_hip_error = 0;
-
-static int attn_launch_check() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_attn_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
-}
-
 template <typename K>
 static int raise_lds(K kern, size_t lds) {
   if (lds > 64 * 1024) {
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXVL_ERR_LAUNCH;
+    return hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   return MXVL_OK;
 }
@@ -1211,7 +1203,7 @@ static int launch_q1(const AttnArgs& a, hipStream_t s) {
   if (rc != MXVL_OK) return rc;
   dim3 grid(a.H * a.batch, (a.Lq + NW * 32 - 1) / (NW * 32), 1);
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return attn_launch_check();
+  return launch_status();
 }
 template <typename E, bool DQ>
 static int launch_fwd64(const AttnArgs& a, hipStream_t s) {
@@ -1219,7 +1211,7 @@ static int launch_fwd64(const AttnArgs& a, hipStream_t s) {
   dim3 grid(a.H * a.batch, (a.Lq + 255) / 256, 1);
   if constexpr (DQ) hipLaunchKernelGGL(attn_dq64_kernel<E>, grid, dim3(256), lds, s, a);
   else hipLaunchKernelGGL(attn_fwd64_kernel<E>, grid, dim3(256), lds, s, a);
-  return attn_launch_check();
+  return launch_status();
 }
 template <typename E, int D, bool DQ>
 static int launch_q(const AttnArgs& a, hipStream_t s) {
@@ -1253,7 +1245,7 @@ static int launch_dkv1(const AttnArgs& a, hipStream_t s) {
   if (rc != MXVL_OK) return rc;
   dim3 grid(a.Hkv * a.batch, (a.Lk + NW * 32 - 1) / (NW * 32), 1);
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return attn_launch_check();
+  return launch_status();
 }
 
 template <typename E>

@@ -685,17 +685,14 @@ extern "C" int mxvl_beam_step(const mxvl_beam_desc* d, void* hip_stream) {
     const size_t words = a.ws_cand_v ? 0 : (size_t)((a.V < tile ? a.V : tile) + 31) / 32;
     const size_t lds = 4 * ((a.nb * words + 1) & ~(size_t)1) + 8 * (size_t)2 * a.nb * a.max_new;
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;          // max_new in the thousands
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (lds > 48 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
       return MXVL_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, (hipStream_t)hip_stream, a);
-    return MXVL_OK;
+    return launch_status();
   };
-  int rc;
   if (a.ws_cand_v && a.S * a.keep <= 256)       // merge + bookkeeping only: four waves (barriers and the serial lane are all that is left)
-    rc = launch(beam_step_kernel<256, 8>, 256, 256 * 8);
-  else if (MXVL_ABL(shape == 1) || (a.ws_cand_v && a.S * a.keep <= 512))
-    rc = launch(beam_step_kernel<512, 16>, 512, 512 * 16);
-  else rc = launch(beam_step_kernel<1024, 32>, 1024, 1024 * 32);
-  if (rc != MXVL_OK) return rc;
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+    return launch(beam_step_kernel<256, 8>, 256, 256 * 8);
+  if (MXVL_ABL(shape == 1) || (a.ws_cand_v && a.S * a.keep <= 512))
+    return launch(beam_step_kernel<512, 16>, 512, 512 * 16);
+  return launch(beam_step_kernel<1024, 32>, 1024, 1024 * 32);
 }

@@ -118,5 +118,5 @@ extern "C" int mxvl_clip_loss(const float* image_features, const float* text_fea
   if (lds > 64 * 1024) return MXVL_ERR_UNSUPPORTED;      // batch <= 89 (the reference trains stage 2 at batch 48)
   ClipArgs a{batch, dim, logit_scale, image_features, text_features, loss, d_image, d_text, d_logit_scale};
   hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(1024), lds, (hipStream_t)hip_stream, a);
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }

@@ -468,11 +468,6 @@ static bool rows_aligned(const void* base, int64_t bs, int64_t ds, int io_dtype)
   return base && ((uintptr_t)base % al) == 0 && bs % 4 == 0 && ds % 4 == 0;
 }
 
-static int check_launch() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
-}
-
 static int conv_check(const mxvl_conv1d_desc* d) {
   if (!d || !d->x || !d->weight) return MXVL_ERR_NULL;
   if (d->io_dtype != MXVL_F32 && d->io_dtype != MXVL_BF16 && d->io_dtype != MXVL_F16) return MXVL_ERR_DTYPE;
@@ -512,7 +507,7 @@ int mxvl_conv1d_fwd(const mxvl_conv1d_desc* d, void* hip_stream) {
     case MXVL_BF16: MXVL_CONV_FWD(bf16_t); break;
     default: MXVL_CONV_FWD(f16_t); break;
   }
-  return check_launch();
+  return launch_status();
 }
 
 int mxvl_conv1d_bwd(const mxvl_conv1d_bwd_desc* d, void* hip_stream) {
@@ -551,7 +546,7 @@ int mxvl_conv1d_bwd(const mxvl_conv1d_bwd_desc* d, void* hip_stream) {
     case MXVL_BF16: MXVL_CONV_BWD(bf16_t); break;
     default: MXVL_CONV_BWD(f16_t); break;
   }
-  return check_launch();
+  return launch_status();
 }
 
 int mxvl_conv1d_update(const void* x, void* conv_state, const void* weight, const void* bias, void* y, int batch,
@@ -575,7 +570,7 @@ int mxvl_conv1d_update(const void* x, void* conv_state, const void* weight, cons
       break;
     default: return MXVL_ERR_DTYPE;
   }
-  return check_launch();
+  return launch_status();
 }
 
 int mxvl_state_update(void* state, const void* x, const void* dt, const void* A, const void* B, const void* C,
@@ -603,7 +598,7 @@ int mxvl_state_update(void* state, const void* x, const void* dt, const void* A,
       break;
     default: return MXVL_ERR_DTYPE;
   }
-  return check_launch();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -229,7 +229,7 @@ static int launch_cross(bool merge, const void* in, void* out, int B, int C, int
       if (v4) hipLaunchKernelGGL((cross_scan_flat_kernel<io_t, 4>), grid, dim3(256), lds, s, (const io_t*)in, (io_t*)out, g);
       else hipLaunchKernelGGL((cross_scan_flat_kernel<io_t, 1>), grid, dim3(256), lds, s, (const io_t*)in, (io_t*)out, g);
     }
-    return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+    return launch_status();
   }
   const int planes = B * C;
   const dim3 grid(((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile), planes < 65535 ? planes : 65535);
@@ -237,7 +237,7 @@ static int launch_cross(bool merge, const void* in, void* out, int B, int C, int
     hipLaunchKernelGGL(cross_merge_kernel<io_t>, grid, dim3(256), 0, s, (const io_t*)in, (io_t*)out, planes, C, H, W);
   else
     hipLaunchKernelGGL(cross_scan_kernel<io_t>, grid, dim3(256), 0, s, (const io_t*)in, (io_t*)out, planes, C, H, W);
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 static int cross_dispatch(bool merge, const void* in, void* out, int B, int C, int H, int W, int dtype, void* stream) {

@@ -866,21 +866,16 @@ __global__ __launch_bounds__(256) void decode_prologue_kernel(const PrologueArgs
   if (gtid == 0) *p.pos = pos;
 }
 
-static int dec_check() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
-}
-
 template <typename E, int M>
 static int launch_gemv(const GemvArgs& a, hipStream_t s) {
   const int grid = std::max(1, std::min(256, (a.N + 15) / 16));
   const size_t lds = (size_t)M * a.K * sizeof(uint16_t);
   if (lds > 150 * 1024) return MXVL_ERR_UNSUPPORTED;  // rows * K bf16 must fit one CU's LDS
   // per call: the attribute belongs to the (kernel, device) pair, and a process may drive several devices
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)gemv_kernel<E, M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)gemv_kernel<E, M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
   hipLaunchKernelGGL((gemv_kernel<E, M>), dim3(grid), dim3(1024), lds, s, a);
-  return MXVL_OK;
+  return launch_status();
 }
 
 template <typename E>
@@ -917,7 +912,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
 #define MXVL_ATTN_BEAMS(DD, NB)                                                                                                    \
   do {                                                                                                                             \
     void (*kern)(const AttnArgs) = nw == 8 ? decode_attn_beams_mfma_kernel<E, DD, NB, (DD <= 128 ? 8 : 4)> : decode_attn_beams_mfma_kernel<E, DD, NB, 4>; \
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
+    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
       return MXVL_ERR_LAUNCH;                                                                                                      \
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);                                                                              \
   } while (0)
@@ -935,7 +930,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
     }
 #undef MXVL_ATTN_BEAMS_D
 #undef MXVL_ATTN_BEAMS
-    return dec_check();
+    return launch_status();
   }
   const int nw = attn_waves_env() ? attn_waves_env() : kAttnWaves;
   const int NG = nw * 64 / (a.D / 8);
@@ -952,7 +947,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
   do { \
     void (*kern)(const AttnArgs) = nw == 16 ? (depth == 8 ? decode_attn_kernel<E, DD, 16, 4> : depth == 4 ? decode_attn_kernel<E, DD, 16, 4> : decode_attn_kernel<E, DD, 16, 2>) \
                                             : (depth == 8 ? decode_attn_kernel<E, DD, 8, 8> : depth == 4 ? decode_attn_kernel<E, DD, 8, 4> : decode_attn_kernel<E, DD, 8, 2>); \
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
+    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
       return MXVL_ERR_LAUNCH; \
     hipLaunchKernelGGL(kern, grid, block, lds, s, a); \
   } while (0)
@@ -963,7 +958,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
     default: return MXVL_ERR_UNSUPPORTED;
   }
 #undef MXVL_ATTN_ROW
-  return dec_check();
+  return launch_status();
 }
 
 template <typename E>
@@ -1011,8 +1006,7 @@ int mxvl_decode_gemv(const mxvl_gemv_desc* d, void* hip_stream) {
   a.x = (const uint16_t*)d->x; a.g = (const uint16_t*)d->norm_weight; a.W = (const uint16_t*)d->W;
   a.W2 = (const uint16_t*)d->W2; a.bias = (const uint16_t*)d->bias; a.res = (const uint16_t*)d->residual; a.y = d->y;
   hipStream_t s = (hipStream_t)hip_stream;
-  const int rc = decode_dtype(d->dtype) == MXVL_F16 ? launch_gemv_rows<EltF16>(a, s) : launch_gemv_rows<EltBf16>(a, s);
-  return rc != MXVL_OK ? rc : dec_check();
+  return decode_dtype(d->dtype) == MXVL_F16 ? launch_gemv_rows<EltF16>(a, s) : launch_gemv_rows<EltBf16>(a, s);
 }
 
 int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
@@ -1051,7 +1045,7 @@ int mxvl_decode_prologue(const mxvl_decode_prologue_desc* d, void* hip_stream) {
   if (a.rows <= 8) hipLaunchKernelGGL(decode_prologue_kernel<8>, grid, dim3(256), 0, s, a);
   else if (a.rows <= 32) hipLaunchKernelGGL(decode_prologue_kernel<32>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(decode_prologue_kernel<80>, grid, dim3(256), 0, s, a);
-  return dec_check();
+  return launch_status();
 }
 
 int mxvl_decode_cross_attn(const mxvl_decode_cross_attn_desc* d, void* hip_stream) {
@@ -1075,7 +1069,7 @@ int mxvl_decode_cross_attn(const mxvl_decode_cross_attn_desc* d, void* hip_strea
   hipStream_t s = (hipStream_t)hip_stream;
   if (decode_dtype(d->dtype) == MXVL_F16) launch_cross_attn<EltF16>(a, grid, block, lds, s);
   else launch_cross_attn<EltBf16>(a, grid, block, lds, s);
-  return dec_check();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -20,10 +20,10 @@ static int launch_dma(const DecodeGemmArgs& a, int splits, hipStream_t s) {
     if constexpr (norm_fits) kern = decode_gemm_dma_kernel<E, MT, R, NW, PF, true>;
     else kern = decode_gemm_dma_kernel<E, MT, R, NW, (PF > 2 ? PF - 1 : 2), true>;
   }
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;   // per call: the attribute is per device
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return MXVL_OK;
+  return launch_status();
 }
 
 // any K % 8 == 0: fragments loaded straight into the MFMA operands
@@ -34,10 +34,10 @@ static int launch_direct(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
   const size_t lds = (size_t)NW * 2 * MT * 1024;
   auto kern = decode_gemm_kernel<E, MT, R, NW, PF>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return MXVL_OK;
+  return launch_status();
 }
 
 // MT >= 2 (17..80 rows), K % 64 == 0, >= 64 workgroups: the waves split N, activations shared through LDS (decode_gemm_wide_kernel)
@@ -60,10 +60,10 @@ static int launch_wide_pf(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
   const size_t lds = (size_t)PF * (MT * 2048 + NW * R * 2048);
   auto kern = decode_gemm_wide_kernel<E, MT, R, NW, PF>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return MXVL_OK;
+  return launch_status();
 }
 
 template <typename E, int MT, int R, int NW = 4>
@@ -166,9 +166,7 @@ int decode_gemm_dispatch(const mxvl_gemv_desc* d, hipStream_t s) {
   int splits = 1;
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
-  const int rc = decode_dtype(d->dtype) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
-  if (rc != MXVL_OK) return rc;
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return decode_dtype(d->dtype) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
 }
 
 // the wide kernel's ring depth for a plan, as launch_wide picks it
@@ -254,7 +252,7 @@ extern "C" int mxvl_decode_rmsnorm(const mxvl_rmsnorm_desc* d, void* hip_stream)
     default: MXVL_RMSNORM(0); break;
   }
 #undef MXVL_RMSNORM
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 /* diagnostic / A-B switch (tools, bench.py --decode-gemm): 0 = the K-split kernels at every row count (round 4), 1 = waves split N with

@@ -392,7 +392,7 @@ static int perm_launch(bool merge, const mxvl_dir_perm_desc* d, void* stream) {
     default: return MXVL_ERR_DTYPE;
   }
 #undef MXVL_PERM
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace mxvl

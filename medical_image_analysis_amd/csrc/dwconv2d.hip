@@ -239,7 +239,7 @@ int mxvl_dwconv2d_fwd(const void* x, const void* weight, const void* bias, void*
     case MXVL_BF16: MXVL_DW_LAUNCH(dwconv_fwd_kernel, bf16_t); break;
     default: MXVL_DW_LAUNCH(dwconv_fwd_kernel, f16_t); break;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 int mxvl_dwconv2d_bwd(const void* x, const void* weight, const void* bias, const void* dy, void* dx, void* dweight,
@@ -263,7 +263,7 @@ int mxvl_dwconv2d_bwd(const void* x, const void* weight, const void* bias, const
     case MXVL_BF16: MXVL_DW_LAUNCH(dwconv_bwd_kernel, bf16_t); break;
     default: MXVL_DW_LAUNCH(dwconv_bwd_kernel, f16_t); break;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

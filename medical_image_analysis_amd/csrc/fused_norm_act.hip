@@ -550,7 +550,7 @@ static int launch_swiglu(const void* ab, const void* dy, void* out, int rows, in
     const int grid = (int)std::min<size_t>((work + 255) / 256, 256 * 64);
     hipLaunchKernelGGL((swiglu_scalar_kernel<io_t, BWD>), dim3(grid), dim3(256), 0, s, (const io_t*)ab, (const io_t*)dy, (io_t*)out, rows, H);
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 template <bool BWD>
 static int dispatch_swiglu(const void* ab, const void* dy, void* out, int rows, int H, int dt, hipStream_t s) {
@@ -591,7 +591,7 @@ static int dispatch_k(bool bwd, const void* args, int rows, int C, hipStream_t s
       case 192: launch_ln<R, B, O, 3, 16>(bwd, args, rows, s); break;
       default: launch_ln_any<R, B, O>(bwd, args, rows, s); break;
     }
-    return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+    return launch_status();
   }
   switch (C / 256) {
     case 1: launch_ln<R, B, O, 1>(bwd, args, rows, s); break;
@@ -602,7 +602,7 @@ static int dispatch_k(bool bwd, const void* args, int rows, int C, hipStream_t s
     case 8: launch_ln<R, B, O, 8>(bwd, args, rows, s); break;
     default: launch_ln_any<R, B, O>(bwd, args, rows, s); break;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 static int dispatch_ln(bool bwd, const void* args, int rows, int C, int res_dt, int br_dt, int out_dt, hipStream_t s) {
   if (res_dt == MXVL_F32 && br_dt == MXVL_F32 && out_dt == MXVL_F32) return dispatch_k<float, float, float>(bwd, args, rows, C, s);
@@ -677,7 +677,7 @@ int mxvl_swiglu_bwd_colsum(const void* ab, const void* dy, void* dab, void* part
   if (vec) {
     if (io_dtype == MXVL_BF16) hipLaunchKernelGGL(swiglu_bwd_colsum_vec_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)ab, (const bf16_t*)dy, (bf16_t*)dab, (float*)partial, rows, hidden, n_partials);
     else hipLaunchKernelGGL(swiglu_bwd_colsum_vec_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)ab, (const f16_t*)dy, (f16_t*)dab, (float*)partial, rows, hidden, n_partials);
-    return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+    return launch_status();
   }
   switch (io_dtype) {
     case MXVL_F32: hipLaunchKernelGGL(swiglu_bwd_colsum_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)ab, (const float*)dy, (float*)dab, (float*)partial, rows, hidden, n_partials); break;
@@ -685,7 +685,7 @@ int mxvl_swiglu_bwd_colsum(const void* ab, const void* dy, void* dab, void* part
     case MXVL_F16: hipLaunchKernelGGL(swiglu_bwd_colsum_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)ab, (const f16_t*)dy, (f16_t*)dab, (float*)partial, rows, hidden, n_partials); break;
     default: return MXVL_ERR_DTYPE;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

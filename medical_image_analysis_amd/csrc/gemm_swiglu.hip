@@ -468,20 +468,16 @@ __global__ __launch_bounds__(GS_NT, 2) void gemm_swiglu_kernel(const GemmSwigluA
   if (!late) __builtin_amdgcn_s_barrier();     // the early group waits for the late group's last COMPUTE segment: equal barrier counts
 }
 
-static thread_local int g_gs_hip_error = 0;
-
 template <typename E, int MODE = 0>
 static int launch_gemm_swiglu(const GemmSwigluArgs& a, hipStream_t s) {
   auto kern = gemm_swiglu_kernel<E, MODE>;
   const size_t lds = (size_t)GS_SLOTS * GS_STAGE;
   // per call: the attribute belongs to the (kernel, device) pair, and a process may drive several devices
-  if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXVL_ERR_LAUNCH;
+  if (hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) return MXVL_ERR_LAUNCH;
   // one persistent workgroup per CU (256 CUs; LDS and the 2-waves-per-SIMD register budget admit exactly one), fewer for small grids
   const int tiles = 8 * a.ntm_x * a.ntn;
   hipLaunchKernelGGL(kern, dim3(tiles < 256 ? tiles : 256), dim3(GS_NT), lds, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_gs_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 }  // namespace mxvl

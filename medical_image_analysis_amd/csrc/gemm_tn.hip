@@ -335,7 +335,7 @@ extern "C" int mxvl_gemm_tn(const mxvl_gemm_tn_desc* d, void* hip_stream) {
   if (d->a_rs < d->M || d->b_rs < d->N || d->c_rs < d->N) return MXVL_ERR_STRIDE;
   hipStream_t s = (hipStream_t)hip_stream;
   if (!d->accumulate) {
-    if (hipMemset2DAsync(d->c, (size_t)d->c_rs * 4, 0, (size_t)d->N * 4, (size_t)d->M, s) != hipSuccess) return MXVL_ERR_LAUNCH;
+    if (hip_status(hipMemset2DAsync(d->c, (size_t)d->c_rs * 4, 0, (size_t)d->N * 4, (size_t)d->M, s)) != MXVL_OK) return MXVL_ERR_LAUNCH;
   }
   GemmTnArgs a;
   a.M = d->M; a.N = d->N; a.K = d->K;
@@ -360,10 +360,10 @@ extern "C" int mxvl_gemm_tn(const mxvl_gemm_tn_desc* d, void* hip_stream) {
   const size_t lds = (size_t)TN_NST * TN_STAGE;
   const void* kern = d->io_dtype == MXVL_BF16 ? (const void*)gemm_tn_kernel<bf16_t> : (const void*)gemm_tn_kernel<f16_t>;
   // per call: the attribute belongs to the (kernel, device) pair, and a process may drive several devices
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXVL_ERR_LAUNCH;
+  if (hip_status(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) return MXVL_ERR_LAUNCH;
   if (d->io_dtype == MXVL_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, dim3(256), dim3(TN_NT), lds, s, a);
   else hipLaunchKernelGGL(gemm_tn_kernel<f16_t>, dim3(256), dim3(TN_NT), lds, s, a);
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 /* see include/mxvl.h: mxvl_colsum */
@@ -387,5 +387,5 @@ extern "C" int mxvl_colsum(const void* x, void* partial, int rows, int cols, int
   hipStream_t s = (hipStream_t)hip_stream;
   if (io_dtype == MXVL_BF16) hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, (float*)partial, rows, cols, row_stride, n_partials);
   else hipLaunchKernelGGL(colsum_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)x, (float*)partial, rows, cols, row_stride, n_partials);
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }

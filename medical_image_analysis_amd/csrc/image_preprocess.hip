@@ -189,7 +189,7 @@ int mxvl_image_preprocess(const mxvl_image_desc* d, void* hip_stream) {
     case MXVL_BF16: hipLaunchKernelGGL(resample_v_norm_kernel<bf16_t>, grid, dim3(kImgThreads), 0, s, a); break;
     default: hipLaunchKernelGGL(resample_v_norm_kernel<f16_t>, grid, dim3(kImgThreads), 0, s, a); break;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -277,7 +277,7 @@ static int rope_launch_cs(const RopeArgs& a, int cs_dtype, hipStream_t s) {
     default: MXVL_ROPE_GO(f16_t); break;
   }
 #undef MXVL_ROPE_GO
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <typename x_t, typename w_t>
@@ -294,7 +294,7 @@ static int rms_launch_y(const RmsArgs& a, bool bwd, hipStream_t s) {
     default: MXVL_RMS_GO(f16_t); break;
   }
 #undef MXVL_RMS_GO
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 template <typename x_t>
 static int rms_launch_w(const RmsArgs& a, bool bwd, hipStream_t s) {
@@ -371,5 +371,5 @@ extern "C" int mxvl_silu_mul(const void* a, const void* b, const void* dy, void*
     case MXVL_BF16: hipLaunchKernelGGL(silu_mul_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)dy, (bf16_t*)y, (bf16_t*)db, n8); break;
     default: hipLaunchKernelGGL(silu_mul_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)a, (const f16_t*)b, (const f16_t*)dy, (f16_t*)y, (f16_t*)db, n8); break;
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }

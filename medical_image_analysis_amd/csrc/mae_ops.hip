@@ -135,11 +135,6 @@ __global__ __launch_bounds__(256) void patch_loss_kernel(const PatchLossArgs p) 
   }
 }
 
-static int mae_check() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
-}
-
 
 // patch_cols_kernel: the im2col of a convolution whose kernel equals its stride (patch embeddings: SmallPatchEmbed conv1 16x16 / s16 on
 // a 1280^2 X-ray, HD_Xray_Pretrain_MAE/pretrain/patch_embed.py:21-43; ViT PatchEmbed, finetune/DP/models/vit.py:186-208) --
@@ -208,7 +203,7 @@ extern "C" int mxvl_row_gather(const void* src, const int32_t* idx, const float*
   else if (out_dtype == MXVL_BF16) MXVL_RG(float, bf16_t);
   else MXVL_RG(float, f16_t);
 #undef MXVL_RG
-  return mae_check();
+  return launch_status();
 }
 
 extern "C" int mxvl_patch_loss(const void* img, const void* pred, const void* dloss, void* loss, void* dpred, int N, int C, int HW,
@@ -232,7 +227,7 @@ extern "C" int mxvl_patch_loss(const void* img, const void* pred, const void* dl
     default: MXVL_PL(f16_t); break;
   }
 #undef MXVL_PL
-  return mae_check();
+  return launch_status();
 }
 
 // ---- window rows of a CHANNELS-LAST feature map, the activation in front of it fused (ABI v11) ---------------------------------------
@@ -301,7 +296,7 @@ extern "C" int mxvl_window_cols(const void* x, const void* dcols, void* out, int
     case MXVL_BF16: hipLaunchKernelGGL(window_cols_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(window_cols_kernel<f16_t>, dim3(grid), dim3(256), 0, s, a); break;
   }
-  return mae_check();
+  return launch_status();
 }
 
 extern "C" int mxvl_patch_cols(const void* img, void* cols, int N, int C, int H, int W, int patch, int in_dtype, int out_dtype,
@@ -326,5 +321,5 @@ extern "C" int mxvl_patch_cols(const void* img, void* cols, int N, int C, int H,
   else if (in_dtype == MXVL_BF16) MXVL_PC(bf16_t, bf16_t);
   else MXVL_PC(f16_t, f16_t);
 #undef MXVL_PC
-  return mae_check();
+  return launch_status();
 }

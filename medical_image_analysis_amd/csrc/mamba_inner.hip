@@ -241,7 +241,7 @@ int mxvl_mamba_inner_fwd(const mxvl_mamba_inner_desc* d, void* hip_stream) {
       if (rc != MXVL_OK) return rc;
     }
   }
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 int mxvl_mamba_inner_bwd(const mxvl_mamba_inner_bwd_desc* b, void* hip_stream) {
@@ -265,7 +265,7 @@ int mxvl_mamba_inner_bwd(const mxvl_mamba_inner_bwd_desc* b, void* hip_stream) {
   char* ws = (char*)d->workspace;
   char* bs = (char*)b->workspace;
   float* dBC = (float*)(bs + v.dBC);
-  if (hipMemsetAsync(dBC, 0, (size_t)d->batch * 2 * N * L * 4, stream) != hipSuccess) return MXVL_ERR_LAUNCH;
+  if (hip_status(hipMemsetAsync(dBC, 0, (size_t)d->batch * 2 * N * L * 4, stream)) != MXVL_OK) return MXVL_ERR_LAUNCH;
 
   std::lock_guard<std::mutex> lock(rb->mu);
   if (rb->set_stream(rb->handle, stream) != 0) return MXVL_ERR_LAUNCH;
@@ -324,7 +324,7 @@ int mxvl_mamba_inner_bwd(const mxvl_mamba_inner_bwd_desc* b, void* hip_stream) {
   cb.dy = bs + v.du; cb.dx = b->dxz; cb.dweight = b->dconv_weight; cb.dbias = b->dconv_bias;
   rc = mxvl_conv1d_bwd(&cb, hip_stream);
   if (rc != MXVL_OK) return rc;
-  return hipGetLastError() == hipSuccess ? MXVL_OK : MXVL_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -27,6 +27,17 @@
 
 namespace mxvl {
 
+// ---- C-ABI status (host) ---------------------------------------------------------------------
+// The hipError_t of the last failing HIP call of this thread in any entry: what mxvl_last_hip_error() returns.  One definition
+// for the library (scan_fwd.hip); sticky, a success leaves it alone.  Every launch check and every LDS opt-in goes through here.
+extern thread_local int g_last_hip_error;
+inline int hip_status(hipError_t e) {
+  if (e == hipSuccess) return MXVL_OK;
+  g_last_hip_error = (int)e;
+  return MXVL_ERR_LAUNCH;
+}
+inline int launch_status() { return hip_status(hipGetLastError()); }
+
 constexpr int kWave = 64;
 typedef float v2f __attribute__((ext_vector_type(2)));   // an aligned VGPR pair: operands of v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32
 constexpr float kLog2e = 1.4426950408889634f;

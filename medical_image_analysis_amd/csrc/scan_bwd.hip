@@ -1008,7 +1008,6 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void scan_bwd_kernel(const ScanBwdA
   }
 }
 
-static thread_local int g_bwd_hip_error = 0;
 extern "C" int mxvl_scan_bwd_variant(void);   // scan_fwd.hip: bits 8..15 of mxvl_set_scan_variant
 
 }  // namespace mxvl
@@ -1069,9 +1068,7 @@ static int try_n1_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
     hipLaunchKernelGGL((scan_n1_bwd_kernel<io_t, 4, NW, false>), grid, block, lds, stream, a, gm);
   }
   taken = true;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_bwd_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 // rows of at most 128 steps that scan_n1_bwd.h cannot take (L % 4 != 0 or unaligned rows): a lane per row (scan_n1_short.h).  Dense
@@ -1103,9 +1100,7 @@ static int try_n1_short_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& take
     else hipLaunchKernelGGL((scan_n1_short_bwd_kernel<io_t, 1, false>), grid, block, lds, stream, a);
   }
   taken = true;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_bwd_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 template <typename io_t, int NWAVES, bool VEC, int NS, bool FOLD = false, bool DMAR = false>
@@ -1117,16 +1112,12 @@ static int launch_bwd1(const ScanBwdArgs& a, hipStream_t stream) {
                      (DMAR ? (size_t)NT * sizeof(float) : 0);                                                           // + its checkpoint entries
   if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
   auto kern = scan_bwd_kernel<io_t, NWAVES, VEC, NS, FOLD, DMAR>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_bwd_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  }
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
+    return MXVL_ERR_LAUNCH;
   const int dpg = a.dim / a.G;
   dim3 grid(a.G * ((dpg + DT - 1) / DT), FOLD ? (a.batch + a.fold_bpp - 1) / a.fold_bpp : a.batch), block(NT);
   hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_bwd_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 // dstate 16 (every Mamba block of the reference) takes the instantiation with the unrolled state loop
 template <typename io_t, int NWAVES, bool VEC>

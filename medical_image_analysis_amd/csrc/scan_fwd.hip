@@ -364,7 +364,7 @@ __global__ __launch_bounds__(NWAVES * 64, MINW) void scan_fwd_kernel(const ScanA
 namespace mxvl {
 
 // ---------------------------------------------------------------------------------------------
-static thread_local int g_last_hip_error = 0;
+thread_local int g_last_hip_error = 0;   // mxvl_common.h: the library's one last-error slot
 static thread_local const char* g_last_kernel = "none";
 static thread_local int g_variant = 0;   // per calling thread: a test / bench hook, not process-global state
 
@@ -374,17 +374,13 @@ static int launch_fwd(const ScanArgs& a, hipStream_t stream, const char* name) {
   const size_t lds = sizeof(float) * ((size_t)2 * a.N * CH + (size_t)3 * DT * CH + (size_t)2 * DT * a.N);
   if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
   auto kern = scan_fwd_kernel<io_t, T, LPR, NWAVES, NU, MINW>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  }
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
+    return MXVL_ERR_LAUNCH;
   const int dpg = a.dim / a.G;
   dim3 grid(a.G * ((dpg + DT - 1) / DT), a.batch), block(NWAVES * 64);
   hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  hipError_t e = hipGetLastError();
   g_last_kernel = name;
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 template <typename io_t, int NWAVES, bool VEC, int MINW, int T, int NS, bool FOLD = false, bool PK = false>
@@ -397,10 +393,8 @@ static int launch_stream1(const ScanArgs& a, hipStream_t stream, const char* nam
   const int dpg = a.dim / a.G;
   dim3 grid(a.G * ((dpg + DT - 1) / DT), FOLD ? (a.batch + a.fold_bpp - 1) / a.fold_bpp : a.batch), block(NWAVES * 64);
   hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  hipError_t e = hipGetLastError();
   g_last_kernel = name;
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 // dstate 16 (every Mamba block of the reference) takes the instantiation with the compile-time state count
 template <typename io_t, int NWAVES, bool VEC, int MINW, int T = 8>
@@ -464,9 +458,7 @@ static int try_n1_fwd(const ScanArgs& a, hipStream_t stream, bool& taken) {
     g_last_kernel = "scan_n1_fwd<T4>";
   }
   taken = true;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 // dstate 1, rows of at most 128 steps that scan_n1.h cannot take (L % 4 != 0 -- VMamba's 7 x 7 stage -- or unaligned rows): a lane per
@@ -498,9 +490,7 @@ static int try_n1_short_fwd(const ScanArgs& a, hipStream_t stream, bool& taken) 
   }
   g_last_kernel = "scan_n1_short_fwd";
   taken = true;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return MXVL_ERR_LAUNCH; }
-  return MXVL_OK;
+  return launch_status();
 }
 
 template <typename io_t>

@@ -29,6 +29,20 @@ from . import _abi, autograd_util
 KERNEL_TIMERS = None
 
 
+def _timed(kind, launch, work):
+    """rc = launch(); with KERNEL_TIMERS set, bracketed by HIP events on the current stream and recorded as
+    (kind, start, end, work()) -- `work` is only evaluated then."""
+    timers = KERNEL_TIMERS
+    if timers is None:
+        return launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = launch()
+    e1.record()
+    timers.append((kind, e0, e1, work()))
+    return rc
+
+
 def scan_algorithmic_bytes(batch, dim, L, N, G, elt, has_z, backward=False, n_ckpt=0):
     """SURVEY.md 8-d.  fwd: elt*((3|4)*B*D*L + 2*B*G*N*L) + 4*(D*N + 2*D) (+ checkpoints 4*B*D*n_ckpt*N);
     bwd: elt*(reads u,delta,z?,dout + writes du,ddelta,dz?) + elt*2*B*G*N*L + 2*4*B*G*N*L (dB,dC fp32) + checkpoints."""
@@ -162,17 +176,10 @@ def scan_fwd_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softp
                 ckpt = torch.empty((batch, dim, n_chunks, N), dtype=torch.float32, device=u.device)
     desc = _abi.ScanDesc()
     _fill_fwd(desc, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, last, ckpt, out_f32, fold)
-    timers = KERNEL_TIMERS
     with torch.cuda.device(u.device):
-        if timers is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = lib.mxvl_scan_fwd(ctypes.byref(desc), _abi.stream_ptr(u.device))
-        if timers is not None:
-            e1.record()
-            timers.append(("scan_fwd", e0, e1, scan_algorithmic_bytes(
-                batch, dim, L, N, B.shape[1], u.element_size(), z is not None, False,
-                _ckpt_chunks(ckpt, batch, dim))))
+        rc = _timed("scan_fwd", lambda: lib.mxvl_scan_fwd(ctypes.byref(desc), _abi.stream_ptr(u.device)),
+                    lambda: scan_algorithmic_bytes(batch, dim, L, N, B.shape[1], u.element_size(), z is not None, False,
+                                                   _ckpt_chunks(ckpt, batch, dim)))
     _abi.check(rc, "mxvl_scan_fwd")
     return out, last, ckpt
 
@@ -224,17 +231,10 @@ def scan_bwd_raw(u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout
     desc.dA, desc.dB, desc.dC = dA.data_ptr(), dB.data_ptr(), dC.data_ptr()
     desc.dD, desc.ddelta_bias = _abi.ptr(dD), _abi.ptr(dbias)
     desc.workspace, desc.workspace_bytes = None, 0     # ABI v3 field, ignored since round 3 (dB / dC leave as fp32 atomics)
-    timers = KERNEL_TIMERS
     with torch.cuda.device(u.device):
-        if timers is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = lib.mxvl_scan_bwd(ctypes.byref(desc), _abi.stream_ptr(u.device))
-        if timers is not None:
-            e1.record()
-            timers.append(("scan_bwd", e0, e1, scan_algorithmic_bytes(
-                batch, dim, L, A.shape[1], B.shape[1], u.element_size(), z is not None, True,
-                _ckpt_chunks(ckpt, batch, dim))))
+        rc = _timed("scan_bwd", lambda: lib.mxvl_scan_bwd(ctypes.byref(desc), _abi.stream_ptr(u.device)),
+                    lambda: scan_algorithmic_bytes(batch, dim, L, A.shape[1], B.shape[1], u.element_size(), z is not None, True,
+                                                   _ckpt_chunks(ckpt, batch, dim)))
     _abi.check(rc, "mxvl_scan_bwd")
     if ratio > 1:
         ddelta = ddelta.view(batch, dim // ratio, ratio, L).sum(2, dtype=torch.float32).to(delta.dtype)
@@ -365,15 +365,9 @@ def gemm_tn(a_km, b_kn, out=None, slices_per_xcd=0):
     d.accumulate, d.slices_per_xcd = (1 if out is not None else 0), slices_per_xcd
     d.a_rs, d.b_rs, d.c_rs = a_km.stride(0), b_kn.stride(0), c.stride(0)
     d.a, d.b, d.c = a_km.data_ptr(), b_kn.data_ptr(), c.data_ptr()
-    timers = KERNEL_TIMERS
     with torch.cuda.device(a_km.device):
-        if timers is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = _abi.load().mxvl_gemm_tn(ctypes.byref(d), _abi.stream_ptr(a_km.device))
-        if timers is not None:
-            e1.record()
-            timers.append(("gemm_tn", e0, e1, 2 * K * M * N))          # MFMA-bound: the work figure is FLOPs, not bytes
+        rc = _timed("gemm_tn", lambda: _abi.load().mxvl_gemm_tn(ctypes.byref(d), _abi.stream_ptr(a_km.device)),
+                    lambda: 2 * K * M * N)          # MFMA-bound: the work figure is FLOPs, not bytes
     _abi.check(rc, "mxvl_gemm_tn")
     return c
 

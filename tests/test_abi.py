@@ -47,6 +47,78 @@ def test_ctypes_struct_mirrors_header(cstruct, pystruct):
     assert names == [f[0] for f in pystruct._fields_]
 
 
+def _prototypes():
+    """{name: (return type, [parameter types])} of every function include/mxvl.h declares, each type reduced to its class:
+    "ptr" (any pointer, `T name[n]` included), "char*" (const char*), or the scalar type with int32_t read as int."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", _header(), flags=re.S)
+    text = re.sub(r"typedef\s+(struct|enum)[^{;]*\{.*?\}[^;]*;", "", text, flags=re.S)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)
+
+    def cls(decl):
+        decl = " ".join(decl.replace("const", " ").split())
+        if re.fullmatch(r"char ?\*", decl):
+            return "char*"
+        if "*" in decl or "[" in decl:
+            return "ptr"
+        return {"int32_t": "int"}.get(decl, decl)
+
+    protos = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s*]*?)\b(mxvl_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [p.strip() for p in m.group(3).split(",")]
+        params = [] if params == ["void"] else [re.sub(r"\b\w+\s*(\[\w*\])?$", lambda a: a.group(1) or "", p) for p in params]
+        protos[m.group(2)] = (cls(m.group(1)), [cls(p) for p in params])
+    return protos
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t is ctypes.c_char_p:
+        return "char*"
+    if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_uint32: "uint32_t", ctypes.c_float: "float"}[t]
+
+
+def test_binding_signatures_match_header_prototypes():
+    """Every export has ONE declared ctypes signature (_abi.SIGNATURES, applied by load()) with the header's arity and, per parameter
+    and return value, the same type class: an int64_t bound as c_int or a pointer bound as an int does not pass."""
+    protos = _prototypes()
+    assert len(protos) == len(_abi.SIGNATURES) and set(protos) == set(_abi.SIGNATURES), set(protos) ^ set(_abi.SIGNATURES)
+    for name, (restype, argtypes) in _abi.SIGNATURES.items():
+        got = (_ctypes_class(restype), [_ctypes_class(t) for t in argtypes])
+        assert got == protos[name], f"{name}: binding {got} != header {protos[name]}"
+    lib = _abi.load()
+    for name, (restype, argtypes) in _abi.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def _csrc():
+    d = os.path.join(ROOT, "medical_image_analysis_amd", "csrc")
+    return {n: open(os.path.join(d, n)).read() for n in sorted(os.listdir(d)) if n.endswith((".hip", ".h"))}
+
+
+def test_hip_errors_reach_one_status_path():
+    """Every launch check of libmxvl goes through mxvl_common.h (launch_status / hip_status), and the library keeps ONE thread-local
+    last hipError -- what mxvl_last_hip_error() returns -- instead of per-file copies nobody reads."""
+    src = _csrc()
+    assert [n for n, t in src.items() if "hipGetLastError" in t] == ["mxvl_common.h"]
+    slots = [(n, m.group(1)) for n, t in src.items()
+             for m in re.finditer(r"\bthread_local\s+(?:const\s+)?[\w:]+\s*\*?\s*(\w+)", t) if re.search(r"err", m.group(1), re.I)]
+    assert sorted(slots) == [("mxvl_common.h", "g_last_hip_error"), ("scan_fwd.hip", "g_last_hip_error")], slots
+    assert re.search(r"\bextern\s+thread_local\s+int\s+g_last_hip_error\s*;", src["mxvl_common.h"])
+    assert re.search(r"int\s+mxvl_last_hip_error\s*\(\s*void\s*\)\s*\{\s*return\s+g_last_hip_error\s*;", src["scan_fwd.hip"])
+
+
+def test_check_reports_the_hip_error_of_launch_failures_only():
+    with pytest.raises(RuntimeError, match=r"^f failed: MXVL_ERR_SHAPE$"):
+        _abi.check(-3, "f")
+    with pytest.raises(RuntimeError, match=r"^f failed: MXVL_ERR_LAUNCH \(hipError -?\d+\)$"):
+        _abi.check(_abi.MXVL_ERR_LAUNCH, "f")
+    _abi.check(0, "f")
+
+
 def test_scan_descriptor_validation_without_gpu():
     lib = _abi.load()
     d = _abi.ScanDesc()
