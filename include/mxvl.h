@@ -73,7 +73,7 @@
 extern "C" {
 #endif
 
-#define MXVL_ABI_VERSION 12
+#define MXVL_ABI_VERSION 13
 
 typedef enum mxvl_status {
   MXVL_OK = 0,
@@ -429,6 +429,46 @@ typedef struct mxvl_beam_desc {
 } mxvl_beam_desc;
 int mxvl_beam_step(const mxvl_beam_desc *desc, void *hip_stream);
 int64_t mxvl_beam_workspace_bytes(int batch, int beams, int keep);
+
+/* ABI v13: one SAMPLING update of report generation (csrc/sample_step.hip) -- what HF `generate(num_beams=1, do_sample=True)` does
+ * between two decoder steps (transformers generation/utils.py `_sample`; the reference passes do_sample=self.hparams.do_sample and
+ * temperature=self.hparams.temperature at EMRRG/models/MambaXrayVL_DownStream.py:440-449, 537-546 and
+ * R2GenKG/models/R2GenKG.py:392-401, 480-489).  On the fp32 logits of step *cur, in HF's processor order:
+ *   repetition penalty over seq[:, :cur] (g < 0 ? g * pen : g / pen) -> EOS ids to -inf while *cur < min_new -> / temperature (an
+ *   IEEE fp32 division) -> top-k (scores below the k-th largest removed, ties with it kept; 0 = off) -> top-p (below) -> the draw:
+ *   u = (sample_hash(seed, row, *cur) >> 8) * 2^-24 (report_decoder.sample_uniform restates it), token = the first index in
+ *   VOCABULARY order whose inclusive cumulative kept mass exceeds u * (kept mass).
+ * Rows that are no longer alive emit `fill`; seq[row][*cur] = tok; alive &= tok not in eos; *cur += 1;
+ * *unfinished = any(alive) && *cur < max_new, also stored at unfinished_log[cur before].  A call that finds *unfinished == 0 returns
+ * at once.  All thresholds come from exact radix selections over the order-preserving 32-bit image of the scores (no sort); masses
+ * are accumulated as 64-bit fixed-point integers (exp(score - max) in units of 2^-40, fewer bits for vocabularies beyond 2^22), so
+ * no result depends on the order in which anything is added: the same inputs give the same token on every run.
+ * Recorded deviation from HF (TopPLogitsWarper): token i is kept iff the softmax mass of the tokens with a STRICTLY GREATER score is
+ * < top_p.  That is HF's rule (ascending sort, cumulative mass <= 1 - top_p removed, at least one token kept) wherever the scores at
+ * the cut are distinct; scores TIED at the cut are kept together here, where HF keeps those of them an unstable torch.sort happens
+ * to place last.  The kept set never depends on the index order of equal scores.
+ * Shapes: 1 <= rows <= 80, n_eos <= 4, rows * vocab < 2^31, temperature > 0 and finite, 0 < top_p <= 1, top_k >= 0 (MXVL_ERR_SHAPE
+ * otherwise, decided before any launch).  Dtypes: logits fp32 (rows, vocab) dense; seq (rows, max_new), tok (rows), cur, eos, seed
+ * int64; alive (rows), unfinished 1-byte booleans. */
+typedef struct mxvl_sample_desc {
+  int32_t rows, vocab, max_new, min_new, n_eos, top_k;
+  float repetition_penalty, temperature, top_p;
+  int32_t reserved0;
+  int64_t fill;                    /* token of the rows that have stopped (pad, else the first EOS) */
+  const void *logits;
+  void *seq, *alive, *tok, *cur;
+  const void *eos;                 /* (n_eos) */
+  const void *seed;                /* (1) int64 in DEVICE memory: read by the kernel, so a captured launch sees every new seed */
+  void *unfinished;                /* scalar */
+  void *unfinished_log;            /* optional, (max_new) host-visible bytes: as mxvl_beam_desc.unfinished_log */
+  void *scratch;                   /* (1) uint32 arrival word of the row workgroups, zero before the first call (left zero) */
+  void *workspace;                 /* mxvl_sample_workspace_bytes(rows, vocab) bytes of device memory, contents irrelevant */
+  int64_t workspace_bytes;
+  void *out_thresh;                /* optional, (rows) fp32: the smallest kept score of the step */
+  void *out_kept;                  /* optional, (rows) int32: how many tokens the filters kept */
+} mxvl_sample_desc;
+int mxvl_sample_step(const mxvl_sample_desc *desc, void *hip_stream);
+int64_t mxvl_sample_workspace_bytes(int rows, int vocab);
 
 /* Residual add + LayerNorm of an ARM / VisionMamba block (CXPMRG_Bench_MambaXray_VL/arm/Finetuning/models_mamba.py:
  * 110-116 `x + mixer(norm1(x))`, `x + mlp(norm2(x))`; the reference's fused_add_norm path pairs them the same way):

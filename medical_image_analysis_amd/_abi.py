@@ -15,7 +15,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmxvl.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 MXVL_F32, MXVL_BF16, MXVL_F16 = 0, 1, 2
 SCAN_DELTA_SOFTPLUS = 1
@@ -252,6 +252,17 @@ class BeamDesc(ctypes.Structure):
     ]
 
 
+class SampleDesc(ctypes.Structure):
+    _fields_ = [
+        ("rows", c_int32), ("vocab", c_int32), ("max_new", c_int32), ("min_new", c_int32), ("n_eos", c_int32), ("top_k", c_int32),
+        ("repetition_penalty", ctypes.c_float), ("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("reserved0", c_int32),
+        ("fill", c_int64),
+        ("logits", c_void_p), ("seq", c_void_p), ("alive", c_void_p), ("tok", c_void_p), ("cur", c_void_p), ("eos", c_void_p),
+        ("seed", c_void_p), ("unfinished", c_void_p), ("unfinished_log", c_void_p), ("scratch", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64), ("out_thresh", c_void_p), ("out_kept", c_void_p),
+    ]
+
+
 class ImageDesc(ctypes.Structure):
     _fields_ = [
         ("in_h", c_int32), ("in_w", c_int32), ("out_h", c_int32), ("out_w", c_int32),
@@ -299,6 +310,8 @@ SIGNATURES = {
     "mxvl_decode_rmsnorm": _DESC,
     "mxvl_beam_step": _DESC,
     "mxvl_beam_workspace_bytes": (_I64, [_I] * 3),
+    "mxvl_sample_step": _DESC,
+    "mxvl_sample_workspace_bytes": (_I64, [_I] * 2),
     # VMamba / VisionMamba
     "mxvl_cross_scan": (_I, [_P, _P] + [_I] * 5 + [_P]),
     "mxvl_cross_merge": (_I, [_P, _P] + [_I] * 5 + [_P]),

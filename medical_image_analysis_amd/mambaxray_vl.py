@@ -224,6 +224,7 @@ class MambaXrayVLDownStream(nn.Module):
             do_sample=_get(a, "do_sample", False), min_new_tokens=_get(a, "min_new_tokens", 80),
             max_new_tokens=_get(a, "max_new_tokens", 120), repetition_penalty=_get(a, "repetition_penalty", 2.0),
             length_penalty=_get(a, "length_penalty", 2.0), temperature=_get(a, "temperature", 0),
+            top_k=_get(a, "top_k", None), top_p=_get(a, "top_p", 1.0), seed=_get(a, "seed", None),
             eos_token_id=_get(self.llama_tokenizer, "eos_token_id", None), pad_token_id=self.llama_tokenizer.pad_token_id)
 
     def _eval_step(self, samples, sink):

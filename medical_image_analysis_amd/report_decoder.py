@@ -335,6 +335,155 @@ class _BeamState:
         self.cur.add_(1)
 
 
+def sample_uniform(seed, rows, step, device="cpu"):
+    """The uniform of the sampled decode for (seed, row, step): a 24-bit value in [0, 1), u = (hash >> 8) * 2^-24, a pure function
+    of its arguments -- the host restatement of csrc/sample_step.hip sample_hash (the mixer of csrc/attn.hip attn_drop_hash, see
+    flash_attention.dropout_keep_mask, over (low seed word, row, step, high seed word)) in int64 arithmetic.  `seed` and `step` are
+    ints or int64 tensors (the state's device seed and step counter); returns (rows,) float64."""
+    M = 0xFFFFFFFF
+    seed = torch.as_tensor(seed, dtype=torch.int64, device=device).reshape(-1)[:1]
+    step = torch.as_tensor(step, dtype=torch.int64, device=device).reshape(-1)[:1]
+    row = torch.arange(rows, dtype=torch.int64, device=device)
+    lo, hi = seed & M, (seed >> 32) & M
+    x = lo ^ ((row * 0x9E3779B1) & M)
+    x = ((x ^ ((step * 0x85EBCA77) & M)) * 0xC2B2AE3D) & M
+    x = x ^ ((hi * 0x27D4EB2F) & M)
+    x = x ^ (x >> 16)
+    x = (x * 0x85EBCA6B) & M
+    x = x ^ (x >> 13)
+    x = (x * 0xC2B2AE35) & M
+    x = x ^ (x >> 16)
+    return (x >> 8).double() * 2.0 ** -24
+
+
+class _SampleState:
+    """HF `_sample` with do_sample=True (num_beams = 1) as ONE static-shape update per generated token, shaped like `_BeamState` so
+    the steppers drive either: RepetitionPenalty -> MinNewTokens -> Temperature -> TopK -> TopP on the fp32 logits (HF's order,
+    generation/utils.py `_get_logits_processor`), then an inverse-CDF draw in vocabulary order fed by `sample_uniform(seed, row, cur)`.
+    The seed lives in DEVICE memory and the step counter is the device scalar `cur`: a captured step replays with a fresh number per
+    token and per call.  Top-p keeps token i iff the softmax mass of the strictly greater scores is < top_p: HF's rule with the ties
+    at the cut kept together (HF's own outcome on ties follows an unstable sort; include/mxvl.h records the deviation)."""
+
+    def __init__(self, B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev):
+        self.B, self.V, self.max_new = B, vocab, max_new
+        self.use_hip = True      # tests flip this to compare the HIP kernel with the torch restatement
+        self.allow_torch = False  # generate(use_graph="torch" / False) sets it: the torch restatement as an EXPLICIT request only
+        self.fill, self.min_new, self.rep_pen = fill, min_new, float(rep_pen)
+        self.temperature, self.top_p = float(temperature), float(top_p)
+        self.top_k = min(int(top_k), vocab) if top_k else 0           # 0 = off (HF: None or 0)
+        self.eos_t = torch.tensor(eos, device=dev, dtype=torch.long)
+        # divisors as fp32 DEVICE scalars: torch divides by a host scalar on a HIP device as a multiplication by its reciprocal, which
+        # is not the IEEE division HF's processors perform on the CPU (and csrc/sample_step.hip on the device)
+        self.temp_t = torch.tensor(self.temperature, dtype=torch.float32, device=dev)
+        self.pen_t = torch.tensor(self.rep_pen, dtype=torch.float32, device=dev)
+        self.ar = torch.arange(max_new, device=dev)
+        self.seq = torch.empty(B, max_new, dtype=torch.long, device=dev)
+        self.alive = torch.empty(B, dtype=torch.bool, device=dev)
+        self.tok = torch.zeros(B, dtype=torch.long, device=dev)
+        self.beam_src = torch.arange(B, device=dev)                    # identity: no beams to re-order
+        self.cur = torch.zeros((), dtype=torch.long, device=dev)
+        self.unfinished = torch.ones((), dtype=torch.bool, device=dev)
+        self.seed = torch.zeros(1, dtype=torch.long, device=dev)        # device memory, never a kernel scalar
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)     # arrival word of the row workgroups
+        self.out_thresh = torch.zeros(B, dtype=torch.float32, device=dev)   # smallest kept score / kept tokens of the last step
+        self.out_kept = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.workspace = None
+        self.unf_log = torch.zeros(max_new, dtype=torch.uint8).pin_memory() if torch.device(dev).type == "cuda" else None
+        self.reset()
+
+    def reset(self):
+        self.seq.fill_(self.fill)
+        self.alive.fill_(True)
+        self.cur.zero_()
+        self.unfinished.fill_(True)
+
+    def _hip_supported(self, logits):
+        """What csrc/sample_step.hip serves: <= 80 rows (the kernel stepper's bound), <= 4 EOS ids, rows * vocab < 2^31."""
+        return (logits.is_cuda and self.B <= 80 and self.eos_t.numel() <= 4 and self.B * self.V < 2 ** 31
+                and logits.dtype == torch.float32 and logits.is_contiguous())
+
+    def _advance_hip(self, logits):
+        """csrc/sample_step.hip: the whole update below as one kernel (capturable in the decode step's hipGraph)."""
+        import ctypes
+        from . import _abi
+        lib = _abi.load()
+        if self.workspace is None:
+            self.workspace = torch.empty(int(lib.mxvl_sample_workspace_bytes(self.B, self.V)), dtype=torch.uint8, device=logits.device)
+        d = _abi.SampleDesc()
+        d.rows, d.vocab, d.max_new, d.min_new, d.n_eos, d.top_k = self.B, self.V, self.max_new, self.min_new, self.eos_t.numel(), self.top_k
+        d.repetition_penalty, d.temperature, d.top_p, d.fill = self.rep_pen, self.temperature, self.top_p, self.fill
+        d.logits, d.seq, d.alive, d.tok, d.cur = logits.data_ptr(), self.seq.data_ptr(), self.alive.data_ptr(), self.tok.data_ptr(), self.cur.data_ptr()
+        d.eos, d.seed = _abi.ptr(self.eos_t if self.eos_t.numel() else None), self.seed.data_ptr()
+        d.unfinished, d.unfinished_log, d.scratch = self.unfinished.data_ptr(), _abi.ptr(self.unf_log), self.ticket.data_ptr()
+        d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
+        d.out_thresh, d.out_kept = self.out_thresh.data_ptr(), self.out_kept.data_ptr()
+        with torch.cuda.device(logits.device):
+            _abi.check(lib.mxvl_sample_step(ctypes.byref(d), _abi.stream_ptr(logits.device)), "mxvl_sample_step")
+
+    def advance(self, logits):
+        """Consume the (B, V) logits of step `cur`; leaves the drawn tokens in .tok / .seq[:, cur] and whether decoding goes on in
+        .unfinished."""
+        if self.use_hip and logits.is_cuda:
+            lg = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.float().contiguous()
+            if self._hip_supported(lg):
+                return self._advance_hip(lg)
+            if not self.allow_torch:
+                raise RuntimeError(
+                    f"sampling update on {logits.device}: csrc/sample_step.hip serves <= 80 rows, <= 4 EOS ids and rows * vocab < 2^31 "
+                    f"(got rows={self.B}, eos ids={self.eos_t.numel()}, vocab={self.V}); pass use_graph=\"torch\" (or False) to "
+                    f"generate() for the torch restatement")
+        return self.advance_torch(logits)
+
+    def scores_torch(self, logits):
+        """Steps 1-5: the processed fp32 scores, the kept mask, the smallest kept score and the kept count of every row."""
+        cur = self.cur
+        sc = logits.float().clone()
+        if self.rep_pen != 1.0:                                                 # RepetitionPenaltyLogitsProcessor, generated tokens only
+            idx = torch.where(self.ar[None, :] < cur, self.seq, self.seq[:, :1])  # unwritten slots alias token 0 of the row
+            g = torch.gather(sc, 1, idx)
+            pen = torch.where(g < 0, g * self.pen_t, g / self.pen_t)
+            sc = sc.scatter(1, idx, torch.where(cur > 0, pen, g))
+        if self.eos_t.numel() > 0 and self.min_new > 0:                         # MinNewTokensLengthLogitsProcessor
+            col = sc.index_select(1, self.eos_t)
+            sc.index_copy_(1, self.eos_t, torch.where(cur < self.min_new, torch.full_like(col, -float("inf")), col))
+        if self.temperature != 1.0:                                             # TemperatureLogitsWarper: a true fp32 division
+            sc = sc / self.temp_t
+        keep = torch.ones_like(sc, dtype=torch.bool)
+        if self.top_k > 0:                                                      # TopKLogitsWarper: ties with the k-th value stay
+            kth = torch.topk(sc, self.top_k)[0][:, -1:]
+            keep = sc >= kth
+        if self.top_p < 1.0:                                                    # TopPLogitsWarper, ties at the cut kept together
+            vals = torch.sort(torch.where(keep, sc, torch.full_like(sc, -float("inf"))), dim=-1, descending=True)[0]
+            p = torch.softmax(vals.double(), dim=-1)
+            above = torch.cumsum(p, dim=-1) - p                                 # mass in front of every sorted position
+            first = torch.ones_like(keep)
+            first[:, 1:] = vals[:, 1:] != vals[:, :-1]
+            s_gt = torch.cummax(torch.where(first, above, torch.full_like(above, -1.0)), dim=-1)[0]   # ... of the strictly greater scores
+            cut = torch.where(s_gt < self.top_p, vals, torch.full_like(vals, float("inf"))).min(dim=-1, keepdim=True)[0]
+            keep = keep & (sc >= cut)
+        thresh = torch.where(keep, sc, torch.full_like(sc, float("inf"))).min(dim=-1)[0]
+        return sc, keep, thresh, keep.sum(-1)
+
+    def advance_torch(self, logits):
+        B, cur = self.B, self.cur
+        sc, keep, thresh, kept = self.scores_torch(logits)
+        p = torch.softmax(torch.where(keep, sc, torch.full_like(sc, -float("inf"))), dim=-1)      # fp32, as HF's `probs`
+        c = p.double().cumsum(-1)
+        u = sample_uniform(self.seed, B, cur, device=logits.device)
+        tok = (c <= (u[:, None] * c[:, -1:])).sum(-1)
+        last = (keep * torch.arange(1, self.V + 1, device=logits.device)).max(-1)[0] - 1           # the last kept index
+        tok = torch.minimum(tok, last)
+        tok = torch.where(self.alive, tok, torch.full_like(tok, self.fill))
+        self.seq.scatter_(1, cur.view(1, 1).expand(B, 1), tok[:, None])
+        if self.eos_t.numel() > 0:
+            self.alive.copy_(self.alive & ~torch.isin(tok, self.eos_t))
+        self.tok.copy_(tok)
+        self.out_thresh.copy_(thresh)
+        self.out_kept.copy_(kept)
+        self.cur.add_(1)
+        self.unfinished.copy_(self.alive.any() & (self.cur < self.max_new))
+
+
 class _KernelStepper(_SearchFusion):
     """One decode step on the hand-written HIP kernels (csrc/decode.hip): per layer a fused RMSNorm+QKV GEMV, the
     RoPE/cache-append/attention kernel, o_proj GEMV (+residual), fused RMSNorm + gate/up GEMV + SwiGLU, down GEMV
@@ -794,6 +943,40 @@ class ReportDecoder(nn.Module):
             emb = self.model.embed_tokens(tok)[:, None, :].to(dtype)
             logits = self.forward(emb, attention_mask=attn, past_key_values=cache)[:, -1]
 
+    def _sample(self, logits, cache, attn, dtype, eos, fill, min_new, max_new, rep_pen, temperature, top_k, top_p, seed, stepper,
+                use_graph):
+        """num_beams = 1, do_sample=True (HF `_sample`): `_SampleState` driven by the token loop of the beam path -- decoder step +
+        sampling update in ONE hipGraph replay per token, no host round trip (`_search_lookahead`)."""
+        B, dev = logits.shape[0], logits.device
+        vocab = logits.shape[-1]
+        if seed is None:
+            # a generator of the decoder's own (seeded once from torch's initial seed): a call must not shift the global CPU stream
+            # that samplers and augmentation draw from
+            gen = self.__dict__.get("_sample_gen")
+            if gen is None:
+                gen = self.__dict__["_sample_gen"] = torch.Generator().manual_seed(torch.initial_seed() & (2 ** 63 - 1))
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=gen, dtype=torch.int64))
+        skey = (B, vocab, max_new, fill, tuple(eos), min_new, rep_pen, temperature, top_k or 0, top_p, str(dev))
+        state = self.__dict__.setdefault("_sample_states", {}).get(skey)
+        if state is None:
+            state = _SampleState(B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev)
+            self._sample_states[skey] = state
+        else:
+            state.reset()
+        state.seed.copy_(torch.tensor([seed & (2 ** 63 - 1)], dtype=torch.long))       # device memory: never baked into a capture
+        state.allow_torch = use_graph == "torch" or use_graph is False
+        state.advance(logits)                                    # step 0: the prefill logits
+        if isinstance(stepper, _KernelStepper) and state.use_hip and state._hip_supported(stepper.logits):
+            self._search_lookahead(stepper, state)
+        while bool(state.unfinished):
+            if stepper is not None:
+                stepper.step_search(state)                       # decoder step + sampling update, one hipGraph replay
+                continue
+            attn = torch.cat([attn, torch.ones(B, 1, dtype=attn.dtype, device=dev)], dim=1)
+            emb = self.model.embed_tokens(state.tok)[:, None, :].to(dtype)
+            state.advance(self.forward(emb, attention_mask=attn, past_key_values=cache)[:, -1])
+        return state.seq[:, :int(state.cur)].clone()
+
     @staticmethod
     def _search_lookahead(stepper, state):
         """Token loop without a host round trip per token: replay k + 1 is enqueued BEFORE the host has seen `unfinished` of replay k
@@ -821,7 +1004,8 @@ class ReportDecoder(nn.Module):
 
     @torch.no_grad()
     def generate(self, inputs_embeds, *args, **kwargs):
-        """Greedy (num_beams=1) / beam search over a prompt given as embeddings.  Returns (B, <= max_new_tokens) ids.
+        """Greedy (num_beams=1) / beam search / sampling (num_beams=1, do_sample=True with temperature, top_k, top_p, seed) over a
+        prompt given as embeddings.  Returns (B, <= max_new_tokens) ids.
         use_graph (default: on for HIP devices): static KV cache + one hipGraph replay per generated token.
         A decoder held in a 16-bit dtype decodes IN that dtype, prompt prefill included: an enclosing autocast context (the
         reference's validation_step runs under Lightning's bf16-mixed one, configs/config.py:67, around an LLM loaded with
@@ -835,9 +1019,22 @@ class ReportDecoder(nn.Module):
 
     def _generate(self, inputs_embeds, attention_mask=None, num_beams=1, do_sample=False, min_new_tokens=0,
                   max_new_tokens=20, repetition_penalty=1.0, length_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                  early_stopping=False, temperature=None, use_graph=None):
+                  early_stopping=False, temperature=None, use_graph=None, top_k=None, top_p=1.0, seed=None):
         if do_sample:
-            raise NotImplementedError("the reference decodes with do_sample=False")
+            # HF validates these before it generates (GenerationConfig.validate, the warpers' constructors): so do we, before
+            # anything is enqueued.  With do_sample=False they stay ignored (the reference's default --temperature 0 keeps working)
+            if num_beams != 1:
+                raise NotImplementedError("beam-sample (num_beams > 1 with do_sample=True) is not built: sample with num_beams=1")
+            temperature = 1.0 if temperature is None else temperature
+            if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not (0.0 < float(temperature) < float("inf")):
+                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive finite float with do_sample=True")
+            top_p = 1.0 if top_p is None else top_p
+            if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0.0 < float(top_p) <= 1.0):
+                raise ValueError(f"`top_p` (={top_p}) has to be a float > 0 and <= 1")
+            if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0):
+                raise ValueError(f"`top_k` (={top_k}) has to be a non-negative integer or None")
+            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+                raise ValueError(f"`seed` (={seed}) has to be an integer or None")
         dev = inputs_embeds.device
         B = inputs_embeds.shape[0]
         nb = num_beams
@@ -889,6 +1086,9 @@ class ReportDecoder(nn.Module):
                 self.__dict__.setdefault("_steppers", {})[key] = stepper
             else:
                 stepper.reset(attention_mask, cache)
+        if do_sample:
+            return self._sample(logits, cache, attention_mask, inputs_embeds.dtype, eos, fill, min_new_tokens, max_new_tokens,
+                                repetition_penalty, float(temperature), top_k, float(top_p), seed, stepper, use_graph)
         if nb == 1:
             return self._greedy(logits, cache, attention_mask, inputs_embeds.dtype, eos_t, fill, min_new_tokens,
                                 max_new_tokens, repetition_penalty, stepper)
