@@ -298,8 +298,8 @@ SIGNATURES = {
     # fused Mamba inner block
     "mxvl_mamba_inner_fwd": _DESC,
     "mxvl_mamba_inner_bwd": _DESC,
-    "mxvl_mamba_inner_workspace_bytes": (_I64, [_P]),
-    "mxvl_mamba_inner_bwd_workspace_bytes": (_I64, [_P]),
+    "mxvl_mamba_inner_workspace_bytes": (_I64, [ctypes.POINTER(MambaInnerDesc)]),       # typed: ctypes passes a descriptor by reference
+    "mxvl_mamba_inner_bwd_workspace_bytes": (_I64, [ctypes.POINTER(MambaInnerDesc)]),
     # report decoder
     "mxvl_decode_gemv": _DESC,
     "mxvl_decode_gemm_plan": (_I, [ctypes.POINTER(GemvDesc), ctypes.POINTER(c_int32)]),
@@ -413,3 +413,14 @@ def check(rc: int, what: str) -> None:
         # the thread's last hipError belongs to this call only when it failed a launch; a validation failure did not touch HIP
         hip = f" (hipError {load().mxvl_last_hip_error()})" if rc == MXVL_ERR_LAUNCH else ""
         raise RuntimeError(f"{what} failed: {STATUS.get(rc, rc)}{hip}")
+
+
+def launch(name: str, first, *rest, device) -> None:
+    """The one way the package enqueues a libmxvl kernel: entry `name` (one whose prototype ends in `void *hip_stream`) on
+    `device`'s current stream, with `device` current -- libmxvl's hipFuncSetAttribute calls act on the current device -- and a
+    non-zero status raised by check().  A descriptor is an entry's first parameter (include/mxvl.h) and goes by reference; the
+    other arguments pass as they are.  A name libmxvl does not export raises before anything is called."""
+    fn = getattr(_lib or load(), name)
+    with torch.cuda.device(device):
+        rc = fn(ctypes.byref(first) if isinstance(first, ctypes.Structure) else first, *rest, stream_ptr(device))
+    check(rc, name)

@@ -9,8 +9,6 @@ padding=W-1) (:78-86, :672-673) and the roll-and-dot decode step (:724-730).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _abi
@@ -33,7 +31,6 @@ def _w2(weight):
 
 
 def conv1d_fwd_raw(x, w32, b32, silu):
-    lib = _abi.load()
     batch, dim, L = x.shape
     y = torch.empty_like(x)  # follows x's memory layout (channel-major inside the mixer)
     d = _abi.Conv1dDesc()
@@ -41,15 +38,13 @@ def conv1d_fwd_raw(x, w32, b32, silu):
     d.io_dtype, d.silu = _abi.dtype_code(x.dtype), silu
     d.x_bs, d.x_ds, d.y_bs, d.y_ds = x.stride(0), x.stride(1), y.stride(0), y.stride(1)
     d.x, d.weight, d.bias, d.y = x.data_ptr(), w32.data_ptr(), _abi.ptr(b32), y.data_ptr()
-    with torch.cuda.device(x.device):
-        _abi.check(lib.mxvl_conv1d_fwd(ctypes.byref(d), _abi.stream_ptr(x.device)), "mxvl_conv1d_fwd")
+    _abi.launch("mxvl_conv1d_fwd", d, device=x.device)
     return y
 
 
 def conv1d_bwd_raw(x, w32, b32, silu, dy, dx=None):
     """dx may be passed in (x's dtype, seqlen-contiguous, any batch/channel strides): the fused mixer backward has the
     kernel write the x half of d(xz) in place."""
-    lib = _abi.load()
     batch, dim, L = x.shape
     if dy.stride(-1) != 1:
         dy = dy.contiguous()
@@ -65,8 +60,7 @@ def conv1d_bwd_raw(x, w32, b32, silu, dy, dx=None):
     f.x, f.weight, f.bias = x.data_ptr(), w32.data_ptr(), _abi.ptr(b32)
     d.dy_bs, d.dy_ds, d.dx_bs, d.dx_ds = dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1)
     d.dy, d.dx, d.dweight, d.dbias = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), _abi.ptr(db)
-    with torch.cuda.device(x.device):
-        _abi.check(lib.mxvl_conv1d_bwd(ctypes.byref(d), _abi.stream_ptr(x.device)), "mxvl_conv1d_bwd")
+    _abi.launch("mxvl_conv1d_bwd", d, device=x.device)
     return dx, dw, db
 
 
@@ -107,7 +101,6 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
     """x: (batch, dim); conv_state: (batch, dim, width), rolled IN PLACE; returns (batch, dim)."""
     silu = _act_flag(activation)
     _abi.require_gpu(x, conv_state, weight, bias)
-    lib = _abi.load()
     if conv_state.dtype != x.dtype or not conv_state.is_contiguous():
         raise RuntimeError("causal_conv1d_update: conv_state must be contiguous and share x's dtype")
     x = x.contiguous()
@@ -115,8 +108,6 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
     b32 = bias.detach().float().contiguous() if bias is not None else None
     batch, dim = x.shape
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = lib.mxvl_conv1d_update(x.data_ptr(), conv_state.data_ptr(), w32.data_ptr(), _abi.ptr(b32), y.data_ptr(),
-                                    batch, dim, w32.shape[1], _abi.dtype_code(x.dtype), silu, _abi.stream_ptr(x.device))
-    _abi.check(rc, "mxvl_conv1d_update")
+    _abi.launch("mxvl_conv1d_update", x.data_ptr(), conv_state.data_ptr(), w32.data_ptr(), _abi.ptr(b32), y.data_ptr(),
+                batch, dim, w32.shape[1], _abi.dtype_code(x.dtype), silu, device=x.device)
     return y

@@ -10,8 +10,6 @@ in include/mxvl.h.  There is no fallback: CPU tensors raise (tests compare again
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _abi
@@ -51,7 +49,6 @@ def _fill(desc, q, k, v, out, lse, scale, mask_mode, cluster, key_mask, bias, dr
 
 
 def attn_fwd_raw(q, k, v, scale, mask_mode=0, cluster=16, key_mask=None, bias=None, want_lse=True, drop=(0.0, 0)):
-    lib = _abi.load()
     _abi.require_gpu(q, k, v)
     B, H, Lq, D = q.shape
     if k.shape[0] != B or v.shape != k.shape or k.shape[3] != D or H % k.shape[1] != 0:
@@ -71,13 +68,11 @@ def attn_fwd_raw(q, k, v, scale, mask_mode=0, cluster=16, key_mask=None, bias=No
     lse = torch.empty(B, H, Lq, dtype=torch.float32, device=q.device) if want_lse else None
     desc = _abi.AttnDesc()
     _fill(desc, q, k, v, out, lse, scale, mask_mode, cluster, key_mask, bias, drop)
-    with torch.cuda.device(q.device):
-        _abi.check(lib.mxvl_attn_fwd(ctypes.byref(desc), _abi.stream_ptr(q.device)), "mxvl_attn_fwd")
+    _abi.launch("mxvl_attn_fwd", desc, device=q.device)
     return out, lse, (q, k, v, key_mask, bias)
 
 
 def attn_bwd_raw(saved, out, lse, dout, scale, mask_mode, cluster, dq=None, dk=None, dv=None, drop=(0.0, 0)):
-    lib = _abi.load()
     q, k, v, key_mask, bias = saved
     B, H, Lq, D = q.shape
     dout = _prep(dout.to(q.dtype))
@@ -92,8 +87,7 @@ def attn_bwd_raw(saved, out, lse, dout, scale, mask_mode, cluster, dq=None, dk=N
     desc.dk_bs, desc.dk_hs, desc.dk_ts = dk.stride(0), dk.stride(1), dk.stride(2)
     desc.dv_bs, desc.dv_hs, desc.dv_ts = dv.stride(0), dv.stride(1), dv.stride(2)
     desc.dout, desc.dq, desc.dk, desc.dv, desc.delta = dout.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
-    with torch.cuda.device(q.device):
-        _abi.check(lib.mxvl_attn_bwd(ctypes.byref(desc), _abi.stream_ptr(q.device)), "mxvl_attn_bwd")
+    _abi.launch("mxvl_attn_bwd", desc, device=q.device)
     return dq, dk, dv
 
 

@@ -8,8 +8,6 @@
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _abi, autograd_util
@@ -35,7 +33,6 @@ def _autocast_dtype(x):
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, branch, weight, bias, eps, out_dtype):
-        lib = _abi.load()
         C = x.shape[-1]
         x2 = x.reshape(-1, C)
         if not x2.is_contiguous():
@@ -64,8 +61,7 @@ class _AddLayerNorm(torch.autograd.Function):
         d.res_dtype, d.branch_dtype, d.out_dtype = _abi.dtype_code(x2.dtype), _abi.dtype_code(br_dtype), _abi.dtype_code(out_dtype)
         d.x, d.branch, d.gamma, d.beta = x2.data_ptr(), _abi.ptr(b2), w.data_ptr(), _abi.ptr(bta)
         d.h, d.n, d.mean, d.rstd = h.data_ptr(), n.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-        with torch.cuda.device(x.device):
-            _abi.check(lib.mxvl_add_layernorm_fwd(ctypes.byref(d), _abi.stream_ptr(x.device)), "mxvl_add_layernorm_fwd")
+        _abi.launch("mxvl_add_layernorm_fwd", d, device=x.device)
         ctx.save_for_backward(h, w, mean, rstd)
         ctx.meta = (x.shape, branch is not None, br_dtype, branch.dtype if branch is not None else None, out_dtype,
                     weight.dtype, bias is not None, bias.dtype if bias is not None else None)
@@ -91,8 +87,7 @@ class _AddLayerNorm(torch.autograd.Function):
         d.dn, d.dh, d.h, d.gamma, d.mean, d.rstd = dn2.data_ptr(), _abi.ptr(dh2), h.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr()
         d.dx, d.dbranch, d.partial_dgamma, d.partial_dbeta = dx.data_ptr(), _abi.ptr(dbr), pg.data_ptr(), pb.data_ptr()
         d.partial_dbranch = pgb[2].data_ptr() if has_br else None
-        with torch.cuda.device(h.device):
-            _abi.check(lib.mxvl_add_layernorm_bwd(ctypes.byref(d), _abi.stream_ptr(h.device)), "mxvl_add_layernorm_bwd")
+        _abi.launch("mxvl_add_layernorm_bwd", d, device=h.device)
         gb = pgb.sum(1)
         dgamma = gb[0].to(w_dtype)
         dbeta = gb[1].to(b_dtype) if has_bias else None
@@ -124,15 +119,12 @@ def add_layer_norm(x, branch, weight, bias, eps=1e-5, out_dtype=None):
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ab):
-        lib = _abi.load()
         H = ab.shape[-1] // 2
         ab2 = ab.reshape(-1, 2 * H)
         if not ab2.is_contiguous():
             ab2 = ab2.contiguous()
         y = torch.empty((ab2.shape[0], H), dtype=ab.dtype, device=ab.device)
-        with torch.cuda.device(ab.device):
-            _abi.check(lib.mxvl_swiglu_fwd(ab2.data_ptr(), y.data_ptr(), ab2.shape[0], H, _abi.dtype_code(ab.dtype),
-                                           _abi.stream_ptr(ab.device)), "mxvl_swiglu_fwd")
+        _abi.launch("mxvl_swiglu_fwd", ab2.data_ptr(), y.data_ptr(), ab2.shape[0], H, _abi.dtype_code(ab.dtype), device=ab.device)
         ctx.save_for_backward(ab2)
         ctx.shape = ab.shape
         return y.view(*ab.shape[:-1], H)
@@ -140,13 +132,10 @@ class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (ab2,) = ctx.saved_tensors
-        lib = _abi.load()
         H = ab2.shape[1] // 2
         dy2 = dy.reshape(-1, H).to(ab2.dtype).contiguous()
         dab = torch.empty_like(ab2)
-        with torch.cuda.device(ab2.device):
-            _abi.check(lib.mxvl_swiglu_bwd(ab2.data_ptr(), dy2.data_ptr(), dab.data_ptr(), ab2.shape[0], H,
-                                           _abi.dtype_code(ab2.dtype), _abi.stream_ptr(ab2.device)), "mxvl_swiglu_bwd")
+        _abi.launch("mxvl_swiglu_bwd", ab2.data_ptr(), dy2.data_ptr(), dab.data_ptr(), ab2.shape[0], H, _abi.dtype_code(ab2.dtype), device=ab2.device)
         return dab.view(ctx.shape)
 
 
@@ -159,7 +148,6 @@ def gemm_swiglu_supported(x2: torch.Tensor, w: torch.Tensor) -> bool:
 
 def gemm_swiglu_fwd_raw(x2, w, bias=None, want_ab=True):
     """One mxvl_gemm_swiglu_fwd call: x2 (M, K), w (2H, K) = [w1; w2], bias (2H) fp32 / io dtype -> (h (M, H), ab (M, 2H) | None)."""
-    lib = _abi.load()
     M, K = x2.shape
     H = w.shape[0] // 2
     h = torch.empty((M, H), dtype=x2.dtype, device=x2.device)
@@ -172,8 +160,7 @@ def gemm_swiglu_fwd_raw(x2, w, bias=None, want_ab=True):
     d.bias_dtype = _abi.dtype_code(bias.dtype) if bias is not None else 0
     d.x_rs, d.w_rs, d.ab_rs, d.h_rs = x2.stride(0), w.stride(0), 2 * H, H
     d.x, d.weight, d.bias, d.ab, d.h = x2.data_ptr(), w.data_ptr(), _abi.ptr(bias), _abi.ptr(ab), h.data_ptr()
-    with torch.cuda.device(x2.device):
-        _abi.check(lib.mxvl_gemm_swiglu_fwd(ctypes.byref(d), _abi.stream_ptr(x2.device)), "mxvl_gemm_swiglu_fwd")
+    _abi.launch("mxvl_gemm_swiglu_fwd", d, device=x2.device)
     return h, ab
 
 
@@ -186,7 +173,6 @@ class _LinearSwiGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         from .selective_scan_interface import _compute_dtype
-        lib = _abi.load()
         cd = _compute_dtype(x)
         x2 = x.reshape(-1, x.shape[-1]).to(cd)
         w = autograd_util.cast_param(weight, cd)
@@ -200,9 +186,7 @@ class _LinearSwiGLU(torch.autograd.Function):
         else:
             ab = torch.nn.functional.linear(x2, w, None if bias is None else autograd_util.cast_param(bias, cd))
             y = torch.empty((ab.shape[0], H), dtype=ab.dtype, device=ab.device)
-            with torch.cuda.device(ab.device):
-                _abi.check(lib.mxvl_swiglu_fwd(ab.data_ptr(), y.data_ptr(), ab.shape[0], H, _abi.dtype_code(ab.dtype),
-                                               _abi.stream_ptr(ab.device)), "mxvl_swiglu_fwd")
+            _abi.launch("mxvl_swiglu_fwd", ab.data_ptr(), y.data_ptr(), ab.shape[0], H, _abi.dtype_code(ab.dtype), device=ab.device)
         if needs_grad:
             ctx.save_for_backward(x2, w, ab)
         ctx.meta = (x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype)
@@ -219,17 +203,15 @@ class _LinearSwiGLU(torch.autograd.Function):
         dab = torch.empty_like(ab)
         n_part = lib.mxvl_swiglu_partials(rows, H) if bdt is not None else 0
         db = None
-        with torch.cuda.device(ab.device):
-            if n_part > 0:
-                partial = torch.empty((n_part, 2 * H), dtype=torch.float32, device=ab.device)
-                _abi.check(lib.mxvl_swiglu_bwd_colsum(ab.data_ptr(), dy2.data_ptr(), dab.data_ptr(), partial.data_ptr(), n_part, rows, H,
-                                                      _abi.dtype_code(ab.dtype), _abi.stream_ptr(ab.device)), "mxvl_swiglu_bwd_colsum")
-                db = partial.sum(0).to(bdt)
-            else:
-                _abi.check(lib.mxvl_swiglu_bwd(ab.data_ptr(), dy2.data_ptr(), dab.data_ptr(), rows, H, _abi.dtype_code(ab.dtype),
-                                               _abi.stream_ptr(ab.device)), "mxvl_swiglu_bwd")
-                if bdt is not None:
-                    db = dab.sum(0, dtype=torch.float32).to(bdt)
+        if n_part > 0:
+            partial = torch.empty((n_part, 2 * H), dtype=torch.float32, device=ab.device)
+            _abi.launch("mxvl_swiglu_bwd_colsum", ab.data_ptr(), dy2.data_ptr(), dab.data_ptr(), partial.data_ptr(), n_part, rows, H,
+                        _abi.dtype_code(ab.dtype), device=ab.device)
+            db = partial.sum(0).to(bdt)
+        else:
+            _abi.launch("mxvl_swiglu_bwd", ab.data_ptr(), dy2.data_ptr(), dab.data_ptr(), rows, H, _abi.dtype_code(ab.dtype), device=ab.device)
+            if bdt is not None:
+                db = dab.sum(0, dtype=torch.float32).to(bdt)
         dx = torch.matmul(dab, w).view(shape).to(xdt)
         dw = splitk_wgrad(dab, x2, wdt)
         return dx, dw, db
@@ -247,8 +229,7 @@ def gemm_swiglu_bwd_raw(dy2, w3t, ab, want_colsum=True):
     d.M, d.K, d.H, d.io_dtype = M, K, H, _abi.dtype_code(dy2.dtype)
     d.dy_rs, d.w_rs, d.ab_rs, d.dab_rs = dy2.stride(0), w3t.stride(0), ab.stride(0), dab.stride(0)
     d.dy, d.w3t, d.ab, d.dab, d.partial = dy2.data_ptr(), w3t.data_ptr(), ab.data_ptr(), dab.data_ptr(), _abi.ptr(partial)
-    with torch.cuda.device(dy2.device):
-        _abi.check(lib.mxvl_gemm_swiglu_bwd(ctypes.byref(d), _abi.stream_ptr(dy2.device)), "mxvl_gemm_swiglu_bwd")
+    _abi.launch("mxvl_gemm_swiglu_bwd", d, device=dy2.device)
     return dab, (partial.sum(0) if partial is not None else None)
 
 
@@ -307,9 +288,8 @@ def _mlp_swiglu_bwd(x2, w, ab, h, w3c, dy, want_b12, want_b3):
         dab = torch.empty_like(ab)
         n_part = lib.mxvl_swiglu_partials(rows, H) if want_b12 else 0
         partial = torch.empty((max(n_part, 1), 2 * H), dtype=torch.float32, device=ab.device)
-        with torch.cuda.device(ab.device):
-            _abi.check(lib.mxvl_swiglu_bwd_colsum(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), partial.data_ptr(), n_part, rows, H,
-                                                  _abi.dtype_code(ab.dtype), _abi.stream_ptr(ab.device)), "mxvl_swiglu_bwd_colsum")
+        _abi.launch("mxvl_swiglu_bwd_colsum", ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), partial.data_ptr(), n_part, rows, H,
+                    _abi.dtype_code(ab.dtype), device=ab.device)
         if want_b12:
             db12 = partial.sum(0)
     dw3 = splitk_wgrad(d2, h, torch.float32)
@@ -405,7 +385,6 @@ def rope_supported(q, k, cos, sin) -> bool:
 
 
 def _rope_launch(q, k, cos, sin, backward):
-    lib = _abi.load()
     B, T, Hq, D = q.shape
     Hk = k.shape[2]
     qo = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
@@ -420,8 +399,7 @@ def _rope_launch(q, k, cos, sin, backward):
     d.ko_bs, d.ko_ts, d.ko_hs = ko.stride(0), ko.stride(1), ko.stride(2)
     d.cs_bs, d.cs_ts = (0 if cos.shape[0] == 1 else cos.stride(0)), cos.stride(1)
     d.q, d.k, d.cos, d.sin, d.q_out, d.k_out = q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), qo.data_ptr(), ko.data_ptr()
-    with torch.cuda.device(q.device):
-        _abi.check(lib.mxvl_rope(ctypes.byref(d), _abi.stream_ptr(q.device)), "mxvl_rope")
+    _abi.launch("mxvl_rope", d, device=q.device)
     return qo, ko
 
 
@@ -458,7 +436,6 @@ def rms_norm_supported(x, weight) -> bool:
 class _RmsNormFrozen(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps, out_dtype):
-        lib = _abi.load()
         C = x.shape[-1]
         x2 = x.reshape(-1, C)
         if not x2.is_contiguous() or x2.data_ptr() % 16:
@@ -472,8 +449,7 @@ class _RmsNormFrozen(torch.autograd.Function):
         d.rows, d.cols, d.eps = rows, C, eps
         d.x_dtype, d.w_dtype, d.y_dtype = _abi.dtype_code(x2.dtype), _abi.dtype_code(w.dtype), _abi.dtype_code(out_dtype)
         d.x, d.weight, d.grad, d.y, d.rstd = x2.data_ptr(), w.data_ptr(), None, y.data_ptr(), _abi.ptr(rstd)
-        with torch.cuda.device(x.device):
-            _abi.check(lib.mxvl_rmsnorm_train_fwd(ctypes.byref(d), _abi.stream_ptr(x.device)), "mxvl_rmsnorm_train_fwd")
+        _abi.launch("mxvl_rmsnorm_train_fwd", d, device=x.device)
         if need:
             ctx.save_for_backward(x2, w, rstd)
             ctx.meta = (x.shape, eps, out_dtype)
@@ -483,7 +459,6 @@ class _RmsNormFrozen(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w, rstd = ctx.saved_tensors
         shape, eps, out_dtype = ctx.meta
-        lib = _abi.load()
         rows, C = x2.shape
         g = dy.reshape(rows, C)
         if g.dtype != out_dtype or not g.is_contiguous() or g.data_ptr() % 16:
@@ -493,8 +468,7 @@ class _RmsNormFrozen(torch.autograd.Function):
         d.rows, d.cols, d.eps = rows, C, eps
         d.x_dtype, d.w_dtype, d.y_dtype = _abi.dtype_code(x2.dtype), _abi.dtype_code(w.dtype), _abi.dtype_code(out_dtype)
         d.x, d.weight, d.grad, d.y, d.rstd = x2.data_ptr(), w.data_ptr(), g.data_ptr(), dx.data_ptr(), rstd.data_ptr()
-        with torch.cuda.device(x2.device):
-            _abi.check(lib.mxvl_rmsnorm_train_bwd(ctypes.byref(d), _abi.stream_ptr(x2.device)), "mxvl_rmsnorm_train_bwd")
+        _abi.launch("mxvl_rmsnorm_train_bwd", d, device=x2.device)
         return dx.view(shape), None, None, None
 
 
@@ -517,23 +491,18 @@ def silu_mul_supported(a, b) -> bool:
 class _SiluMul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
-        lib = _abi.load()
         y = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            _abi.check(lib.mxvl_silu_mul(a.data_ptr(), b.data_ptr(), None, y.data_ptr(), None, a.numel(), _abi.dtype_code(a.dtype),
-                                         _abi.stream_ptr(a.device)), "mxvl_silu_mul")
+        _abi.launch("mxvl_silu_mul", a.data_ptr(), b.data_ptr(), None, y.data_ptr(), None, a.numel(), _abi.dtype_code(a.dtype), device=a.device)
         ctx.save_for_backward(a, b)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         a, b = ctx.saved_tensors
-        lib = _abi.load()
         g = dy.to(a.dtype).contiguous()
         da, db = torch.empty_like(a), torch.empty_like(b)
-        with torch.cuda.device(a.device):
-            _abi.check(lib.mxvl_silu_mul(a.data_ptr(), b.data_ptr(), g.data_ptr(), da.data_ptr(), db.data_ptr(), a.numel(),
-                                         _abi.dtype_code(a.dtype), _abi.stream_ptr(a.device)), "mxvl_silu_mul")
+        _abi.launch("mxvl_silu_mul", a.data_ptr(), b.data_ptr(), g.data_ptr(), da.data_ptr(), db.data_ptr(), a.numel(), _abi.dtype_code(a.dtype),
+                    device=a.device)
         return da, db
 
 

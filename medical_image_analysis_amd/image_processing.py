@@ -14,7 +14,6 @@ same bits out as the CPU pipeline, in the dtype the encoder wants.  There is no 
 """
 from __future__ import annotations
 
-import ctypes
 import functools
 import json
 import os
@@ -84,9 +83,7 @@ def preprocess_image(img: torch.Tensor, out_h: int, out_w: int, resample: int, t
     d.out_dtype = _abi.dtype_code(out.dtype)
     d.src, d.bounds_h, d.kk_h, d.bounds_v, d.kk_v = img.data_ptr(), b_h.data_ptr(), k_h.data_ptr(), b_v.data_ptr(), k_v.data_ptr()
     d.lut, d.tmp, d.out = table.data_ptr(), tmp.data_ptr(), out.data_ptr()
-    with torch.cuda.device(dev):
-        rc = _abi.load().mxvl_image_preprocess(ctypes.byref(d), _abi.stream_ptr(dev))
-    _abi.check(rc, "mxvl_image_preprocess")
+    _abi.launch("mxvl_image_preprocess", d, device=dev)
     return out
 
 

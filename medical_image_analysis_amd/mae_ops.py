@@ -15,15 +15,12 @@ from . import _abi
 
 
 def _gather(src, idx, fill, add, out_dtype, rows_out):
-    lib = _abi.load()
     N, Ls, D = src.shape
     if not src.is_contiguous():
         src = src.contiguous()
     out = torch.empty((N, rows_out, D), dtype=out_dtype, device=src.device)
-    with torch.cuda.device(src.device):
-        _abi.check(lib.mxvl_row_gather(src.data_ptr(), idx.data_ptr(), _abi.ptr(fill), _abi.ptr(add), out.data_ptr(), N, Ls, rows_out, D,
-                                       Ls * D, rows_out * D, _abi.dtype_code(src.dtype), _abi.dtype_code(out_dtype),
-                                       _abi.stream_ptr(src.device)), "mxvl_row_gather")
+    _abi.launch("mxvl_row_gather", src.data_ptr(), idx.data_ptr(), _abi.ptr(fill), _abi.ptr(add), out.data_ptr(), N, Ls, rows_out, D, Ls * D,
+                rows_out * D, _abi.dtype_code(src.dtype), _abi.dtype_code(out_dtype), device=src.device)
     return out
 
 
@@ -90,13 +87,11 @@ def unshuffle_with_mask_tokens(x, ids_restore, mask_token, pos_embed):
 class _PatchLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, imgs, pred, patch, norm):
-        lib = _abi.load()
         N, C, H, W = imgs.shape
         L = (H // patch) * (W // patch)
         loss = torch.empty((N, L), dtype=torch.float32, device=pred.device)
-        with torch.cuda.device(pred.device):
-            _abi.check(lib.mxvl_patch_loss(imgs.data_ptr(), pred.data_ptr(), None, loss.data_ptr(), None, N, C, H, patch, int(norm),
-                                           _abi.dtype_code(pred.dtype), _abi.stream_ptr(pred.device)), "mxvl_patch_loss")
+        _abi.launch("mxvl_patch_loss", imgs.data_ptr(), pred.data_ptr(), None, loss.data_ptr(), None, N, C, H, patch, int(norm),
+                    _abi.dtype_code(pred.dtype), device=pred.device)
         ctx.save_for_backward(imgs, pred)
         ctx.cfg = (patch, norm)
         return loss
@@ -105,13 +100,11 @@ class _PatchLoss(torch.autograd.Function):
     def backward(ctx, dloss):
         imgs, pred = ctx.saved_tensors
         patch, norm = ctx.cfg
-        lib = _abi.load()
         N, C, H, W = imgs.shape
         dl = dloss.float().contiguous()
         dpred = torch.empty_like(pred)
-        with torch.cuda.device(pred.device):
-            _abi.check(lib.mxvl_patch_loss(imgs.data_ptr(), pred.data_ptr(), dl.data_ptr(), None, dpred.data_ptr(), N, C, H, patch, int(norm),
-                                           _abi.dtype_code(pred.dtype), _abi.stream_ptr(pred.device)), "mxvl_patch_loss")
+        _abi.launch("mxvl_patch_loss", imgs.data_ptr(), pred.data_ptr(), dl.data_ptr(), None, dpred.data_ptr(), N, C, H, patch, int(norm),
+                    _abi.dtype_code(pred.dtype), device=pred.device)
         return None, dpred, None, None
 
 
@@ -130,12 +123,10 @@ def patch_loss(imgs, pred, patch, norm_pix_loss):
 class _PatchCols(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, patch, out_dtype):
-        lib = _abi.load()
         N, C, H, W = img.shape
         cols = torch.empty((N, (H // patch) * (W // patch), C * patch * patch), dtype=out_dtype, device=img.device)
-        with torch.cuda.device(img.device):
-            _abi.check(lib.mxvl_patch_cols(img.data_ptr(), cols.data_ptr(), N, C, H, W, patch, _abi.dtype_code(img.dtype),
-                                           _abi.dtype_code(out_dtype), _abi.stream_ptr(img.device)), "mxvl_patch_cols")
+        _abi.launch("mxvl_patch_cols", img.data_ptr(), cols.data_ptr(), N, C, H, W, patch, _abi.dtype_code(img.dtype), _abi.dtype_code(out_dtype),
+                    device=img.device)
         ctx.meta = (img.shape, img.dtype, patch)
         return cols
 
@@ -152,12 +143,10 @@ class _WindowCols(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_nhwc, k, relu):
-        lib = _abi.load()
         N, H, W, C = x_nhwc.shape
         cols = torch.empty((N, (H // k) * (W // k), k * k * C), dtype=x_nhwc.dtype, device=x_nhwc.device)
-        with torch.cuda.device(x_nhwc.device):
-            _abi.check(lib.mxvl_window_cols(x_nhwc.data_ptr(), None, cols.data_ptr(), N, H, W, C, k, int(relu), 0, _abi.dtype_code(x_nhwc.dtype),
-                                            _abi.stream_ptr(x_nhwc.device)), "mxvl_window_cols")
+        _abi.launch("mxvl_window_cols", x_nhwc.data_ptr(), None, cols.data_ptr(), N, H, W, C, k, int(relu), 0, _abi.dtype_code(x_nhwc.dtype),
+                    device=x_nhwc.device)
         if relu:
             ctx.save_for_backward(x_nhwc)
         ctx.meta = (x_nhwc.shape, k, relu)
@@ -166,13 +155,11 @@ class _WindowCols(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dcols):
         (N, H, W, C), k, relu = ctx.meta
-        lib = _abi.load()
         x = ctx.saved_tensors[0] if relu else None
         dcols = dcols.contiguous()
         dx = torch.empty((N, H, W, C), dtype=dcols.dtype, device=dcols.device)
-        with torch.cuda.device(dcols.device):
-            _abi.check(lib.mxvl_window_cols(_abi.ptr(x), dcols.data_ptr(), dx.data_ptr(), N, H, W, C, k, int(relu), 1, _abi.dtype_code(dcols.dtype),
-                                            _abi.stream_ptr(dcols.device)), "mxvl_window_cols (backward)")
+        _abi.launch("mxvl_window_cols", _abi.ptr(x), dcols.data_ptr(), dx.data_ptr(), N, H, W, C, k, int(relu), 1, _abi.dtype_code(dcols.dtype),
+                    device=dcols.device)
         return dx, None, None
 
 

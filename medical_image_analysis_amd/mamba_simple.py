@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import autograd_util
+from . import _abi, autograd_util
 from .causal_conv1d import causal_conv1d_fn, causal_conv1d_update
 from .selective_scan_interface import _SplitHalves, bimamba_inner_fn, mamba_inner_fn, proj_in, selective_scan_fn
 from .selective_state_update import selective_state_update
@@ -50,9 +50,6 @@ def _middle_cls_transpose_index(L: int, device) -> torch.Tensor:
 def _dir_perm(merge, rows, stacked, index, L, Lp, gate=None, pre=None, dgate=None, scale=1.0):
     """One mxvl_dir_gather / mxvl_dir_merge launch.  rows: (B, D, L) view (L stride 1); stacked: (B, K, D, Lp) view.
     gate / pre / dgate: the optional silu output gate of the merge and of its backward (csrc/dir_perm.hip)."""
-    import ctypes
-    from . import _abi
-    lib = _abi.load()
     d = _abi.DirPermDesc()
     B, K, D, _ = stacked.shape
     d.batch, d.dim, d.seqlen, d.padded_len, d.n_dirs, d.io_dtype = B, D, L, Lp, K, _abi.dtype_code(rows.dtype)
@@ -65,9 +62,7 @@ def _dir_perm(merge, rows, stacked, index, L, Lp, gate=None, pre=None, dgate=Non
             d.pre, d.pre_bs, d.pre_ds = pre.data_ptr(), pre.stride(0), pre.stride(1)
         if dgate is not None:
             d.dgate, d.dgate_bs, d.dgate_ds = dgate.data_ptr(), dgate.stride(0), dgate.stride(1)
-    fn = lib.mxvl_dir_merge if merge else lib.mxvl_dir_gather
-    with torch.cuda.device(rows.device):
-        _abi.check(fn(ctypes.byref(d), _abi.stream_ptr(rows.device)), "mxvl_dir_merge" if merge else "mxvl_dir_gather")
+    _abi.launch("mxvl_dir_merge" if merge else "mxvl_dir_gather", d, device=rows.device)
 
 
 def _rows_view(t):

@@ -297,16 +297,13 @@ class _ClipLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, txt, logit_scale):
         from . import _abi
-        lib = _abi.load()
         img, txt = img.contiguous(), txt.contiguous()
         ls = logit_scale.detach().float().reshape(1).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=img.device)
         dimg, dtxt = torch.empty_like(img), torch.empty_like(txt)
         dsc = torch.empty((), dtype=torch.float32, device=img.device)
-        with torch.cuda.device(img.device):
-            _abi.check(lib.mxvl_clip_loss(img.data_ptr(), txt.data_ptr(), ls.data_ptr(), img.shape[0],
-                                          img.shape[1], loss.data_ptr(), dimg.data_ptr(), dtxt.data_ptr(), dsc.data_ptr(),
-                                          _abi.stream_ptr(img.device)), "mxvl_clip_loss")
+        _abi.launch("mxvl_clip_loss", img.data_ptr(), txt.data_ptr(), ls.data_ptr(), img.shape[0], img.shape[1], loss.data_ptr(), dimg.data_ptr(),
+                    dtxt.data_ptr(), dsc.data_ptr(), device=img.device)
         ctx.save_for_backward(dimg, dtxt, dsc)
         ctx.scale_dtype = logit_scale.dtype
         return loss

@@ -29,6 +29,7 @@ import math
 import torch
 import torch.nn as nn
 
+from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
 
 
@@ -240,8 +241,6 @@ class _BeamState:
 
     def _advance_hip(self, logits):
         """csrc/beam_step.hip: the whole update below as one kernel (capturable in the decode step's hipGraph)."""
-        import ctypes
-        from . import _abi
         lib = _abi.load()
         d = _abi.BeamDesc()
         d.batch, d.beams, d.vocab, d.max_new, d.min_new = self.B, self.nb, self.V, self.max_new, self.min_new
@@ -257,8 +256,7 @@ class _BeamState:
             if self.workspace is None:
                 self.workspace = torch.empty(max(int(lib.mxvl_beam_workspace_bytes(self.B, self.nb, self.keep)), 4), dtype=torch.uint8, device=logits.device)
             d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
-        with torch.cuda.device(logits.device):
-            _abi.check(lib.mxvl_beam_step(ctypes.byref(d), _abi.stream_ptr(logits.device)), "mxvl_beam_step")
+        _abi.launch("mxvl_beam_step", d, device=logits.device)
 
     def advance(self, logits):
         """Consume the (B*nb, V) logits of step `cur`; leaves the next tokens in .tok, the parent beam of every live
@@ -404,8 +402,6 @@ class _SampleState:
 
     def _advance_hip(self, logits):
         """csrc/sample_step.hip: the whole update below as one kernel (capturable in the decode step's hipGraph)."""
-        import ctypes
-        from . import _abi
         lib = _abi.load()
         if self.workspace is None:
             self.workspace = torch.empty(int(lib.mxvl_sample_workspace_bytes(self.B, self.V)), dtype=torch.uint8, device=logits.device)
@@ -417,8 +413,7 @@ class _SampleState:
         d.unfinished, d.unfinished_log, d.scratch = self.unfinished.data_ptr(), _abi.ptr(self.unf_log), self.ticket.data_ptr()
         d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         d.out_thresh, d.out_kept = self.out_thresh.data_ptr(), self.out_kept.data_ptr()
-        with torch.cuda.device(logits.device):
-            _abi.check(lib.mxvl_sample_step(ctypes.byref(d), _abi.stream_ptr(logits.device)), "mxvl_sample_step")
+        _abi.launch("mxvl_sample_step", d, device=logits.device)
 
     def advance(self, logits):
         """Consume the (B, V) logits of step `cur`; leaves the drawn tokens in .tok / .seq[:, cur] and whether decoding goes on in
@@ -506,7 +501,6 @@ class _KernelStepper(_SearchFusion):
     @staticmethod
     def supported(model, rows, dtype, device):
         if torch.device(device).type == "cuda":
-            from . import _abi
             _abi.load()          # a missing libmxvl.so is an error on a GPU box, never a silent torch path
         cfg = model.config
         D = cfg.hidden_size // cfg.num_attention_heads
@@ -533,10 +527,6 @@ class _KernelStepper(_SearchFusion):
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
 
     def __init__(self, model, rows, prompt_mask, dyn_cache, max_new, dtype):
-        import ctypes
-        from . import _abi
-        self._abi, self._ct = _abi, ctypes
-        self.lib = _abi.load()
         dev = prompt_mask.device
         cfg = model.config
         self.model, self.rows = model, rows
@@ -632,7 +622,7 @@ class _KernelStepper(_SearchFusion):
             k, v = at._vision_kv(lay.input_layernorm(lay.vis_x.to(self.x.dtype)))           # (Bv, Hkv, Lv, D) views
             km = lay.cross_attn_mask
             on = (lay.media_locations == 3).sum(dim=-1).bool()
-            flags = self._abi.GATE_TANH if any(isinstance(mod, nn.Tanh) for mod in at.cross_attn_gate_proj) else 0
+            flags = _abi.GATE_TANH if any(isinstance(mod, nn.Tanh) for mod in at.cross_attn_gate_proj) else 0
             lin = at.cross_attn_gate_proj[0]
             c = self.cond.get(i)
             if c is None or c["k"].shape != k.shape:
@@ -655,41 +645,41 @@ class _KernelStepper(_SearchFusion):
             del self.cond[i]
             self.graph = None
 
-    def _cross_attn(self, i, sp):
+    def _cross_attn(self, i):
         c = self.cond[i]
-        d = self._abi.DecodeCrossAttnDesc()
+        d = _abi.DecodeCrossAttnDesc()
         d.rows, d.n_heads, d.n_kv_heads, d.head_dim, d.n_keys = self.rows, self.H, self.Hkv, self.D, c["k"].shape[2]
         d.kv_rows_div, d.gate_flags, d.scale, d.dtype = c["div"], c["flags"], self.D ** -0.5, self.dt
         d.q_rope, d.k, d.v = self.q_rope.data_ptr(), c["k"].data_ptr(), c["v"].data_ptr()
-        d.key_mask, d.row_on = self._abi.ptr(c["km"]), c["on"].data_ptr()
+        d.key_mask, d.row_on = _abi.ptr(c["km"]), c["on"].data_ptr()
         d.text_state, d.out = self.att.data_ptr(), self.att2.data_ptr()
-        d.gate_weight, d.gate_bias, d.warm_up_gate = c["gate_w"].data_ptr(), c["gate_b"].data_ptr(), self._abi.ptr(c["warm"])
-        self._abi.check(self.lib.mxvl_decode_cross_attn(self._ct.byref(d), sp), "mxvl_decode_cross_attn")
+        d.gate_weight, d.gate_bias, d.warm_up_gate = c["gate_w"].data_ptr(), c["gate_b"].data_ptr(), _abi.ptr(c["warm"])
+        _abi.launch("mxvl_decode_cross_attn", d, device=self.x.device)
 
     def _rmsnorm(self, x, norm, eps, K, fold_res=None, x_out=None, splits=1):
         """rows > 8: RMSNorm ahead of an MFMA projection (the GEMV kernel, rows <= 8, normalises in its own prologue).  With
         fold_res the row is first completed from the split projection's fp32 sums: x_out = bf16(acc) + fold_res; acc is cleared."""
-        n = self._abi.RmsNormDesc()
+        n = _abi.RmsNormDesc()
         n.rows, n.K, n.eps, n.dtype = self.rows, K, eps, self.dt
-        n.x, n.weight, n.y = self._abi.ptr(x), norm.data_ptr(), self.xn.data_ptr()
+        n.x, n.weight, n.y = _abi.ptr(x), norm.data_ptr(), self.xn.data_ptr()
         if fold_res is not None:
             n.acc, n.residual, n.x_out, n.acc_splits = self.acc.data_ptr(), fold_res.data_ptr(), x_out.data_ptr(), splits
-        self._abi.check(self.lib.mxvl_decode_rmsnorm(self._ct.byref(n), self._abi.stream_ptr(self.x.device)), "mxvl_decode_rmsnorm")
+        _abi.launch("mxvl_decode_rmsnorm", n, device=self.x.device)
         return self.xn
 
     def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0):
-        d = self._abi.GemvDesc()
+        d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
-        d.x, d.norm_weight, d.W = x.data_ptr(), self._abi.ptr(norm), W.data_ptr()
+        d.x, d.norm_weight, d.W = x.data_ptr(), _abi.ptr(norm), W.data_ptr()
         if norm is not None and self._gain_scale:
             d.norm_gain_scale = self._gain_scale.get((norm.data_ptr(), norm._version), 1.0)
-        d.W2, d.bias, d.residual, d.y = self._abi.ptr(W2), self._abi.ptr(bias), self._abi.ptr(res), self._abi.ptr(y)
+        d.W2, d.bias, d.residual, d.y = _abi.ptr(W2), _abi.ptr(bias), _abi.ptr(res), _abi.ptr(y)
         if split:
             d.split_acc, d.k_splits = self.acc.data_ptr(), split
         elif self.batched:
             d.k_splits = 1
-        self._abi.check(self.lib.mxvl_decode_gemv(self._ct.byref(d), self._abi.stream_ptr(x.device)), "mxvl_decode_gemv")
+        _abi.launch("mxvl_decode_gemv", d, device=x.device)
 
     @staticmethod
     def _k_splits(N, K, rows=0):
@@ -707,7 +697,7 @@ class _KernelStepper(_SearchFusion):
     def _prologue(self, tok, beam, cur):
         """slot-table re-ordering, new position's slot / mask bit, token embeddings, RoPE rows: ONE launch (mxvl_decode_prologue)
         instead of 22 small torch kernels per token."""
-        d = self._abi.DecodePrologueDesc()
+        d = _abi.DecodePrologueDesc()
         d.rows, d.hidden, d.max_len, d.head_dim = self.rows, self.hidden, self.max_len, self.D
         d.prompt_len, d.table_len = self.P, self.cos_table.shape[0]
         d.tok, d.beam_src, d.cur, d.n_real = tok.data_ptr(), beam.data_ptr(), cur.data_ptr(), self.n_real.data_ptr()
@@ -715,7 +705,7 @@ class _KernelStepper(_SearchFusion):
         d.cos_table, d.sin_table = self.cos_table.data_ptr(), self.sin_table.data_ptr()
         d.slot_table, d.mask, d.x = self.slot.data_ptr(), self.mask.data_ptr(), self.x.data_ptr()
         d.cos, d.sin, d.pos = self.cos.data_ptr(), self.sin.data_ptr(), self.pos.data_ptr()
-        self._abi.check(self.lib.mxvl_decode_prologue(self._ct.byref(d), self._abi.stream_ptr(self.x.device)), "mxvl_decode_prologue")
+        _abi.launch("mxvl_decode_prologue", d, device=self.x.device)
 
     def _beams_attn_fits(self):
         """what mxvl_decode_attn checks before it runs the beams of a sample in one workgroup (csrc/decode.hip): 32-bit cache offsets
@@ -728,7 +718,7 @@ class _KernelStepper(_SearchFusion):
     def _body(self, tok, beam, cur):
         m = self.model
         self._prologue(tok, beam, cur)
-        a = self._abi.DecodeAttnDesc()
+        a = _abi.DecodeAttnDesc()
         a.rows, a.n_heads, a.n_kv_heads, a.head_dim, a.max_len = self.rows, self.H, self.Hkv, self.D, self.max_len
         a.scale, a.dtype = self.D ** -0.5, self.dt
         # the beams of a sample share a workgroup (and the cache lines they have in common) once head x sample workgroups fill the
@@ -736,7 +726,6 @@ class _KernelStepper(_SearchFusion):
         a.beams = self.beams if (2 <= self.beams <= 5 and self.H * (self.rows // self.beams) >= 128 and self._beams_attn_fits()) else 0
         a.qkv, a.cos, a.sin = self.qkv.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr()
         a.slot_table, a.pos, a.mask, a.out = self.slot.data_ptr(), self.pos.data_ptr(), self.mask.data_ptr(), self.att.data_ptr()
-        sp = self._abi.stream_ptr(self.x.device)
         batched = self.batched and not self.fused_norm   # MFMA projections with explicit RMSNorm launches; o_proj / down_proj split K and are folded by the next norm
         so, sd = (self._k_splits(self.hidden, self.H * self.D, self.rows), self._k_splits(self.hidden, self.inter, self.rows)) if batched else (0, 0)
         for i, layer in enumerate(m.model.layers):
@@ -751,10 +740,10 @@ class _KernelStepper(_SearchFusion):
                            bias=at.qkv_bias)
             a.k_cache, a.v_cache = self.kc[i].data_ptr(), self.vc[i].data_ptr()
             a.q_rope = self.q_rope.data_ptr() if i in self.cond else None
-            self._abi.check(self.lib.mxvl_decode_attn(self._ct.byref(a), sp), "mxvl_decode_attn")
+            _abi.launch("mxvl_decode_attn", a, device=self.x.device)
             att = self.att
             if i in self.cond:                       # gated image cross-attention on the rotated query, before o_proj
-                self._cross_attn(i, sp)
+                self._cross_attn(i)
                 att = self.att2
             if batched:
                 self._gemv(att, at.o_proj.weight, None, self.H * self.D, self.hidden, split=so)

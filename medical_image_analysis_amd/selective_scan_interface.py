@@ -15,8 +15,6 @@ csrc/selective_scan/cus/selective_scan.cpp:165-215 raised as RuntimeError.
 """
 from __future__ import annotations
 
-import ctypes
-
 import os
 
 import torch
@@ -29,18 +27,19 @@ from . import _abi, autograd_util
 KERNEL_TIMERS = None
 
 
-def _timed(kind, launch, work):
-    """rc = launch(); with KERNEL_TIMERS set, bracketed by HIP events on the current stream and recorded as
-    (kind, start, end, work()) -- `work` is only evaluated then."""
+def _timed(kind, name, desc, device, work):
+    """_abi.launch(name, desc, device=device); with KERNEL_TIMERS set, bracketed by HIP events on the device's current stream and
+    recorded as (kind, start, end, work()) -- `work` is only evaluated then.  A launch that fails raises from inside the bracket:
+    nothing is recorded for it."""
     timers = KERNEL_TIMERS
     if timers is None:
-        return launch()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    rc = launch()
-    e1.record()
+        return _abi.launch(name, desc, device=device)
+    with torch.cuda.device(device):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _abi.launch(name, desc, device=device)
+        e1.record()
     timers.append((kind, e0, e1, work()))
-    return rc
 
 
 def scan_algorithmic_bytes(batch, dim, L, N, G, elt, has_z, backward=False, n_ckpt=0):
@@ -176,11 +175,8 @@ def scan_fwd_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softp
                 ckpt = torch.empty((batch, dim, n_chunks, N), dtype=torch.float32, device=u.device)
     desc = _abi.ScanDesc()
     _fill_fwd(desc, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, last, ckpt, out_f32, fold)
-    with torch.cuda.device(u.device):
-        rc = _timed("scan_fwd", lambda: lib.mxvl_scan_fwd(ctypes.byref(desc), _abi.stream_ptr(u.device)),
-                    lambda: scan_algorithmic_bytes(batch, dim, L, N, B.shape[1], u.element_size(), z is not None, False,
-                                                   _ckpt_chunks(ckpt, batch, dim)))
-    _abi.check(rc, "mxvl_scan_fwd")
+    _timed("scan_fwd", "mxvl_scan_fwd", desc, u.device,
+           lambda: scan_algorithmic_bytes(batch, dim, L, N, B.shape[1], u.element_size(), z is not None, False, _ckpt_chunks(ckpt, batch, dim)))
     return out, last, ckpt
 
 
@@ -189,7 +185,6 @@ def scan_bwd_raw(u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout
     """One mxvl_scan_bwd call; returns du, ddelta, dA, dB, dC, dD, dz, ddelta_bias (fp32 for weights,B,C).
     du / dz (io dtype, seqlen-contiguous, any batch/channel strides) and dB / dC (fp32, ZEROED by the caller) may be passed
     in: the fused mixer backward lets the kernel write straight into the buffers the next GEMM reads."""
-    lib = _abi.load()
     batch, dim, L = u.shape
     dout_f32 = bool(dout_f32) and u.dtype != torch.float32      # dout read as fp32 by the kernel (oflex i16o32)
     if dout.dtype != (torch.float32 if dout_f32 else u.dtype):
@@ -231,11 +226,8 @@ def scan_bwd_raw(u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout
     desc.dA, desc.dB, desc.dC = dA.data_ptr(), dB.data_ptr(), dC.data_ptr()
     desc.dD, desc.ddelta_bias = _abi.ptr(dD), _abi.ptr(dbias)
     desc.workspace, desc.workspace_bytes = None, 0     # ABI v3 field, ignored since round 3 (dB / dC leave as fp32 atomics)
-    with torch.cuda.device(u.device):
-        rc = _timed("scan_bwd", lambda: lib.mxvl_scan_bwd(ctypes.byref(desc), _abi.stream_ptr(u.device)),
-                    lambda: scan_algorithmic_bytes(batch, dim, L, A.shape[1], B.shape[1], u.element_size(), z is not None, True,
-                                                   _ckpt_chunks(ckpt, batch, dim)))
-    _abi.check(rc, "mxvl_scan_bwd")
+    _timed("scan_bwd", "mxvl_scan_bwd", desc, u.device,
+           lambda: scan_algorithmic_bytes(batch, dim, L, A.shape[1], B.shape[1], u.element_size(), z is not None, True, _ckpt_chunks(ckpt, batch, dim)))
     if ratio > 1:
         ddelta = ddelta.view(batch, dim // ratio, ratio, L).sum(2, dtype=torch.float32).to(delta.dtype)
         if dbias is not None:
@@ -355,8 +347,6 @@ def wgrad_splits(K, M, N):
 
 def gemm_tn(a_km, b_kn, out=None, slices_per_xcd=0):
     """c (M, N) fp32 = a_km^T @ b_kn through mxvl_gemm_tn (csrc/gemm_tn.hip); `out`: an fp32 (M, N) tensor to ADD into."""
-    import ctypes
-    from . import _abi
     K, M = a_km.shape
     N = b_kn.shape[1]
     c = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=a_km.device)
@@ -365,10 +355,7 @@ def gemm_tn(a_km, b_kn, out=None, slices_per_xcd=0):
     d.accumulate, d.slices_per_xcd = (1 if out is not None else 0), slices_per_xcd
     d.a_rs, d.b_rs, d.c_rs = a_km.stride(0), b_kn.stride(0), c.stride(0)
     d.a, d.b, d.c = a_km.data_ptr(), b_kn.data_ptr(), c.data_ptr()
-    with torch.cuda.device(a_km.device):
-        rc = _timed("gemm_tn", lambda: _abi.load().mxvl_gemm_tn(ctypes.byref(d), _abi.stream_ptr(a_km.device)),
-                    lambda: 2 * K * M * N)          # MFMA-bound: the work figure is FLOPs, not bytes
-    _abi.check(rc, "mxvl_gemm_tn")
+    _timed("gemm_tn", "mxvl_gemm_tn", d, a_km.device, lambda: 2 * K * M * N)          # MFMA-bound: the work figure is FLOPs, not bytes
     return c
 
 
@@ -456,9 +443,7 @@ def colsum(d2):
     rows, C = d2.shape
     n = lib.mxvl_colsum_partials(rows, C)
     partial = torch.empty((n, C), dtype=torch.float32, device=d2.device)
-    with torch.cuda.device(d2.device):
-        _abi.check(lib.mxvl_colsum(d2.data_ptr(), partial.data_ptr(), rows, C, d2.stride(0), n, _abi.dtype_code(d2.dtype),
-                                   _abi.stream_ptr(d2.device)), "mxvl_colsum")
+    _abi.launch("mxvl_colsum", d2.data_ptr(), partial.data_ptr(), rows, C, d2.stride(0), n, _abi.dtype_code(d2.dtype), device=d2.device)
     return partial.sum(0) if n > 1 else partial[0]
 
 
@@ -833,14 +818,13 @@ class _MambaInnerNativeFn(torch.autograd.Function):
         desc.x_proj_weight, desc.dt_proj_weight = wx.data_ptr(), wdt.data_ptr()
         desc.out_proj_weight, desc.out_proj_bias = _abi.ptr(wo), _abi.ptr(bo)
         desc.A, desc.D, desc.delta_bias = A32.data_ptr(), _abi.ptr(D32), _abi.ptr(db32)
-        nbytes = lib.mxvl_mamba_inner_workspace_bytes(ctypes.byref(desc))
+        nbytes = lib.mxvl_mamba_inner_workspace_bytes(desc)
         if nbytes < 0:
             raise RuntimeError("mxvl_mamba_inner_workspace_bytes: invalid descriptor")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=xz.device)
         out = torch.empty((batch, L, desc.d_model) if wo is not None else (batch, d, L), dtype=io, device=xz.device)
         desc.out, desc.workspace, desc.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
-        with torch.cuda.device(xz.device):
-            _abi.check(lib.mxvl_mamba_inner_fwd(ctypes.byref(desc), _abi.stream_ptr(xz.device)), "mxvl_mamba_inner_fwd")
+        _abi.launch("mxvl_mamba_inner_fwd", desc, device=xz.device)
         ctx.save_for_backward(xz, w32, b32, wx, wdt, wo, bo, A32, D32, db32, ws)
         ctx.meta = (delta_softplus, conv_w.shape, conv_w.dtype, None if conv_b is None else conv_b.dtype, x_proj_w.dtype, dt_proj_w.dtype,
                     None if out_w is None else out_w.dtype, None if out_b is None else out_b.dtype, A.dtype,
@@ -868,15 +852,14 @@ class _MambaInnerNativeFn(torch.autograd.Function):
         dxz = torch.empty_like(xz)
         z32 = lambda t: torch.zeros(t.shape, dtype=torch.float32, device=dev) if t is not None else None
         dcw, dcb, dwx, dwdt, dwo, dbo, dA, dD, ddb = (z32(t) for t in (w32, b32, wx, wdt, wo, bo, A32, D32, db32))
-        nbytes = lib.mxvl_mamba_inner_bwd_workspace_bytes(ctypes.byref(f))
+        nbytes = lib.mxvl_mamba_inner_bwd_workspace_bytes(f)
         bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         b.dout, b.dxz = dout.data_ptr(), dxz.data_ptr()
         b.dconv_weight, b.dconv_bias, b.dx_proj_weight, b.ddt_proj_weight = dcw.data_ptr(), _abi.ptr(dcb), dwx.data_ptr(), dwdt.data_ptr()
         b.dout_proj_weight, b.dout_proj_bias = _abi.ptr(dwo), _abi.ptr(dbo)
         b.dA, b.dD, b.ddelta_bias = dA.data_ptr(), _abi.ptr(dD), _abi.ptr(ddb)
         b.workspace, b.workspace_bytes = bws.data_ptr(), nbytes
-        with torch.cuda.device(dev):
-            _abi.check(lib.mxvl_mamba_inner_bwd(ctypes.byref(b), _abi.stream_ptr(dev)), "mxvl_mamba_inner_bwd")
+        _abi.launch("mxvl_mamba_inner_bwd", b, device=dev)
         to = lambda t, dt: t.to(dt) if t is not None else None
         return (dxz, dcw.reshape(cw_shape).to(cw_dt), to(dcb, cb_dt), dwx.to(wx_dt), dwdt.to(wdt_dt), to(dwo, wo_dt), to(dbo, bo_dt),
                 dA.to(A_dt), to(dD, D_dt), to(ddb, bias_dt), None)

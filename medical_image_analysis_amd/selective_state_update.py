@@ -12,7 +12,6 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     """state: (batch, dim, dstate) fp32, updated IN PLACE; x, dt, z: (batch, dim); A: (dim, dstate);
     B, C: (batch, dstate); D, dt_bias: (dim,).  Returns out (batch, dim) in x.dtype."""
     _abi.require_gpu(state, x, dt, A, B, C, D, z, dt_bias)
-    lib = _abi.load()
     if state.dtype != torch.float32 or not state.is_contiguous():
         raise RuntimeError("selective_state_update: state must be contiguous float32")
     batch, dim, N = state.shape
@@ -25,9 +24,7 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     if tuple(x.shape) != (batch, dim) or tuple(A32.shape) != (dim, N) or tuple(B.shape) != (batch, N):
         raise RuntimeError("selective_state_update: shape mismatch")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = lib.mxvl_state_update(state.data_ptr(), x.data_ptr(), dt.data_ptr(), A32.data_ptr(), B.data_ptr(),
-                                   C.data_ptr(), _abi.ptr(D32), _abi.ptr(z), _abi.ptr(b32), out.data_ptr(),
-                                   batch, dim, N, _abi.dtype_code(io), int(bool(dt_softplus)), _abi.stream_ptr(x.device))
-    _abi.check(rc, "mxvl_state_update")
+    _abi.launch("mxvl_state_update", state.data_ptr(), x.data_ptr(), dt.data_ptr(), A32.data_ptr(), B.data_ptr(),
+                C.data_ptr(), _abi.ptr(D32), _abi.ptr(z), _abi.ptr(b32), out.data_ptr(),
+                batch, dim, N, _abi.dtype_code(io), int(bool(dt_softplus)), device=x.device)
     return out

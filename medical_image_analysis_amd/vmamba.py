@@ -32,13 +32,10 @@ from .models_mamba import run_blocks
 # ---- the 4-direction orderings ------------------------------------------------------------------------------------
 def _cross(t: torch.Tensor, B: int, C: int, H: int, W: int, merge: bool) -> torch.Tensor:
     _abi.require_gpu(t)
-    lib = _abi.load()
     t = t.contiguous()
     out = t.new_empty((B, C, H * W) if merge else (B, 4, C, H * W))
-    fn = lib.mxvl_cross_merge if merge else lib.mxvl_cross_scan
-    with torch.cuda.device(t.device):
-        rc = fn(t.data_ptr(), out.data_ptr(), B, C, H, W, _abi.dtype_code(t.dtype), _abi.stream_ptr(t.device))
-    _abi.check(rc, "mxvl_cross_merge" if merge else "mxvl_cross_scan")
+    _abi.launch("mxvl_cross_merge" if merge else "mxvl_cross_scan", t.data_ptr(), out.data_ptr(), B, C, H, W, _abi.dtype_code(t.dtype),
+                device=t.device)
     return out
 
 
@@ -79,15 +76,13 @@ class _DwConv2dAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, silu):
-        lib = _abi.load()
         x = x.contiguous()
         B, C, H, W = x.shape
         w = weight.reshape(C, 9).float().contiguous()
         b = bias.float().contiguous() if bias is not None else None
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _abi.check(lib.mxvl_dwconv2d_fwd(x.data_ptr(), w.data_ptr(), _abi.ptr(b), y.data_ptr(), B, C, H, W, 3,
-                                             _abi.dtype_code(x.dtype), int(silu), _abi.stream_ptr(x.device)), "mxvl_dwconv2d_fwd")
+        _abi.launch("mxvl_dwconv2d_fwd", x.data_ptr(), w.data_ptr(), _abi.ptr(b), y.data_ptr(), B, C, H, W, 3, _abi.dtype_code(x.dtype), int(silu),
+                    device=x.device)
         ctx.save_for_backward(x, w, b)
         ctx.meta = (silu, weight.shape, weight.dtype, None if bias is None else bias.dtype)
         return y
@@ -96,16 +91,13 @@ class _DwConv2dAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, b = ctx.saved_tensors
         silu, wshape, wdt, bdt = ctx.meta
-        lib = _abi.load()
         B, C, H, W = x.shape
         dy = dy.to(x.dtype).contiguous()
         dx = torch.empty_like(x)
         dw = torch.zeros_like(w)
         db = torch.zeros(C, dtype=torch.float32, device=x.device) if b is not None else None
-        with torch.cuda.device(x.device):
-            _abi.check(lib.mxvl_dwconv2d_bwd(x.data_ptr(), w.data_ptr(), _abi.ptr(b), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                             _abi.ptr(db), B, C, H, W, 3, _abi.dtype_code(x.dtype), int(silu),
-                                             _abi.stream_ptr(x.device)), "mxvl_dwconv2d_bwd")
+        _abi.launch("mxvl_dwconv2d_bwd", x.data_ptr(), w.data_ptr(), _abi.ptr(b), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), _abi.ptr(db), B, C, H,
+                    W, 3, _abi.dtype_code(x.dtype), int(silu), device=x.device)
         return dx, dw.view(wshape).to(wdt), (db.to(bdt) if db is not None else None), None
 
 

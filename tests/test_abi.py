@@ -1,8 +1,11 @@
 """CPU: the C-ABI library loads, exports every symbol include/mxvl.h declares, the ctypes structs
 match the header's field order, and argument validation rejects bad descriptors without a GPU."""
+import ast
 import ctypes
+import glob
 import os
 import re
+import types
 
 import pytest
 
@@ -47,9 +50,10 @@ def test_ctypes_struct_mirrors_header(cstruct, pystruct):
     assert names == [f[0] for f in pystruct._fields_]
 
 
-def _prototypes():
+def _prototypes(with_names=False):
     """{name: (return type, [parameter types])} of every function include/mxvl.h declares, each type reduced to its class:
-    "ptr" (any pointer, `T name[n]` included), "char*" (const char*), or the scalar type with int32_t read as int."""
+    "ptr" (any pointer, `T name[n]` included), "char*" (const char*), or the scalar type with int32_t read as int.
+    with_names: a third element, [parameter names]."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", "", _header(), flags=re.S)
     text = re.sub(r"typedef\s+(struct|enum)[^{;]*\{.*?\}[^;]*;", "", text, flags=re.S)
     text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)
@@ -65,8 +69,8 @@ def _prototypes():
     protos = {}
     for m in re.finditer(r"([A-Za-z_][\w\s*]*?)\b(mxvl_\w+)\s*\(([^)]*)\)\s*;", text):
         params = [p.strip() for p in m.group(3).split(",")]
-        params = [] if params == ["void"] else [re.sub(r"\b\w+\s*(\[\w*\])?$", lambda a: a.group(1) or "", p) for p in params]
-        protos[m.group(2)] = (cls(m.group(1)), [cls(p) for p in params])
+        named = [] if params == ["void"] else [re.fullmatch(r"(.*?)\b(\w+)\s*(\[\w*\])?", p).groups() for p in params]
+        protos[m.group(2)] = (cls(m.group(1)), [cls(t + (dim or "")) for t, _, dim in named]) + (([n for _, n, _ in named],) if with_names else ())
     return protos
 
 
@@ -117,6 +121,129 @@ def test_check_reports_the_hip_error_of_launch_failures_only():
     with pytest.raises(RuntimeError, match=r"^f failed: MXVL_ERR_LAUNCH \(hipError -?\d+\)$"):
         _abi.check(_abi.MXVL_ERR_LAUNCH, "f")
     _abi.check(0, "f")
+
+
+def _launching_entries():
+    """The entries that enqueue work: a prototype of include/mxvl.h whose last parameter is `void *hip_stream`."""
+    names = {n for n, (_, types, params) in _prototypes(with_names=True).items() if params[-1:] == ["hip_stream"] and types[-1] == "ptr"}
+    assert names == set(re.findall(r"\b(mxvl_\w+)\s*\([^)]*\bvoid\s*\*\s*hip_stream\s*\)\s*;", _header())) and len(names) == 43
+    return names
+
+
+def _is_call(node, dotted):
+    f = node.func if isinstance(node, ast.Call) else None
+    if "." not in dotted:
+        return isinstance(f, ast.Name) and f.id == dotted
+    mod, attr = dotted.split(".")
+    return isinstance(f, ast.Attribute) and f.attr == attr and isinstance(f.value, ast.Name) and f.value.id == mod
+
+
+def test_package_launches_through_the_one_helper():
+    """Outside _abi.py the package spells a kernel launch one way, _abi.launch(name, ...): no byref, no stream_ptr, no _abi.check
+    but the two of the host-only resample entries (they take no stream), no ctypes import.  Every name it launches is written out
+    at the call (a literal, or a conditional of two literals; selective_scan_interface._timed hands its `name` parameter on, so
+    its callers' literals count), is a key of _abi.SIGNATURES and a launching entry of the header; and no launching entry is
+    reached any other way (as an attribute of the library, or by a name string outside a launch).
+    The package launches 42 of the header's 43 launching entries: all but mxvl_gemm_nt, which only tests and dev tools drive."""
+    launching = _launching_entries()
+    launched, checks = set(), []
+    for path in sorted(glob.glob(os.path.join(ROOT, "medical_image_analysis_amd", "*.py"))):
+        mod = os.path.basename(path)
+        if mod == "_abi.py":
+            continue
+        text = open(path).read()
+        assert "byref(" not in text and "stream_ptr(" not in text, mod
+        assert not re.search(r"^\s*(import ctypes|from ctypes)\b", text, re.M), mod
+        tree = ast.parse(text)
+        name_nodes = set()
+        timed = [n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == "_timed"]
+        for call in [n for n in ast.walk(tree) if isinstance(n, ast.Call)]:
+            if _is_call(call, "_abi.check"):
+                checks.append((mod, ast.get_source_segment(text, call.args[1])))
+            if _is_call(call, "_abi.launch"):
+                arg = call.args[0]
+            elif _is_call(call, "_timed") and mod == "selective_scan_interface.py":
+                arg = call.args[1]
+            else:
+                continue
+            literals = [n for n in ast.walk(arg) if isinstance(n, ast.Constant)]
+            if isinstance(arg, ast.Name):          # only _timed may pass a name on: its own parameter, a literal at its callers
+                assert timed and call in ast.walk(timed[0]) and arg.id == timed[0].args.args[1].arg, (mod, call.lineno)
+            else:
+                assert isinstance(arg, ast.Constant) or (isinstance(arg, ast.IfExp) and len(literals) == 2), (mod, call.lineno)
+            for lit in literals:
+                assert lit.value in _abi.SIGNATURES and lit.value in launching, (mod, call.lineno, lit.value)
+                launched.add(lit.value)
+                name_nodes.add(lit)
+        for n in ast.walk(tree):
+            if isinstance(n, ast.Attribute):
+                assert n.attr not in launching, f"{mod}:{n.lineno} reaches {n.attr} without _abi.launch"
+            if isinstance(n, ast.Constant) and n.value in launching:
+                assert n in name_nodes, f"{mod}:{n.lineno} names {n.value} outside _abi.launch"
+    assert sorted(checks) == [("image_processing.py", '"mxvl_resample_coeffs"'),
+                              ("image_processing.py", 'f"mxvl_resample_ksize(in={in_size}, out={out_size}, filter={resample})"')], checks
+    assert launching - launched == {"mxvl_gemm_nt"}, launching - launched
+
+
+class _Desc(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32)]
+
+
+def test_launch_guards_the_device_passes_its_stream_and_raises_through_check(monkeypatch):
+    """_abi.launch(name, *args, device): the entry receives the args, a ctypes.Structure by reference, then the current stream of
+    `device` as its last argument, called with `device` current; a non-zero status raises what check() raises; a name the library
+    does not export raises before anything is called.  A stub library and a recording device guard: no GPU."""
+    import torch
+    events = []
+
+    class Guard:
+        def __init__(self, device):
+            self.device = device
+
+        def __enter__(self):
+            events.append(("enter", self.device))
+
+        def __exit__(self, *exc):
+            events.append(("exit", self.device))
+
+    def entry(status):
+        def fn(*args):
+            events.append(("call", args))
+            return status
+        return fn
+
+    stub = types.SimpleNamespace(mxvl_ok=entry(0), mxvl_bad_shape=entry(-3), mxvl_bad_launch=entry(_abi.MXVL_ERR_LAUNCH),
+                                 mxvl_last_hip_error=lambda: 719)
+    streams = {"cuda:0": 0x1000, "cuda:1": 0x2000}
+    monkeypatch.setattr(_abi, "_lib", stub)
+    monkeypatch.setattr(torch.cuda, "device", Guard)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=streams[device]))
+
+    assert _abi.launch("mxvl_ok", 64, None, 7, device="cuda:1") is None
+    assert events == [("enter", "cuda:1"), ("call", (64, None, 7, 0x2000)), ("exit", "cuda:1")]
+    del events[:]
+    d = _Desc(rows=5)
+    _abi.launch("mxvl_ok", d, device="cuda:0")
+    (_, dev0), (_, (ref, stream)), (_, dev1) = events
+    assert [e[0] for e in events] == ["enter", "call", "exit"] and dev0 == dev1 == "cuda:0" and stream == 0x1000
+    assert type(ref) is type(ctypes.byref(d)) and ref._obj is d          # by reference: the descriptor itself, not a copy
+
+    for name, rc in (("mxvl_bad_shape", -3), ("mxvl_bad_launch", _abi.MXVL_ERR_LAUNCH)):
+        with pytest.raises(RuntimeError) as want:
+            _abi.check(rc, name)
+        with pytest.raises(RuntimeError) as got:
+            _abi.launch(name, 1, device="cuda:0")
+        assert str(got.value) == str(want.value) and name in str(got.value)
+    assert "MXVL_ERR_SHAPE" in str(want.value) or "(hipError 719)" in str(want.value)
+
+    del events[:]
+    with pytest.raises(AttributeError):
+        _abi.launch("mxvl_no_such_entry", 1, device="cuda:0")
+    assert events == []
+    monkeypatch.setattr(_abi, "_lib", None)                              # the real library refuses an unknown name the same way
+    with pytest.raises(AttributeError):
+        _abi.launch("mxvl_no_such_entry", 1, device="cuda:0")
+    assert events == []
 
 
 def test_scan_descriptor_validation_without_gpu():
