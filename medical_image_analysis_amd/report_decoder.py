@@ -91,34 +91,43 @@ class StaticKVCache:
             self.v[i].copy_(self.v[i].index_select(0, beam_idx))
 
 
-class _SearchFusion:
-    """step_search(): decoder step + beam-search update (`_BeamState.advance`) as ONE captured hipGraph per token; the
-    host only reads the 1-byte `unfinished` flag between replays."""
-    sgraph = None
+class _Stepper:
+    """What the two steppers share: the prompt-mask reset, the one hipGraph capture site, and step_search() -- decoder step +
+    search update (`_SearchState.advance`) as ONE captured hipGraph per token; the host only reads the 1-byte `unfinished`
+    flag between replays."""
+    graph = None         # step(): the decoder step alone
+    sgraph = None        # step_search(): the decoder step + the update of search state `sstate`
     sstate = None
 
-    def _search_body(self, state):
-        if getattr(self, "fused_prologue", False):        # the kernel stepper reads the search state's tensors itself
-            state.advance(self._body(state.tok, state.beam_src, state.cur))
-            return
-        self.tok.copy_(state.tok)
-        self.beam.copy_(state.beam_src)
-        self.step_no.copy_((state.cur - 1).view(1))
-        self.pos.copy_((state.cur + (self.P - 1)).view(1))
-        state.advance(self._body())
+    def _load_prompt_mask(self, prompt_mask):
+        self.mask.zero_()
+        self.mask[:, :self.P] = prompt_mask.repeat_interleave(self.mask.shape[0] // prompt_mask.shape[0], dim=0)
+        self.n_real.copy_(self.mask[:, :self.P].sum(-1, keepdim=True))          # RoPE position of the first new token
+
+    def _replay(self, slot, body, *args):
+        """Replay the graph held in attribute `slot`.  Without one: run `body(*args)` eagerly (this is also the warm-up capture needs),
+        then record the same body once; recording executes nothing, so the state (cache, mask, search state) is advanced
+        exactly once per token.  Returns a clone of what the eager run returned (None on a replay)."""
+        graph = getattr(self, slot)
+        if graph is not None:
+            graph.replay()
+            return None
+        out = body(*args)
+        out = out if out is None else out.clone()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            body(*args)
+        setattr(self, slot, graph)
+        return out
 
     def step_search(self, state):
-        if self.sgraph is None or self.sstate is not state:
-            self._search_body(state)            # eager once: the warm-up capture needs; advances exactly one token
-            torch.cuda.synchronize()
-            self.sgraph, self.sstate = torch.cuda.CUDAGraph(), state
-            with torch.cuda.graph(self.sgraph):
-                self._search_body(state)
-            return
-        self.sgraph.replay()
+        if self.sstate is not state:
+            self.sgraph, self.sstate = None, state
+        self._replay("sgraph", self._search_body, state)
 
 
-class _GraphStepper(_SearchFusion):
+class _GraphStepper(_Stepper):
     """One decode step (beam re-order of the cache + one-token forward) captured ONCE in a hipGraph and replayed per
     token: a 32-layer decoder is ~1400 kernel launches per token in eager mode -- launch-bound at batch 1-3."""
 
@@ -126,29 +135,23 @@ class _GraphStepper(_SearchFusion):
         dev = prompt_mask.device
         cfg = model.config
         self.model = model
-        P = prompt_mask.shape[1]
-        self.P = P
-        self.max_len = P + max_new
+        self.P = prompt_mask.shape[1]
+        self.max_len = self.P + max_new
         self.cache = StaticKVCache(cfg.num_hidden_layers, rows, cfg.num_key_value_heads, self.max_len,
                                    cfg.hidden_size // cfg.num_attention_heads, dtype, dev)
-        self.cache.load_prefix(dyn_cache, rows // prompt_mask.shape[0])
         self.mask = torch.zeros(rows, self.max_len, dtype=torch.long, device=dev)
-        self.mask[:, :P] = prompt_mask.repeat_interleave(rows // prompt_mask.shape[0], dim=0)
-        self.n_real = self.mask[:, :P].sum(-1, keepdim=True)            # RoPE position of the first new token
+        self.n_real = torch.zeros(rows, 1, dtype=torch.long, device=dev)
         self.tok = torch.zeros(rows, dtype=torch.long, device=dev)
         self.beam = torch.arange(rows, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)          # cache slot of the token being fed
         self.step_no = torch.zeros(1, dtype=torch.long, device=dev)
         self.logits = None
-        self.graph = None
         self.dtype = dtype
+        self.reset(prompt_mask, dyn_cache)
 
     def reset(self, prompt_mask, dyn_cache):
-        rep = self.mask.shape[0] // prompt_mask.shape[0]
-        self.cache.load_prefix(dyn_cache, rep)
-        self.mask.zero_()
-        self.mask[:, :self.P] = prompt_mask.repeat_interleave(rep, dim=0)
-        self.n_real.copy_(self.mask[:, :self.P].sum(-1, keepdim=True))
+        self.cache.load_prefix(dyn_cache, self.mask.shape[0] // prompt_mask.shape[0])
+        self._load_prompt_mask(prompt_mask)
 
     def _body(self):
         self.cache.reorder_(self.beam)
@@ -162,41 +165,80 @@ class _GraphStepper(_SearchFusion):
                       cache_position=self.pos, position_embeddings=pos_emb)[0]
         return self.model.lm_head(self.model.model.norm(h))[:, -1]
 
+    def _step_body(self):
+        self.logits = self._body()          # (the recorded call leaves the graph's own output buffer here)
+        return self.logits
+
+    def _search_body(self, state):
+        self.tok.copy_(state.tok)
+        self.beam.copy_(state.beam_src)
+        self.step_no.copy_((state.cur - 1).view(1))
+        self.pos.copy_((state.cur + (self.P - 1)).view(1))
+        state.advance(self._body())
+
     def step(self, tok, beam_idx, k):
         """k-th new token (k >= 0): feed `tok` (rows,), re-order the cache by `beam_idx`, return next logits."""
         self.tok.copy_(tok)
         self.beam.copy_(beam_idx)
         self.pos.fill_(self.P + k)
         self.step_no.fill_(k)
-        if self.graph is None:
-            # first token: run eagerly (this is also the warm-up capture needs), then record the same body once;
-            # recording executes nothing, so the state (cache, mask) is advanced exactly once per token
-            out = self._body().clone()
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.logits = self._body()
-            return out
-        self.graph.replay()
-        return self.logits
+        out = self._replay("graph", self._step_body)
+        return self.logits if out is None else out
 
 
-class _BeamState:
-    """HF beam search (transformers generation/utils.py `_beam_search`, the vectorised form) as ONE static-shape
-    update per generated token: every tensor has a fixed shape and the step index `cur` is a device scalar, so the
-    same code runs eagerly (CPU tests, torch fallback) and inside the captured hipGraph of the decode step.
+class _SearchState:
+    """One search (beam search, sampling) as ONE static-shape update per generated token -- the protocol the steppers and the token
+    loop (`ReportDecoder._search`) drive: `advance(logits)` consumes the (rows, V) logits of step `cur` and leaves the next tokens in
+    .tok, the parent row of every live row in .beam_src and whether decoding goes on in .unfinished.  Every tensor has a fixed shape
+    and the step index `cur` is a device scalar, so the same code runs eagerly (CPU tests, torch restatement) and inside the captured
+    hipGraph of the decode step.  A subclass adds its own tensors and supplies `_hip_supported`, `_advance_hip` (its kernel),
+    `advance_torch` (the restatement the kernel is held against), `_serves` (for the error) and `result`."""
+    nb = 1           # rows per sample: the token loop expands / re-orders the cache for a search that has more
+
+    def __init__(self, rows, vocab, max_new, fill, eos, min_new, rep_pen, dev):
+        self.V, self.max_new, self.fill, self.min_new, self.rep_pen = vocab, max_new, fill, min_new, rep_pen
+        self.use_hip = True      # tests flip this to compare the HIP kernel with the torch restatement
+        self.allow_torch = False  # generate(use_graph="torch" / False) sets it: the torch restatement as an EXPLICIT request only
+        self.eos_t = torch.tensor(eos, device=dev, dtype=torch.long)
+        self.ar = torch.arange(max_new, device=dev)
+        self.cur = torch.zeros((), dtype=torch.long, device=dev)
+        self.tok = torch.zeros(rows, dtype=torch.long, device=dev)
+        self.beam_src = torch.arange(rows, device=dev)                   # identity until a search re-orders its rows
+        self.unfinished = torch.ones((), dtype=torch.bool, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # arrival word of the multi-workgroup kernels
+        self.workspace = None
+        # *unfinished of the step that ran at cur = c, at [c], where the HOST can read it (pinned, device-mapped): the look-ahead
+        # token loop polls this instead of enqueueing a device-to-host copy between two replays (a 4 us copy kernel + a 5 us gap
+        # per token in the round-4 timeline)
+        self.unf_log = torch.zeros(max_new, dtype=torch.uint8).pin_memory() if torch.device(dev).type == "cuda" else None
+
+    def reset(self):
+        self.cur.zero_()
+        self.unfinished.fill_(True)
+
+    def advance(self, logits):
+        if self.use_hip and logits.is_cuda:
+            lg = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.float().contiguous()
+            if self._hip_supported(lg):
+                return self._advance_hip(lg)
+            if not self.allow_torch:
+                # ONE search update on a HIP device, as for the decoder step: the kernel, or an error naming what it cannot serve
+                what, served = self._serves()
+                raise RuntimeError(f"{what} update on {logits.device}: {served}; pass use_graph=\"torch\" (or False) to generate() "
+                                   f"for the torch restatement")
+        return self.advance_torch(logits)
+
+
+class _BeamState(_SearchState):
+    """HF beam search (transformers generation/utils.py `_beam_search`, the vectorised form).
     Processors: RepetitionPenalty + MinNewTokensLength on the log-probabilities; criteria: MaxLength + EosToken."""
 
     def __init__(self, B, nb, vocab, max_new, fill, eos, min_new, rep_pen, len_pen, early_stopping, dev):
-        self.B, self.nb, self.V, self.max_new = B, nb, vocab, max_new
-        self.use_hip = True      # tests flip this to compare the HIP kernel with the torch restatement
-        self.allow_torch = False  # generate(use_graph="torch" / False) sets it: the torch restatement as an EXPLICIT request only
-        self.fill, self.min_new, self.rep_pen, self.early = fill, min_new, rep_pen, early_stopping
-        self.eos_t = torch.tensor(eos, device=dev, dtype=torch.long)
+        super().__init__(B * nb, vocab, max_new, fill, eos, min_new, rep_pen, dev)
+        self.B, self.nb, self.early = B, nb, early_stopping
         self.keep = max(2, 1 + len(eos)) * nb
         self.top_mask = torch.zeros(self.keep, dtype=torch.bool, device=dev)
         self.top_mask[:nb] = True
-        self.ar = torch.arange(max_new, device=dev)
         self.row0 = torch.arange(B, device=dev)[:, None] * nb
         # (cur+1)**length_penalty and the early-stop heuristic's hypothesis length, as fp32 tables indexed by cur
         steps = torch.arange(1, max_new + 1, dtype=torch.float64)
@@ -209,17 +251,7 @@ class _BeamState:
         self.fin_score = torch.empty(B, nb, device=dev)
         self.fin_done = torch.empty(B, nb, dtype=torch.bool, device=dev)
         self.heur_open = torch.empty(B, 1, dtype=torch.bool, device=dev)
-        self.cur = torch.zeros((), dtype=torch.long, device=dev)
-        self.tok = torch.zeros(B * nb, dtype=torch.long, device=dev)
-        self.beam_src = torch.zeros(B * nb, dtype=torch.long, device=dev)
-        self.unfinished = torch.ones((), dtype=torch.bool, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # arrival word of the multi-workgroup beam kernel
-        self.workspace = None
         self.split_vocab = True          # (tests switch it off to run the one-workgroup-per-sample sweeps)
-        # *unfinished of the step that ran at cur = c, at [c], where the HOST can read it (pinned, device-mapped): the look-ahead
-        # token loop polls this instead of enqueueing a device-to-host copy between two replays (a 4 us copy kernel + a 5 us gap
-        # per token in the round-4 timeline)
-        self.unf_log = torch.zeros(max_new, dtype=torch.uint8).pin_memory() if torch.device(dev).type == "cuda" else None
         self.reset()
 
     def reset(self):
@@ -230,8 +262,24 @@ class _BeamState:
         self.fin_score.fill_(-1e9)
         self.fin_done.fill_(False)
         self.heur_open.fill_(True)
-        self.cur.zero_()
-        self.unfinished.fill_(True)
+        super().reset()
+
+    def _serves(self):
+        return "beam-search", (f"csrc/beam_step.hip serves num_beams <= 8, <= 4 EOS ids and num_beams * vocab < 2^31 "
+                               f"(got num_beams={self.nb}, eos ids={self.eos_t.numel()}, vocab={self.V})")
+
+    def result(self):
+        """The best finished hypothesis of every sample, trimmed to the longest returned one (HF trims by the recorded beam indices)."""
+        out = self.fin_seq[:, 0].clone()
+        lens = []
+        for b in range(self.B):
+            n = self.max_new
+            if self.eos_t.numel():
+                e = torch.isin(out[b], self.eos_t).nonzero()
+                if len(e):
+                    n = int(e[0]) + 1
+            lens.append(n)
+        return out[:, :max(lens)]
 
     def _hip_supported(self, logits):
         """What csrc/beam_step.hip serves: beams <= 8, keep <= 16, <= 4 EOS ids, beams * vocab < 2^31 -- any vocabulary size (the
@@ -257,21 +305,6 @@ class _BeamState:
                 self.workspace = torch.empty(max(int(lib.mxvl_beam_workspace_bytes(self.B, self.nb, self.keep)), 4), dtype=torch.uint8, device=logits.device)
             d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         _abi.launch("mxvl_beam_step", d, device=logits.device)
-
-    def advance(self, logits):
-        """Consume the (B*nb, V) logits of step `cur`; leaves the next tokens in .tok, the parent beam of every live
-        beam (flat row index) in .beam_src, and whether decoding goes on in .unfinished."""
-        if self.use_hip and logits.is_cuda:
-            lg = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.float().contiguous()
-            if self._hip_supported(lg):
-                return self._advance_hip(lg)
-            if not self.allow_torch:
-                # ONE search update on a HIP device, as for the decoder step: the kernel, or an error naming what it cannot serve
-                raise RuntimeError(
-                    f"beam-search update on {logits.device}: csrc/beam_step.hip serves num_beams <= 8, <= 4 EOS ids and "
-                    f"num_beams * vocab < 2^31 (got num_beams={self.nb}, eos ids={self.eos_t.numel()}, vocab={self.V}); pass "
-                    f"use_graph=\"torch\" (or False) to generate() for the torch restatement")
-        return self.advance_torch(logits)
 
     def advance_torch(self, logits):
         B, nb, V, keep, cur = self.B, self.nb, self.V, self.keep, self.cur
@@ -354,46 +387,41 @@ def sample_uniform(seed, rows, step, device="cpu"):
     return (x >> 8).double() * 2.0 ** -24
 
 
-class _SampleState:
-    """HF `_sample` with do_sample=True (num_beams = 1) as ONE static-shape update per generated token, shaped like `_BeamState` so
-    the steppers drive either: RepetitionPenalty -> MinNewTokens -> Temperature -> TopK -> TopP on the fp32 logits (HF's order,
-    generation/utils.py `_get_logits_processor`), then an inverse-CDF draw in vocabulary order fed by `sample_uniform(seed, row, cur)`.
+class _SampleState(_SearchState):
+    """HF `_sample` with do_sample=True (num_beams = 1): RepetitionPenalty -> MinNewTokens -> Temperature -> TopK -> TopP on the fp32
+    logits (HF's order, generation/utils.py `_get_logits_processor`), then an inverse-CDF draw in vocabulary order fed by
+    `sample_uniform(seed, row, cur)`; the drawn tokens also land in .seq[:, cur].
     The seed lives in DEVICE memory and the step counter is the device scalar `cur`: a captured step replays with a fresh number per
     token and per call.  Top-p keeps token i iff the softmax mass of the strictly greater scores is < top_p: HF's rule with the ties
     at the cut kept together (HF's own outcome on ties follows an unstable sort; include/mxvl.h records the deviation)."""
 
     def __init__(self, B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev):
-        self.B, self.V, self.max_new = B, vocab, max_new
-        self.use_hip = True      # tests flip this to compare the HIP kernel with the torch restatement
-        self.allow_torch = False  # generate(use_graph="torch" / False) sets it: the torch restatement as an EXPLICIT request only
-        self.fill, self.min_new, self.rep_pen = fill, min_new, float(rep_pen)
+        super().__init__(B, vocab, max_new, fill, eos, min_new, float(rep_pen), dev)
+        self.B = B
         self.temperature, self.top_p = float(temperature), float(top_p)
         self.top_k = min(int(top_k), vocab) if top_k else 0           # 0 = off (HF: None or 0)
-        self.eos_t = torch.tensor(eos, device=dev, dtype=torch.long)
         # divisors as fp32 DEVICE scalars: torch divides by a host scalar on a HIP device as a multiplication by its reciprocal, which
         # is not the IEEE division HF's processors perform on the CPU (and csrc/sample_step.hip on the device)
         self.temp_t = torch.tensor(self.temperature, dtype=torch.float32, device=dev)
         self.pen_t = torch.tensor(self.rep_pen, dtype=torch.float32, device=dev)
-        self.ar = torch.arange(max_new, device=dev)
         self.seq = torch.empty(B, max_new, dtype=torch.long, device=dev)
         self.alive = torch.empty(B, dtype=torch.bool, device=dev)
-        self.tok = torch.zeros(B, dtype=torch.long, device=dev)
-        self.beam_src = torch.arange(B, device=dev)                    # identity: no beams to re-order
-        self.cur = torch.zeros((), dtype=torch.long, device=dev)
-        self.unfinished = torch.ones((), dtype=torch.bool, device=dev)
         self.seed = torch.zeros(1, dtype=torch.long, device=dev)        # device memory, never a kernel scalar
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)     # arrival word of the row workgroups
         self.out_thresh = torch.zeros(B, dtype=torch.float32, device=dev)   # smallest kept score / kept tokens of the last step
         self.out_kept = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.workspace = None
-        self.unf_log = torch.zeros(max_new, dtype=torch.uint8).pin_memory() if torch.device(dev).type == "cuda" else None
         self.reset()
 
     def reset(self):
         self.seq.fill_(self.fill)
         self.alive.fill_(True)
-        self.cur.zero_()
-        self.unfinished.fill_(True)
+        super().reset()
+
+    def _serves(self):
+        return "sampling", (f"csrc/sample_step.hip serves <= 80 rows, <= 4 EOS ids and rows * vocab < 2^31 "
+                            f"(got rows={self.B}, eos ids={self.eos_t.numel()}, vocab={self.V})")
+
+    def result(self):
+        return self.seq[:, :int(self.cur)].clone()
 
     def _hip_supported(self, logits):
         """What csrc/sample_step.hip serves: <= 80 rows (the kernel stepper's bound), <= 4 EOS ids, rows * vocab < 2^31."""
@@ -414,20 +442,6 @@ class _SampleState:
         d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
         d.out_thresh, d.out_kept = self.out_thresh.data_ptr(), self.out_kept.data_ptr()
         _abi.launch("mxvl_sample_step", d, device=logits.device)
-
-    def advance(self, logits):
-        """Consume the (B, V) logits of step `cur`; leaves the drawn tokens in .tok / .seq[:, cur] and whether decoding goes on in
-        .unfinished."""
-        if self.use_hip and logits.is_cuda:
-            lg = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.float().contiguous()
-            if self._hip_supported(lg):
-                return self._advance_hip(lg)
-            if not self.allow_torch:
-                raise RuntimeError(
-                    f"sampling update on {logits.device}: csrc/sample_step.hip serves <= 80 rows, <= 4 EOS ids and rows * vocab < 2^31 "
-                    f"(got rows={self.B}, eos ids={self.eos_t.numel()}, vocab={self.V}); pass use_graph=\"torch\" (or False) to "
-                    f"generate() for the torch restatement")
-        return self.advance_torch(logits)
 
     def scores_torch(self, logits):
         """Steps 1-5: the processed fp32 scores, the kept mask, the smallest kept score and the kept count of every row."""
@@ -479,7 +493,7 @@ class _SampleState:
         self.unfinished.copy_(self.alive.any() & (self.cur < self.max_new))
 
 
-class _KernelStepper(_SearchFusion):
+class _KernelStepper(_Stepper):
     """One decode step on the hand-written HIP kernels (csrc/decode.hip): per layer a fused RMSNorm+QKV GEMV, the
     RoPE/cache-append/attention kernel, o_proj GEMV (+residual), fused RMSNorm + gate/up GEMV + SwiGLU, down GEMV
     (+residual); then RMSNorm + lm_head.  161 launches per token for 32 layers, captured once in a hipGraph.
@@ -592,7 +606,6 @@ class _KernelStepper(_SearchFusion):
         with torch.no_grad():
             ct, st = model.model.rotary_emb(self.cos, torch.arange(self.max_len + 1, device=dev)[None])
         self.cos_table, self.sin_table = ct[0].float().contiguous(), st[0].float().contiguous()
-        self.graph = None
         self.reset(prompt_mask, dyn_cache)
 
     def reset(self, prompt_mask, dyn_cache):
@@ -601,9 +614,7 @@ class _KernelStepper(_SearchFusion):
             n = dyn_cache.k[i].shape[-2]
             self.kc[i][:, :, :n] = dyn_cache.k[i].repeat_interleave(rep, dim=0)
             self.vc[i][:, :, :n] = dyn_cache.v[i].repeat_interleave(rep, dim=0)
-        self.mask.zero_()
-        self.mask[:, :self.P] = prompt_mask.repeat_interleave(rep, dim=0)
-        self.n_real.copy_(self.mask[:, :self.P].sum(-1, keepdim=True))
+        self._load_prompt_mask(prompt_mask)
         self.slot.copy_(self.own.expand(-1, self.max_len))
         # the beams of a sample continue the SAME prompt: their prompt positions name one physical copy (the sample's first row), so
         # the other beams' attention reads of it are L2 hits (same head -> same XCD) instead of HBM reads of identical bytes --
@@ -691,7 +702,6 @@ class _KernelStepper(_SearchFusion):
             s //= 2
         return s
 
-    fused_prologue = True
     norm_mode = "fused"
 
     def _prologue(self, tok, beam, cur):
@@ -763,19 +773,15 @@ class _KernelStepper(_SearchFusion):
                        eps=m.model.norm.variance_epsilon, out_f32=True)
         return self.logits
 
+    def _search_body(self, state):
+        state.advance(self._body(state.tok, state.beam_src, state.cur))      # the prologue kernel reads the search state's tensors itself
+
     def step(self, tok, beam_idx, k):
         self.tok.copy_(tok)
         self.beam.copy_(beam_idx)
         self.cur.fill_(k + 1)               # the prologue kernel derives the position and the RoPE step from it
-        if self.graph is None:
-            out = self._body(self.tok, self.beam, self.cur).clone()      # eager first token = the warm-up hipGraph capture needs
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._body(self.tok, self.beam, self.cur)
-            return out
-        self.graph.replay()
-        return self.logits
+        out = self._replay("graph", self._body, self.tok, self.beam, self.cur)
+        return self.logits if out is None else out
 
 
 class _Stack(nn.Module):
@@ -932,12 +938,43 @@ class ReportDecoder(nn.Module):
             emb = self.model.embed_tokens(tok)[:, None, :].to(dtype)
             logits = self.forward(emb, attention_mask=attn, past_key_values=cache)[:, -1]
 
-    def _sample(self, logits, cache, attn, dtype, eos, fill, min_new, max_new, rep_pen, temperature, top_k, top_p, seed, stepper,
-                use_graph):
-        """num_beams = 1, do_sample=True (HF `_sample`): `_SampleState` driven by the token loop of the beam path -- decoder step +
-        sampling update in ONE hipGraph replay per token, no host round trip (`_search_lookahead`)."""
-        B, dev = logits.shape[0], logits.device
-        vocab = logits.shape[-1]
+    def _search_state(self, store, cls, *args):
+        """The search state of an argument set (the cache key), built once -- its tensors, workspace and pinned log keep their
+        addresses, so a captured step stays valid over calls -- and reset for every call."""
+        states = self.__dict__.setdefault(store, {})
+        state = states.get(args)
+        if state is None:
+            state = states[args] = cls(*args)
+        else:
+            state.reset()
+        return state
+
+    def _search(self, state, logits, cache, attn, dtype, stepper, use_graph):
+        """The token loop of every `_SearchState`: with a stepper, decoder step + search update in ONE hipGraph replay per token and
+        no host round trip (`_search_lookahead`); without one, the eager forward on the dynamic cache.  `logits` (B, V): the prefill's."""
+        nb = state.nb
+        if nb > 1:
+            logits = logits.repeat_interleave(nb, dim=0)
+        state.allow_torch = use_graph == "torch" or use_graph is False
+        state.advance(logits)                                    # step 0: the prefill logits
+        if stepper is None and nb > 1:
+            cache.expand(nb)
+            attn = attn.repeat_interleave(nb, dim=0)
+        if isinstance(stepper, _KernelStepper) and state.use_hip and state._hip_supported(stepper.logits):
+            self._search_lookahead(stepper, state)
+        while bool(state.unfinished):
+            if stepper is not None:
+                stepper.step_search(state)                       # decoder step + search update, one hipGraph replay
+                continue
+            if nb > 1:
+                cache.reorder(state.beam_src)
+            attn = torch.cat([attn, torch.ones(attn.shape[0], 1, dtype=attn.dtype, device=attn.device)], dim=1)
+            emb = self.model.embed_tokens(state.tok)[:, None, :].to(dtype)
+            state.advance(self.forward(emb, attention_mask=attn, past_key_values=cache)[:, -1])
+        return state.result()
+
+    def _sample(self, seed, state_args, *loop_args):
+        """num_beams = 1, do_sample=True (HF `_sample`): a `_SampleState` on the token loop of the beam path."""
         if seed is None:
             # a generator of the decoder's own (seeded once from torch's initial seed): a call must not shift the global CPU stream
             # that samplers and augmentation draw from
@@ -945,26 +982,9 @@ class ReportDecoder(nn.Module):
             if gen is None:
                 gen = self.__dict__["_sample_gen"] = torch.Generator().manual_seed(torch.initial_seed() & (2 ** 63 - 1))
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=gen, dtype=torch.int64))
-        skey = (B, vocab, max_new, fill, tuple(eos), min_new, rep_pen, temperature, top_k or 0, top_p, str(dev))
-        state = self.__dict__.setdefault("_sample_states", {}).get(skey)
-        if state is None:
-            state = _SampleState(B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev)
-            self._sample_states[skey] = state
-        else:
-            state.reset()
+        state = self._search_state("_sample_states", _SampleState, *state_args)
         state.seed.copy_(torch.tensor([seed & (2 ** 63 - 1)], dtype=torch.long))       # device memory: never baked into a capture
-        state.allow_torch = use_graph == "torch" or use_graph is False
-        state.advance(logits)                                    # step 0: the prefill logits
-        if isinstance(stepper, _KernelStepper) and state.use_hip and state._hip_supported(stepper.logits):
-            self._search_lookahead(stepper, state)
-        while bool(state.unfinished):
-            if stepper is not None:
-                stepper.step_search(state)                       # decoder step + sampling update, one hipGraph replay
-                continue
-            attn = torch.cat([attn, torch.ones(B, 1, dtype=attn.dtype, device=dev)], dim=1)
-            emb = self.model.embed_tokens(state.tok)[:, None, :].to(dtype)
-            state.advance(self.forward(emb, attention_mask=attn, past_key_values=cache)[:, -1])
-        return state.seq[:, :int(state.cur)].clone()
+        return self._search(state, *loop_args)
 
     @staticmethod
     def _search_lookahead(stepper, state):
@@ -1075,49 +1095,14 @@ class ReportDecoder(nn.Module):
                 self.__dict__.setdefault("_steppers", {})[key] = stepper
             else:
                 stepper.reset(attention_mask, cache)
-        if do_sample:
-            return self._sample(logits, cache, attention_mask, inputs_embeds.dtype, eos, fill, min_new_tokens, max_new_tokens,
-                                repetition_penalty, float(temperature), top_k, float(top_p), seed, stepper, use_graph)
-        if nb == 1:
+        if nb == 1 and not do_sample:
             return self._greedy(logits, cache, attention_mask, inputs_embeds.dtype, eos_t, fill, min_new_tokens,
                                 max_new_tokens, repetition_penalty, stepper)
         vocab = logits.shape[-1]
-        logits = logits.repeat_interleave(nb, dim=0)
-        skey = (B, nb, vocab, max_new_tokens, fill, tuple(eos), min_new_tokens, repetition_penalty, length_penalty,
-                early_stopping, str(dev))
-        state = self.__dict__.setdefault("_beam_states", {}).get(skey)
-        if state is None:
-            state = _BeamState(B, nb, vocab, max_new_tokens, fill, eos, min_new_tokens, repetition_penalty, length_penalty,
-                               early_stopping, dev)
-            self._beam_states[skey] = state
-        else:
-            state.reset()
-        state.allow_torch = use_graph == "torch" or use_graph is False
-        state.advance(logits)                                    # step 0: the prefill logits
-        if stepper is None:
-            cache.expand(nb)
-            attn = attention_mask.repeat_interleave(nb, dim=0)
-        if isinstance(stepper, _KernelStepper) and state.use_hip and state._hip_supported(stepper.logits):
-            self._search_lookahead(stepper, state)
-        while bool(state.unfinished):
-            if stepper is not None:
-                stepper.step_search(state)                       # decoder step + search update, one hipGraph replay
-                continue
-            cache.reorder(state.beam_src)
-            attn = torch.cat([attn, torch.ones(B * nb, 1, dtype=attn.dtype, device=dev)], dim=1)
-            emb = self.model.embed_tokens(state.tok)[:, None, :]
-            logits = self.forward(emb.to(inputs_embeds.dtype), attention_mask=attn, past_key_values=cache)[:, -1]
-            state.advance(logits)
-        fin_seq = state.fin_seq
-        out = fin_seq[:, 0].clone()
-        # trim to the longest returned hypothesis (HF trims by the recorded beam indices)
-        lens = []
-        for b in range(B):
-            row = out[b]
-            n = max_new_tokens
-            if eos:
-                e = torch.isin(row, eos_t).nonzero()
-                if len(e):
-                    n = int(e[0]) + 1
-            lens.append(n)
-        return out[:, :max(lens)]
+        loop_args = (logits, cache, attention_mask, inputs_embeds.dtype, stepper, use_graph)
+        if do_sample:
+            return self._sample(seed, (B, vocab, max_new_tokens, fill, tuple(eos), min_new_tokens, repetition_penalty, float(temperature),
+                                       top_k or 0, float(top_p), str(dev)), *loop_args)
+        state = self._search_state("_beam_states", _BeamState, B, nb, vocab, max_new_tokens, fill, tuple(eos), min_new_tokens,
+                                   repetition_penalty, length_penalty, early_stopping, str(dev))
+        return self._search(state, *loop_args)

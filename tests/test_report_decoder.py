@@ -92,6 +92,15 @@ def test_generation_with_conditioned_hybrid_layers_runs_and_depends_on_image():
     assert torch.equal(m.generate(emb, **kw), base), "clear_vis_x restores the unconditioned decoder"
 
 
+def _stepper_pair(m, emb, mask, rows, new, dtype):
+    """The kernel stepper and the torch-module stepper over the same prompt, each on a prefill cache of its own."""
+    from medical_image_analysis_amd.report_decoder import _GraphStepper, _KernelStepper, KVCache
+    c1, c2 = KVCache(), KVCache()
+    m(emb, attention_mask=mask, past_key_values=c1)
+    m(emb, attention_mask=mask, past_key_values=c2)
+    return _KernelStepper(m, rows, mask, c1, new, dtype), _GraphStepper(m, rows, mask, c2, new, dtype)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,nb,inter", [(2, 4, 11008), (6, 3, 1408), (16, 5, 704)])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
@@ -99,7 +108,7 @@ def test_hip_decode_step_matches_torch_step_at_wide_and_batched_shapes(B, nb, in
     """The kernel stepper against the torch-module stepper, teacher-forced with random beam re-ordering, where the HF goldens do not
     reach: 8 rows at the Llama-2-7B intermediate width (11008: the GEMV kernel's LDS bound refused this -- the MFMA kernels have
     none), 18 rows (K-split o_proj / down_proj folded by the norm kernel, beams attention) and 80 rows (beam 5)."""
-    from medical_image_analysis_amd.report_decoder import ReportDecoder, _GraphStepper, _KernelStepper, KVCache
+    from medical_image_analysis_amd.report_decoder import ReportDecoder, _KernelStepper
     dev = "cuda:0"
     torch.manual_seed(0)
     m = ReportDecoder(vocab_size=512, hidden_size=256, intermediate_size=inter, num_hidden_layers=2, num_attention_heads=2,
@@ -113,11 +122,7 @@ def test_hip_decode_step_matches_torch_step_at_wide_and_batched_shapes(B, nb, in
     mask[1, :3] = 0
     assert _KernelStepper.supported(m, B * nb, dtype, dev)
     with torch.no_grad():
-        c1, c2 = KVCache(), KVCache()
-        m(emb, attention_mask=mask, past_key_values=c1)
-        m(emb, attention_mask=mask, past_key_values=c2)
-        ks = _KernelStepper(m, B * nb, mask, c1, new, dtype)
-        ts = _GraphStepper(m, B * nb, mask, c2, new, dtype)
+        ks, ts = _stepper_pair(m, emb, mask, B * nb, new, dtype)
         assert ks.batched
         g = torch.Generator(device="cpu").manual_seed(1)
         for k in range(new):
@@ -136,7 +141,7 @@ def test_hip_decode_step_matches_torch_step_16bit(dtype):
     same bf16 weights, teacher-forced over several tokens with RANDOM beam re-ordering at a larger width than the HF
     goldens (which pin the kernels themselves: test_hip_decode_kernels_* below).  Both sides compute in bf16 with fp32
     accumulation; logits agree to bf16 rounding noise."""
-    from medical_image_analysis_amd.report_decoder import ReportDecoder, _GraphStepper, _KernelStepper, KVCache
+    from medical_image_analysis_amd.report_decoder import ReportDecoder, _KernelStepper
     dev = "cuda:0"
     torch.manual_seed(0)
     m = ReportDecoder(vocab_size=512, hidden_size=256, intermediate_size=704, num_hidden_layers=3, num_attention_heads=4,
@@ -150,11 +155,7 @@ def test_hip_decode_step_matches_torch_step_16bit(dtype):
     mask[1, :3] = 0
     assert _KernelStepper.supported(m, B * nb, dtype, dev)
     with torch.no_grad():
-        c1, c2 = KVCache(), KVCache()
-        m(emb, attention_mask=mask, past_key_values=c1)
-        m(emb, attention_mask=mask, past_key_values=c2)
-        ks = _KernelStepper(m, B * nb, mask, c1, new, dtype)
-        ts = _GraphStepper(m, B * nb, mask, c2, new, dtype)
+        ks, ts = _stepper_pair(m, emb, mask, B * nb, new, dtype)
         g = torch.Generator(device="cpu").manual_seed(1)
         for k in range(new):
             tok = torch.randint(3, 512, (B * nb,), generator=g).to(dev)
@@ -176,7 +177,7 @@ def test_hip_decode_step_with_image_conditioned_hybrid_layers_matches_module_pat
     the image K / V, scalar gate, added before o_proj) against the module path (the torch stepper calling the layers' forward,
     which is pinned to the reference by tests/golden/hybrid_decoder.npz), teacher-forced.  One sample carries no image
     (token_type has no 3: its context is zeroed, :693), some image tokens are masked, grouped-query heads."""
-    from medical_image_analysis_amd.report_decoder import ReportDecoder, _GraphStepper, _KernelStepper, KVCache
+    from medical_image_analysis_amd.report_decoder import ReportDecoder, _KernelStepper, KVCache
     dev = "cuda:0"
     torch.manual_seed(0)
     m = ReportDecoder(vocab_size=512, hidden_size=256, intermediate_size=704, num_hidden_layers=3, num_attention_heads=4,
@@ -207,11 +208,7 @@ def test_hip_decode_step_with_image_conditioned_hybrid_layers_matches_module_pat
         plain = _KernelStepper(m, B, mask, c0, new, dtype)
         m.condition_vis_x(vis, cmask, tt)
         assert _KernelStepper.supported(m, B, dtype, dev)
-        c1, c2 = KVCache(), KVCache()
-        m(emb, attention_mask=mask, past_key_values=c1)
-        m(emb, attention_mask=mask, past_key_values=c2)
-        ks = _KernelStepper(m, B, mask, c1, new, dtype)
-        ts = _GraphStepper(m, B, mask, c2, new, dtype)
+        ks, ts = _stepper_pair(m, emb, mask, B, new, dtype)
         assert sorted(ks.cond) == [0, 2]
         g = torch.Generator(device="cpu").manual_seed(1)
         beam = torch.arange(B, device=dev)
@@ -243,7 +240,7 @@ def test_hip_decode_conditioned_hybrid_layers_with_beams_matches_module_path(dty
     (kernel: kv_rows_div = beams; module path: the layer expands vis_x / masks with repeat_interleave, HF's beam expansion of
     per-sample inputs).  Teacher-forced with beam re-orderings that stay inside a sample, kernel stepper vs module path; then
     generate(num_beams=3) end to end on the kernel stepper."""
-    from medical_image_analysis_amd.report_decoder import ReportDecoder, _GraphStepper, _KernelStepper, KVCache
+    from medical_image_analysis_amd.report_decoder import ReportDecoder, _KernelStepper
     dev = "cuda:0"
     torch.manual_seed(1)
     m = ReportDecoder(vocab_size=512, hidden_size=256, intermediate_size=704, num_hidden_layers=3, num_attention_heads=4,
@@ -269,11 +266,7 @@ def test_hip_decode_conditioned_hybrid_layers_with_beams_matches_module_path(dty
     with torch.no_grad():
         m.condition_vis_x(vis, cmask, tt)
         assert _KernelStepper.supported(m, rows, dtype, dev)
-        c1, c2 = KVCache(), KVCache()
-        m(emb, attention_mask=mask, past_key_values=c1)
-        m(emb, attention_mask=mask, past_key_values=c2)
-        ks = _KernelStepper(m, rows, mask, c1, new, dtype)
-        ts = _GraphStepper(m, rows, mask, c2, new, dtype)
+        ks, ts = _stepper_pair(m, emb, mask, rows, new, dtype)
         g = torch.Generator(device="cpu").manual_seed(2)
         base = torch.arange(rows) // nb * nb
         for k in range(new):
