@@ -407,7 +407,10 @@ int mxvl_dir_merge(const mxvl_dir_perm_desc *desc, void *hip_stream);
 typedef struct mxvl_beam_desc {
   int32_t batch, beams, vocab, max_new, min_new, n_eos, early_stopping, keep; /* early_stopping: 1 = True, 0 = False/"never" */
   float repetition_penalty;
-  int32_t reserved0;
+  int32_t no_repeat_ngram_size;    /* 0 = off; this word was `reserved0` (always zero) until now, so size and layout are unchanged: n > 0
+                                      bans, per live beam row, every token that would repeat an n-gram of run_seq[b][beam][0:cur]
+                                      (the rule is stated at mxvl_sample_desc); the banned log-probabilities become -inf after the
+                                      repetition penalty and before the min-new-tokens mask; < 0 is MXVL_ERR_SHAPE */
   const void *logits;              /* (batch*beams, vocab) */
   void *run_seq, *fin_seq;         /* (batch, beams, max_new) */
   void *run_score, *fin_score;     /* (batch, beams) */
@@ -434,8 +437,8 @@ int64_t mxvl_beam_workspace_bytes(int batch, int beams, int keep);
  * between two decoder steps (transformers generation/utils.py `_sample`; the reference passes do_sample=self.hparams.do_sample and
  * temperature=self.hparams.temperature at EMRRG/models/MambaXrayVL_DownStream.py:440-449, 537-546 and
  * R2GenKG/models/R2GenKG.py:392-401, 480-489).  On the fp32 logits of step *cur, in HF's processor order:
- *   repetition penalty over seq[:, :cur] (g < 0 ? g * pen : g / pen) -> EOS ids to -inf while *cur < min_new -> / temperature (an
- *   IEEE fp32 division) -> top-k (scores below the k-th largest removed, ties with it kept; 0 = off) -> top-p (below) -> the draw:
+ *   repetition penalty over seq[:, :cur] (g < 0 ? g * pen : g / pen) -> no-repeat-n-gram ban (below) -> EOS ids to -inf while
+ *   *cur < min_new -> / temperature (an IEEE fp32 division) -> top-k (scores below the k-th largest removed, ties with it kept; 0 = off) -> top-p (below) -> the draw:
  *   u = (sample_hash(seed, row, *cur) >> 8) * 2^-24 (report_decoder.sample_uniform restates it), token = the first index in
  *   VOCABULARY order whose inclusive cumulative kept mass exceeds u * (kept mass).
  * Rows that are no longer alive emit `fill`; seq[row][*cur] = tok; alive &= tok not in eos; *cur += 1;
@@ -447,13 +450,17 @@ int64_t mxvl_beam_workspace_bytes(int batch, int beams, int keep);
  * < top_p.  That is HF's rule (ascending sort, cumulative mass <= 1 - top_p removed, at least one token kept) wherever the scores at
  * the cut are distinct; scores TIED at the cut are kept together here, where HF keeps those of them an unstable torch.sort happens
  * to place last.  The kept set never depends on the index order of equal scores.
- * Shapes: 1 <= rows <= 80, n_eos <= 4, rows * vocab < 2^31, temperature > 0 and finite, 0 < top_p <= 1, top_k >= 0 (MXVL_ERR_SHAPE
- * otherwise, decided before any launch).  Dtypes: logits fp32 (rows, vocab) dense; seq (rows, max_new), tok (rows), cur, eos, seed
+ * No-repeat-n-gram ban (HF NoRepeatNGramLogitsProcessor; n = no_repeat_ngram_size > 0, h = the row's generated tokens, here
+ * seq[row][0:cur], in mxvl_beam_desc run_seq[b][beam][0:cur]): nothing is banned while cur + 1 < n; otherwise token w is banned iff
+ * some i <= cur - n has h[i : i+n-1] == h[cur-n+1 : cur] and h[i+n-1] == w (n == 1: every token generated so far).  A banned score
+ * is -inf, whatever the repetition penalty made of it.
+ * Shapes: 1 <= rows <= 80, n_eos <= 4, rows * vocab < 2^31, temperature > 0 and finite, 0 < top_p <= 1, top_k >= 0,
+ * no_repeat_ngram_size >= 0 (MXVL_ERR_SHAPE otherwise, decided before any launch).  Dtypes: logits fp32 (rows, vocab) dense; seq (rows, max_new), tok (rows), cur, eos, seed
  * int64; alive (rows), unfinished 1-byte booleans. */
 typedef struct mxvl_sample_desc {
   int32_t rows, vocab, max_new, min_new, n_eos, top_k;
   float repetition_penalty, temperature, top_p;
-  int32_t reserved0;
+  int32_t no_repeat_ngram_size;    /* 0 = off; this word was `reserved0` (always zero) until now: size and layout are unchanged */
   int64_t fill;                    /* token of the rows that have stopped (pad, else the first EOS) */
   const void *logits;
   void *seq, *alive, *tok, *cur;

@@ -244,7 +244,7 @@ class BeamDesc(ctypes.Structure):
     _fields_ = [
         ("batch", c_int32), ("beams", c_int32), ("vocab", c_int32), ("max_new", c_int32), ("min_new", c_int32), ("n_eos", c_int32),
         ("early_stopping", c_int32), ("keep", c_int32),
-        ("repetition_penalty", ctypes.c_float), ("reserved0", c_int32),
+        ("repetition_penalty", ctypes.c_float), ("no_repeat_ngram_size", c_int32),
         ("logits", c_void_p), ("run_seq", c_void_p), ("fin_seq", c_void_p), ("run_score", c_void_p), ("fin_score", c_void_p),
         ("fin_done", c_void_p), ("heur_open", c_void_p), ("cur", c_void_p), ("eos", c_void_p), ("len_tab", c_void_p),
         ("hyp_tab", c_void_p), ("tok", c_void_p), ("beam_src", c_void_p), ("unfinished", c_void_p), ("scratch", c_void_p),
@@ -255,7 +255,8 @@ class BeamDesc(ctypes.Structure):
 class SampleDesc(ctypes.Structure):
     _fields_ = [
         ("rows", c_int32), ("vocab", c_int32), ("max_new", c_int32), ("min_new", c_int32), ("n_eos", c_int32), ("top_k", c_int32),
-        ("repetition_penalty", ctypes.c_float), ("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("reserved0", c_int32),
+        ("repetition_penalty", ctypes.c_float), ("temperature", ctypes.c_float), ("top_p", ctypes.c_float),
+        ("no_repeat_ngram_size", c_int32),
         ("fill", c_int64),
         ("logits", c_void_p), ("seq", c_void_p), ("alive", c_void_p), ("tok", c_void_p), ("cur", c_void_p), ("eos", c_void_p),
         ("seed", c_void_p), ("unfinished", c_void_p), ("unfinished_log", c_void_p), ("scratch", c_void_p),

@@ -15,6 +15,9 @@
 // independent loads in flight per thread: a single workgroup is latency-, not bandwidth-limited on 384 KB of logits), (2) every
 // thread keeps the `keep` best penalised candidates of its strided share, history membership through an LDS bitmap,
 // (3) `keep` rounds of a block arg-max merge them, (4) a few lanes do the bookkeeping on the `keep` survivors.
+// no_repeat_ngram_size = n > 0 (HF NoRepeatNGramLogitsProcessor, include/mxvl.h): every window of a row's history that equals its last
+// n - 1 tokens bans the token that followed it -- a list of at most max_new followers per row in LDS (ban_followers), turned into a
+// second bitmap of the tile next to the penalty's (mark_ban); a banned candidate is -inf after the penalty, the way a masked EOS is.
 #include <math.h>
 #include <stdlib.h>
 
@@ -27,6 +30,7 @@ constexpr int kMaxKeep = 16, kMaxBeams = 8, kMaxEos = 4, kMaxSurv = 256;
 
 struct BeamArgs {
   int batch, nb, V, max_new, min_new, n_eos, early, keep, ablate;   // early: 1 = early_stopping True
+  int ngram;                           // no_repeat_ngram_size, 0 = off
   int vec4;                            // V % 4 == 0 and 16-byte aligned logits: a thread's words come four at a time
   float rep_pen;
   const float* logits;                 // (batch*nb, V)
@@ -49,6 +53,31 @@ struct BeamArgs {
 };
 
 __device__ inline bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// ban[r * max_new + i] = the token that followed window i of row r's history h = hist[r * max_new + (0 .. cur)) if that window equals
+// the last n - 1 tokens (i <= cur - n, so the follower is a generated token), else -1.  Called with cur >= n > 0 by every thread.
+__device__ inline void ban_followers(const long long* hist, int* ban, int nb, int max_new, int cur, int n, int V, int threads) {
+  for (int k = threadIdx.x; k < nb * max_new; k += threads) {
+    const int r = k / max_new, i = k - r * max_new;
+    int w = -1;
+    if (i <= cur - n) {
+      const long long* h = hist + r * max_new;
+      bool same = true;
+      for (int j = 0; j < n - 1 && same; ++j) same = h[i + j] == h[cur - n + 1 + j];
+      const long long f = h[i + n - 1];
+      if (same && f >= 0 && f < V) w = (int)f;
+    }
+    ban[k] = w;
+  }
+}
+
+// the banned tokens of [t0, t0 + tile) below vend into the (zeroed) [nb][words] bitmap
+__device__ inline void mark_ban(const int* ban, unsigned int* banmap, int nb, int max_new, int words, int t0, int tile, int vend, int threads) {
+  for (int k = threadIdx.x; k < nb * max_new; k += threads) {
+    const int w = ban[k], v = w - t0;
+    if (w >= t0 && v < tile && w < vend) atomicOr(&banmap[(k / max_new) * words + (v >> 5)], 1u << (v & 31));
+  }
+}
 
 // ---- the vocabulary over workgroups (round 4) ---------------------------------------------------------------------------------------
 // One workgroup per sample reads its nb x V logits twice (statistics, candidates) through ONE CU: 384 KB at the 30-40 GB/s a CU
@@ -99,8 +128,10 @@ __global__ __launch_bounds__(kSliceThreads) void beam_stats_kernel(const BeamArg
   }
 }
 
+template <bool kBan>      // kBan: the n-gram ban is compiled in (no_repeat_ngram_size > 0); without it the kernel is what it was
 __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned int cand_smem[];      // [nb][words of the slice] history membership
+  // [nb][words of the slice] history membership; with an n-gram ban: + [nb][words] banned tokens + [nb][max_new] banned followers
+  extern __shared__ __attribute__((aligned(16))) unsigned int cand_smem[];
   __shared__ float s_red[kCandWaves];
   __shared__ int s_redi[kCandWaves];
   __shared__ float s_rowmax[kMaxBeams], s_logz[kMaxBeams], s_rscore[kMaxBeams];
@@ -117,6 +148,10 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
   const int words = (tile + 31) / 32;
   const int cur = (int)*p.cur;
   unsigned int* bitmap = cand_smem;
+  unsigned int* banmap = bitmap + nb * words;
+  int* ban = (int*)(banmap + nb * words);
+  const bool ban_on = kBan && p.ngram > 0 && cur >= p.ngram && cur < max_new;      // no window start i <= cur - n before that
+  if (ban_on) ban_followers(p.run_seq + (size_t)b * nb * max_new, ban, nb, max_new, cur, p.ngram, V, kCandThreads);
   int eos32[kMaxEos];
 #pragma unroll
   for (int e = 0; e < kMaxEos; ++e) eos32[e] = e < p.n_eos ? (int)p.eos[e] : -1;
@@ -136,8 +171,9 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
   // bitmap of the history tokens that fall into [t0, t0 + tile) (workgroup-uniform call: it synchronises)
   auto build_bitmap = [&](int t0) {
     __syncthreads();
-    for (int i = tid; i < nb * words; i += kCandThreads) bitmap[i] = 0u;
+    for (int i = tid; i < nb * words * (ban_on ? 2 : 1); i += kCandThreads) bitmap[i] = 0u;      // (banmap follows bitmap)
     __syncthreads();
+    if (ban_on) mark_ban(ban, banmap, nb, max_new, words, t0, tile, v1, kCandThreads);
     if (p.rep_pen != 1.0f && cur > 0) {
       const long long* rs = p.run_seq + (size_t)b * nb * max_new;
       for (int i = tid; i < nb * cur; i += kCandThreads) {
@@ -154,6 +190,7 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
     float x = (raw - s_rowmax[r]) - s_logz[r];                              // log_softmax
     const bool hit = (bitmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u;
     if (__any(hit)) x = hit ? (x < 0.0f ? x * p.rep_pen : x / p.rep_pen) : x;
+    if (ban_on && ((banmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u)) x = -INFINITY;
     if (mask_eos) {
 #pragma unroll
       for (int e = 0; e < kMaxEos; ++e)
@@ -261,7 +298,7 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
 
 // kBeamThreads x U logits of a row are in flight per trip: 1024 x 32 covers a 32 000-word vocabulary row in ONE round trip (the
 // 512 x 16 shape of round 3 walked a row in four dependent trips, twice -- statistics and candidates -- for every beam row).
-template <int kBeamThreads, int U>
+template <int kBeamThreads, int U, bool kBan>      // kBan: as beam_cand_kernel (never with the merged candidates)
 __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs p) {
   constexpr int kBeamWaves = kBeamThreads / 64;
   extern __shared__ __attribute__((aligned(16))) unsigned int smem_u[];
@@ -287,10 +324,14 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
   constexpr int TILE = kBeamThreads * U;                           // one trip of the sweeps = one bitmap tile
   const bool merged = p.ws_cand_v != nullptr;                      // the sweeps were done by beam_stats_kernel / beam_cand_kernel
   const int words = merged ? 0 : ((V < TILE ? V : TILE) + 31) / 32;
-  unsigned int* bitmap = smem_u;                                   // [nb][words] history membership of the tile being swept
-  long long* old_run = (long long*)(smem_u + ((nb * words + 1) & ~1));   // [nb][max_new]
-  long long* old_fin = old_run + nb * max_new;                     // [nb][max_new]
   const int cur = (int)*p.cur;
+  const bool ban_lds = kBan && !merged && p.ngram > 0;                     // the launch reserved the ban bitmap and the follower list
+  const bool ban_on = ban_lds && cur >= p.ngram && cur < max_new;  // no window start i <= cur - n before that
+  unsigned int* bitmap = smem_u;                                   // [nb][words] history membership of the tile being swept
+  unsigned int* banmap = bitmap + nb * words;                      // [nb][words] tokens the n-gram rule bans (ban_lds)
+  long long* old_run = (long long*)(smem_u + ((nb * words * (ban_lds ? 2 : 1) + 1) & ~1));   // [nb][max_new]
+  long long* old_fin = old_run + nb * max_new;                     // [nb][max_new]
+  int* ban = (int*)(old_fin + nb * max_new);                       // [nb][max_new] banned followers (ban_lds)
   // a search that has already stopped stays stopped: the stepper enqueues token k + 1 before the host has read token k's flag
   // (report_decoder._search_lookahead), and that speculative launch must leave the state as the last real one left it
   if (*p.unfinished == 0) return;
@@ -318,11 +359,13 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
     }
     for (int i = tid; i < nb * max_new; i += kBeamThreads) { old_run[i] = rs[i]; old_fin[i] = fs[i]; }
     __syncthreads();
+    if (ban_on) ban_followers(old_run, ban, nb, max_new, cur, p.ngram, V, kBeamThreads);      // (build_bitmap synchronises)
     // bitmap of the history tokens in [t0, t0 + TILE) (workgroup-uniform call: it synchronises)
     auto build_bitmap = [&](int t0) {
       __syncthreads();
-      for (int i = tid; i < nb * words; i += kBeamThreads) bitmap[i] = 0u;
+      for (int i = tid; i < nb * words * (ban_on ? 2 : 1); i += kBeamThreads) bitmap[i] = 0u;      // (banmap follows bitmap)
       __syncthreads();
+      if (ban_on) mark_ban(ban, banmap, nb, max_new, words, t0, TILE, V, kBeamThreads);
       if (p.rep_pen != 1.0f && cur > 0)
         for (int i = tid; i < nb * cur; i += kBeamThreads) {
           const int r = i / cur, t = i - r * cur;
@@ -403,6 +446,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
       // (the penalty behind a wave-uniform test: as a select, hipcc ran the fp32 division sequence for every word of the vocabulary)
       const bool hit = (bitmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u;
       if (__any(hit)) x = hit ? (x < 0.0f ? x * p.rep_pen : x / p.rep_pen) : x;
+      if (ban_on && ((banmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u)) x = -INFINITY;
       if (mask_eos) {
 #pragma unroll
         for (int e = 0; e < kMaxEos; ++e)
@@ -651,12 +695,12 @@ extern "C" int mxvl_beam_step(const mxvl_beam_desc* d, void* hip_stream) {
       !d->cur || !d->len_tab || !d->hyp_tab || !d->tok || !d->beam_src || !d->unfinished)
     return MXVL_ERR_NULL;
   if (d->n_eos > 0 && !d->eos) return MXVL_ERR_NULL;
-  if (d->batch <= 0 || d->beams <= 0 || d->vocab <= 0 || d->max_new <= 0) return MXVL_ERR_SHAPE;
+  if (d->batch <= 0 || d->beams <= 0 || d->vocab <= 0 || d->max_new <= 0 || d->no_repeat_ngram_size < 0) return MXVL_ERR_SHAPE;
   if (d->n_eos > kMaxEos || d->beams > kMaxBeams || d->keep > kMaxKeep || d->keep < d->beams || (long long)d->beams * d->vocab > 0x7fffffffLL)
     return MXVL_ERR_UNSUPPORTED;
   BeamArgs a;
   a.batch = d->batch; a.nb = d->beams; a.V = d->vocab; a.max_new = d->max_new; a.min_new = d->min_new; a.n_eos = d->n_eos;
-  a.early = d->early_stopping; a.keep = d->keep; a.rep_pen = d->repetition_penalty;
+  a.early = d->early_stopping; a.keep = d->keep; a.rep_pen = d->repetition_penalty; a.ngram = d->no_repeat_ngram_size;
   a.ablate = MXVL_ABL_ENV("MXVL_BEAM_ABLATE");
   a.logits = (const float*)d->logits; a.run_seq = (long long*)d->run_seq; a.fin_seq = (long long*)d->fin_seq;
   a.run_score = (float*)d->run_score; a.fin_score = (float*)d->fin_score; a.fin_done = (unsigned char*)d->fin_done;
@@ -675,15 +719,21 @@ extern "C" int mxvl_beam_step(const mxvl_beam_desc* d, void* hip_stream) {
     a.ws_cand_v = a.ws_stats + (size_t)d->batch * d->beams * a.S * 2;
     a.ws_cand_i = (int*)(a.ws_cand_v + (size_t)d->batch * a.S * d->keep);
     hipLaunchKernelGGL(beam_stats_kernel, dim3(a.S, d->batch * d->beams), dim3(kSliceThreads), 0, (hipStream_t)hip_stream, a);
-    const size_t lds_c = 4 * (size_t)a.nb * (((a.VS < kCandTile ? a.VS : kCandTile) + 31) / 32);     // <= 8 KB at 8 beams
-    hipLaunchKernelGGL(beam_cand_kernel, dim3(a.S, d->batch), dim3(kCandThreads), lds_c, (hipStream_t)hip_stream, a);
+    size_t lds_c = 4 * (size_t)a.nb * (((a.VS < kCandTile ? a.VS : kCandTile) + 31) / 32);           // <= 8 KB at 8 beams
+    if (a.ngram > 0) lds_c = 2 * lds_c + 4 * (size_t)a.nb * a.max_new;                                // + ban bitmap + banned followers
+    if (lds_c > 56 * 1024) return MXVL_ERR_UNSUPPORTED;                                                // (max_new in the thousands)
+    if (a.ngram > 0 && lds_c > 40 * 1024 && hip_status(hipFuncSetAttribute((const void*)beam_cand_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c)) != MXVL_OK)
+      return MXVL_ERR_LAUNCH;
+    const auto cand = a.ngram > 0 ? beam_cand_kernel<true> : beam_cand_kernel<false>;
+    hipLaunchKernelGGL(cand, dim3(a.S, d->batch), dim3(kCandThreads), lds_c, (hipStream_t)hip_stream, a);
   }
   static const int shape = MXVL_ABL_ENV("MXVL_BEAM_SHAPE");      // measurement build: 1 = the 512 x 16 shape
   // LDS: the copies of the old sequences (16 bytes x beams x max_new) + the history bitmap of ONE sweep tile (threads x U words of the
   // vocabulary; none when the sweeps were done by the slice kernels) -- independent of the vocabulary size
   auto launch = [&](auto kern, int threads, int tile) -> int {
     const size_t words = a.ws_cand_v ? 0 : (size_t)((a.V < tile ? a.V : tile) + 31) / 32;
-    const size_t lds = 4 * ((a.nb * words + 1) & ~(size_t)1) + 8 * (size_t)2 * a.nb * a.max_new;
+    const bool ban_lds = words && a.ngram > 0;                    // + the ban bitmap of the tile + the banned followers
+    const size_t lds = 4 * ((a.nb * words * (ban_lds ? 2 : 1) + 1) & ~(size_t)1) + 8 * (size_t)2 * a.nb * a.max_new + (ban_lds ? 4 * (size_t)a.nb * a.max_new : 0);
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;          // max_new in the thousands
     if (lds > 48 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
       return MXVL_ERR_LAUNCH;
@@ -691,8 +741,9 @@ extern "C" int mxvl_beam_step(const mxvl_beam_desc* d, void* hip_stream) {
     return launch_status();
   };
   if (a.ws_cand_v && a.S * a.keep <= 256)       // merge + bookkeeping only: four waves (barriers and the serial lane are all that is left)
-    return launch(beam_step_kernel<256, 8>, 256, 256 * 8);
+    return launch(beam_step_kernel<256, 8, false>, 256, 256 * 8);
+  const bool ban = a.ngram > 0 && !a.ws_cand_v;               // the merge-only kernel sees candidates that are already banned
   if (MXVL_ABL(shape == 1) || (a.ws_cand_v && a.S * a.keep <= 512))
-    return launch(beam_step_kernel<512, 16>, 512, 512 * 16);
-  return launch(beam_step_kernel<1024, 32>, 1024, 1024 * 32);
+    return ban ? launch(beam_step_kernel<512, 16, true>, 512, 512 * 16) : launch(beam_step_kernel<512, 16, false>, 512, 512 * 16);
+  return ban ? launch(beam_step_kernel<1024, 32, true>, 1024, 1024 * 32) : launch(beam_step_kernel<1024, 32, false>, 1024, 1024 * 32);
 }

@@ -8,8 +8,9 @@
 //
 // One workgroup (1024 threads) per row; the rows meet in ONE returning atomicAdd on the arrival word (as beam_step.hip does).
 // Per row, every pass is a sweep of the row with 8 independent 16-byte loads in flight per lane:
-//   A   logits -> processed scores in the workspace (temperature; then the <= max_new penalised history entries and the EOS ids are
-//       patched in place: the patches are idempotent, so duplicates in the history write the same value)
+//   A   logits -> processed scores in the workspace (temperature; then the <= max_new penalised history entries, the <= max_new
+//       followers the no-repeat-n-gram rule bans (-inf, after the penalty: a ban wins) and the EOS ids are patched in place: the
+//       patches are idempotent, so duplicates in the history write the same value)
 //   1   row max + the first radix level of the top-k selection
 //   2,3 the other two levels: the k-th largest score EXACTLY (the smallest key t with count{key > t} < k), no sort
 //   4-6 the same three-level descent with a MASS per bucket instead of a count: the smallest key t with mass{key > t} < top_p * Z
@@ -28,7 +29,7 @@ constexpr int kBins = 2048;                      // radix digits: 11 + 11 + 10 b
 typedef unsigned long long u64;
 
 struct SampleArgs {
-  int rows, V, max_new, min_new, n_eos, top_k, vec4;
+  int rows, V, max_new, min_new, n_eos, top_k, vec4, ngram;
   float rep_pen, temperature, top_p, mass_scale;  // mass_scale = 2^qbits
   long long fill;
   const float* logits;
@@ -164,8 +165,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_step_kernel(SampleArgs p)
       }
     }
     __syncthreads();
+    const long long* hist_tok = p.seq + (size_t)row * p.max_new;
     if (p.rep_pen != 1.0f) {
-      const long long* hist_tok = p.seq + (size_t)row * p.max_new;
       for (int t = tid; t < cur; t += kSampThreads) {
         const long long ix = hist_tok[t];
         if (ix < 0 || ix >= V) continue;          // a fill token outside the vocabulary has no logit to penalise
@@ -173,6 +174,17 @@ __global__ __launch_bounds__(kSampThreads) void sample_step_kernel(SampleArgs p)
         g = g < 0.f ? g * p.rep_pen : g / p.rep_pen;
         if (div) g /= T;
         sc[ix] = g == 0.f ? 0.f : g;
+      }
+      __syncthreads();
+    }
+    // NoRepeatNGram: every earlier window that equals the last n - 1 tokens bans the token that followed it (include/mxvl.h)
+    const int n = p.ngram;
+    if (n > 0 && cur >= n) {                      // cur < n: no window start i <= cur - n (covers HF's cur + 1 < n and cur + 1 == n)
+      for (int i = tid; i <= cur - n; i += kSampThreads) {
+        bool same = true;
+        for (int j = 0; j < n - 1 && same; ++j) same = hist_tok[i + j] == hist_tok[cur - n + 1 + j];
+        const long long w = hist_tok[i + n - 1];
+        if (same && w >= 0 && w < V) sc[w] = -__builtin_inff();
       }
       __syncthreads();
     }
@@ -418,7 +430,7 @@ extern "C" int64_t mxvl_sample_workspace_bytes(int rows, int vocab) {
 extern "C" int mxvl_sample_step(const mxvl_sample_desc* d, void* hip_stream) {
   if (!d) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->rows > kSampMaxRows || d->vocab <= 0 || d->max_new <= 0 || d->min_new < 0 || d->n_eos < 0 || d->n_eos > kSampMaxEos ||
-      d->top_k < 0 || (long long)d->rows * d->vocab > 0x7fffffffLL)
+      d->top_k < 0 || d->no_repeat_ngram_size < 0 || (long long)d->rows * d->vocab > 0x7fffffffLL)
     return MXVL_ERR_SHAPE;
   if (!(d->temperature > 0.f) || !(d->temperature < __builtin_inff()) || !(d->top_p > 0.f) || !(d->top_p <= 1.f) ||
       !(d->repetition_penalty > 0.f))
@@ -429,6 +441,7 @@ extern "C" int mxvl_sample_step(const mxvl_sample_desc* d, void* hip_stream) {
   if (d->n_eos > 0 && !d->eos) return MXVL_ERR_NULL;
   SampleArgs a;
   a.rows = d->rows; a.V = d->vocab; a.max_new = d->max_new; a.min_new = d->min_new; a.n_eos = d->n_eos; a.top_k = d->top_k;
+  a.ngram = d->no_repeat_ngram_size;
   a.rep_pen = d->repetition_penalty; a.temperature = d->temperature; a.top_p = d->top_p; a.fill = d->fill;
   // mass unit 2^-qbits: the sum of `vocab` masses <= 1 stays below 2^62
   int lg = 0;

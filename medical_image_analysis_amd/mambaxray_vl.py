@@ -219,6 +219,9 @@ class MambaXrayVLDownStream(nn.Module):
     def generate(self, samples):
         prefix, atts = self._prefix(samples)
         a = self.args
+        # args.no_repeat_ngram_size is NOT forwarded: the reference declares the flag (configs/config.py, default 2) but never hands it
+        # to HF generate (EMRRG/models/MambaXrayVL_DownStream.py:440-449), so its default would change every report against the
+        # reference.  The ban is reached through ReportDecoder.generate(no_repeat_ngram_size=n)
         return self.llama_model.generate(
             prefix.to(self.embed_tokens.weight.dtype), attention_mask=atts, num_beams=_get(a, "beam_size", 3),
             do_sample=_get(a, "do_sample", False), min_new_tokens=_get(a, "min_new_tokens", 80),

@@ -186,6 +186,27 @@ class _GraphStepper(_Stepper):
         return self.logits if out is None else out
 
 
+def ngram_banned(hist, cur, n, vocab):
+    """HF NoRepeatNGramLogitsProcessor as a static-shape mask.  hist (rows, L): the generated tokens of every row, [:, :cur] written;
+    cur: the step index (0-dim int64 tensor); n = no_repeat_ngram_size > 0.  Returns (rows, vocab) bool: token w of a row is banned iff
+    some window start i <= cur - n has hist[i : i+n-1] == hist[cur-n+1 : cur] and hist[i+n-1] == w -- nothing while cur + 1 < n (and
+    nothing at cur + 1 == n: no window start exists yet); n == 1 bans every generated token.  One comparison per window position and
+    per token of the n - 1 wide suffix, all rows at once: no host read of `cur`, so it runs inside a captured step."""
+    rows, L = hist.shape
+    W = L - n + 1                                                               # window starts that fit into the row
+    banned = torch.zeros(rows, vocab + 1, dtype=torch.bool, device=hist.device)  # column `vocab` collects what is not banned
+    if W <= 0:
+        return banned[:, :vocab]
+    ok = (torch.arange(W, device=hist.device) <= cur - n)[None, :].expand(rows, W)
+    for j in range(n - 1):                                                      # token j of the window == token j of the current suffix
+        suffix = hist.index_select(1, (cur - n + 1 + j).clamp(min=0).view(1))
+        ok = ok & (hist[:, j:j + W] == suffix)
+    follower = hist[:, n - 1:n - 1 + W]
+    ok = ok & (follower >= 0) & (follower < vocab)                              # (a fill id outside the vocabulary has no score)
+    banned.scatter_(1, torch.where(ok, follower, torch.full_like(follower, vocab)), True)
+    return banned[:, :vocab]
+
+
 class _SearchState:
     """One search (beam search, sampling) as ONE static-shape update per generated token -- the protocol the steppers and the token
     loop (`ReportDecoder._search`) drive: `advance(logits)` consumes the (rows, V) logits of step `cur` and leaves the next tokens in
@@ -195,8 +216,9 @@ class _SearchState:
     `advance_torch` (the restatement the kernel is held against), `_serves` (for the error) and `result`."""
     nb = 1           # rows per sample: the token loop expands / re-orders the cache for a search that has more
 
-    def __init__(self, rows, vocab, max_new, fill, eos, min_new, rep_pen, dev):
+    def __init__(self, rows, vocab, max_new, fill, eos, min_new, rep_pen, dev, no_repeat_ngram_size=0):
         self.V, self.max_new, self.fill, self.min_new, self.rep_pen = vocab, max_new, fill, min_new, rep_pen
+        self.no_repeat = int(no_repeat_ngram_size)          # NoRepeatNGramLogitsProcessor, 0 = off
         self.use_hip = True      # tests flip this to compare the HIP kernel with the torch restatement
         self.allow_torch = False  # generate(use_graph="torch" / False) sets it: the torch restatement as an EXPLICIT request only
         self.eos_t = torch.tensor(eos, device=dev, dtype=torch.long)
@@ -231,10 +253,10 @@ class _SearchState:
 
 class _BeamState(_SearchState):
     """HF beam search (transformers generation/utils.py `_beam_search`, the vectorised form).
-    Processors: RepetitionPenalty + MinNewTokensLength on the log-probabilities; criteria: MaxLength + EosToken."""
+    Processors: RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength on the log-probabilities; criteria: MaxLength + EosToken."""
 
-    def __init__(self, B, nb, vocab, max_new, fill, eos, min_new, rep_pen, len_pen, early_stopping, dev):
-        super().__init__(B * nb, vocab, max_new, fill, eos, min_new, rep_pen, dev)
+    def __init__(self, B, nb, vocab, max_new, fill, eos, min_new, rep_pen, len_pen, early_stopping, dev, no_repeat_ngram_size=0):
+        super().__init__(B * nb, vocab, max_new, fill, eos, min_new, rep_pen, dev, no_repeat_ngram_size)
         self.B, self.nb, self.early = B, nb, early_stopping
         self.keep = max(2, 1 + len(eos)) * nb
         self.top_mask = torch.zeros(self.keep, dtype=torch.bool, device=dev)
@@ -284,8 +306,10 @@ class _BeamState(_SearchState):
     def _hip_supported(self, logits):
         """What csrc/beam_step.hip serves: beams <= 8, keep <= 16, <= 4 EOS ids, beams * vocab < 2^31 -- any vocabulary size (the
         history bitmap is tiled since round 5: Qwen1.5's 151 936 tokens at beam 5 take the same kernels as Llama's 32 000)."""
+        # LDS of the one-workgroup kernel: the old sequences; with an n-gram ban also its bitmap of a 32 768-word tile and the followers
+        ban_lds = (4 * self.nb * ((min(self.V, 32768) + 31) // 32) + 4 * self.nb * self.max_new) if self.no_repeat else 0
         return (logits.is_cuda and self.nb <= 8 and self.keep <= 16 and self.eos_t.numel() <= 4 and self.nb * self.V < 2 ** 31
-                and 16 * self.nb * self.max_new <= 128 * 1024 and logits.dtype == torch.float32 and logits.is_contiguous())
+                and 16 * self.nb * self.max_new + ban_lds <= 128 * 1024 and logits.dtype == torch.float32 and logits.is_contiguous())
 
     def _advance_hip(self, logits):
         """csrc/beam_step.hip: the whole update below as one kernel (capturable in the decode step's hipGraph)."""
@@ -293,6 +317,7 @@ class _BeamState(_SearchState):
         d = _abi.BeamDesc()
         d.batch, d.beams, d.vocab, d.max_new, d.min_new = self.B, self.nb, self.V, self.max_new, self.min_new
         d.n_eos, d.early_stopping, d.keep, d.repetition_penalty = self.eos_t.numel(), int(self.early is True), self.keep, self.rep_pen
+        d.no_repeat_ngram_size = self.no_repeat
         d.logits, d.run_seq, d.fin_seq = logits.data_ptr(), self.run_seq.data_ptr(), self.fin_seq.data_ptr()
         d.run_score, d.fin_score, d.fin_done = self.run_score.data_ptr(), self.fin_score.data_ptr(), self.fin_done.data_ptr()
         d.heur_open, d.cur, d.eos = self.heur_open.data_ptr(), self.cur.data_ptr(), _abi.ptr(self.eos_t if self.eos_t.numel() else None)
@@ -316,6 +341,8 @@ class _BeamState(_SearchState):
             sc = torch.gather(logp, 1, idx)
             pen = torch.where(sc < 0, sc * self.rep_pen, sc / self.rep_pen)
             logp = logp.scatter(1, idx, torch.where(cur > 0, pen, sc))
+        if self.no_repeat > 0:                                                  # NoRepeatNGramLogitsProcessor: after the penalty, a ban wins
+            logp = logp.masked_fill(ngram_banned(self.run_seq.view(B * nb, -1), cur, self.no_repeat, V), -float("inf"))
         if has_eos and self.min_new > 0:                                        # MinNewTokensLengthLogitsProcessor
             col = logp.index_select(1, self.eos_t)
             logp.index_copy_(1, self.eos_t, torch.where(cur < self.min_new, torch.full_like(col, -float("inf")), col))
@@ -388,15 +415,15 @@ def sample_uniform(seed, rows, step, device="cpu"):
 
 
 class _SampleState(_SearchState):
-    """HF `_sample` with do_sample=True (num_beams = 1): RepetitionPenalty -> MinNewTokens -> Temperature -> TopK -> TopP on the fp32
+    """HF `_sample` with do_sample=True (num_beams = 1): RepetitionPenalty -> NoRepeatNGram -> MinNewTokens -> Temperature -> TopK -> TopP on the fp32
     logits (HF's order, generation/utils.py `_get_logits_processor`), then an inverse-CDF draw in vocabulary order fed by
     `sample_uniform(seed, row, cur)`; the drawn tokens also land in .seq[:, cur].
     The seed lives in DEVICE memory and the step counter is the device scalar `cur`: a captured step replays with a fresh number per
     token and per call.  Top-p keeps token i iff the softmax mass of the strictly greater scores is < top_p: HF's rule with the ties
     at the cut kept together (HF's own outcome on ties follows an unstable sort; include/mxvl.h records the deviation)."""
 
-    def __init__(self, B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev):
-        super().__init__(B, vocab, max_new, fill, eos, min_new, float(rep_pen), dev)
+    def __init__(self, B, vocab, max_new, fill, eos, min_new, rep_pen, temperature, top_k, top_p, dev, no_repeat_ngram_size=0):
+        super().__init__(B, vocab, max_new, fill, eos, min_new, float(rep_pen), dev, no_repeat_ngram_size)
         self.B = B
         self.temperature, self.top_p = float(temperature), float(top_p)
         self.top_k = min(int(top_k), vocab) if top_k else 0           # 0 = off (HF: None or 0)
@@ -436,6 +463,7 @@ class _SampleState(_SearchState):
         d = _abi.SampleDesc()
         d.rows, d.vocab, d.max_new, d.min_new, d.n_eos, d.top_k = self.B, self.V, self.max_new, self.min_new, self.eos_t.numel(), self.top_k
         d.repetition_penalty, d.temperature, d.top_p, d.fill = self.rep_pen, self.temperature, self.top_p, self.fill
+        d.no_repeat_ngram_size = self.no_repeat
         d.logits, d.seq, d.alive, d.tok, d.cur = logits.data_ptr(), self.seq.data_ptr(), self.alive.data_ptr(), self.tok.data_ptr(), self.cur.data_ptr()
         d.eos, d.seed = _abi.ptr(self.eos_t if self.eos_t.numel() else None), self.seed.data_ptr()
         d.unfinished, d.unfinished_log, d.scratch = self.unfinished.data_ptr(), _abi.ptr(self.unf_log), self.ticket.data_ptr()
@@ -452,6 +480,8 @@ class _SampleState(_SearchState):
             g = torch.gather(sc, 1, idx)
             pen = torch.where(g < 0, g * self.pen_t, g / self.pen_t)
             sc = sc.scatter(1, idx, torch.where(cur > 0, pen, g))
+        if self.no_repeat > 0:                                                  # NoRepeatNGramLogitsProcessor: after the penalty, a ban wins
+            sc = sc.masked_fill(ngram_banned(self.seq, cur, self.no_repeat, self.V), -float("inf"))
         if self.eos_t.numel() > 0 and self.min_new > 0:                         # MinNewTokensLengthLogitsProcessor
             col = sc.index_select(1, self.eos_t)
             sc.index_copy_(1, self.eos_t, torch.where(cur < self.min_new, torch.full_like(col, -float("inf")), col))
@@ -909,7 +939,7 @@ class ReportDecoder(nn.Module):
         return sum(t.numel() * t.element_size() for _, t in cache.values())
 
     # ---- generation ------------------------------------------------------------------------------------------
-    def _greedy(self, logits, cache, attn, dtype, eos_t, fill, min_new, max_new, rep_pen, stepper=None):
+    def _greedy(self, logits, cache, attn, dtype, eos_t, fill, min_new, max_new, rep_pen, stepper=None, no_repeat=0):
         """num_beams = 1 (HF `_sample` with do_sample=False): the processors act on the raw LOGITS here (on
         log-probabilities in beam search), finished rows keep emitting the pad token."""
         B, dev = logits.shape[0], logits.device
@@ -921,6 +951,8 @@ class ReportDecoder(nn.Module):
             if rep_pen != 1.0 and seq.shape[1] > 0:
                 g = torch.gather(sc, 1, seq)
                 sc = sc.scatter(1, seq, torch.where(g < 0, g * rep_pen, g / rep_pen))
+            if no_repeat > 0:                                                   # NoRepeatNGramLogitsProcessor (pad tokens of stopped rows count, as in HF)
+                sc = sc.masked_fill(ngram_banned(seq, torch.tensor(seq.shape[1], device=dev), no_repeat, sc.shape[1]), -float("inf"))
             if has_eos and seq.shape[1] < min_new:
                 sc[:, eos_t] = -float("inf")
             tok = sc.argmax(-1)
@@ -1015,6 +1047,8 @@ class ReportDecoder(nn.Module):
     def generate(self, inputs_embeds, *args, **kwargs):
         """Greedy (num_beams=1) / beam search / sampling (num_beams=1, do_sample=True with temperature, top_k, top_p, seed) over a
         prompt given as embeddings.  Returns (B, <= max_new_tokens) ids.
+        no_repeat_ngram_size = n > 0 (HF's keyword; 0 = off): no n-gram of generated tokens occurs twice in a row's output, in all
+        three modes; on a HIP device the ban is part of the beam / sampling kernel of the captured step.
         use_graph (default: on for HIP devices): static KV cache + one hipGraph replay per generated token.
         A decoder held in a 16-bit dtype decodes IN that dtype, prompt prefill included: an enclosing autocast context (the
         reference's validation_step runs under Lightning's bf16-mixed one, configs/config.py:67, around an LLM loaded with
@@ -1028,7 +1062,10 @@ class ReportDecoder(nn.Module):
 
     def _generate(self, inputs_embeds, attention_mask=None, num_beams=1, do_sample=False, min_new_tokens=0,
                   max_new_tokens=20, repetition_penalty=1.0, length_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                  early_stopping=False, temperature=None, use_graph=None, top_k=None, top_p=1.0, seed=None):
+                  early_stopping=False, temperature=None, use_graph=None, top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=0):
+        # HF: a strictly positive integer or unset; 0 (the default here) switches the processor off.  Checked before anything is enqueued
+        if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or no_repeat_ngram_size < 0:
+            raise ValueError(f"`no_repeat_ngram_size` (={no_repeat_ngram_size}) has to be a non-negative integer (0 = off)")
         if do_sample:
             # HF validates these before it generates (GenerationConfig.validate, the warpers' constructors): so do we, before
             # anything is enqueued.  With do_sample=False they stay ignored (the reference's default --temperature 0 keeps working)
@@ -1097,12 +1134,12 @@ class ReportDecoder(nn.Module):
                 stepper.reset(attention_mask, cache)
         if nb == 1 and not do_sample:
             return self._greedy(logits, cache, attention_mask, inputs_embeds.dtype, eos_t, fill, min_new_tokens,
-                                max_new_tokens, repetition_penalty, stepper)
+                                max_new_tokens, repetition_penalty, stepper, no_repeat_ngram_size)
         vocab = logits.shape[-1]
         loop_args = (logits, cache, attention_mask, inputs_embeds.dtype, stepper, use_graph)
         if do_sample:
             return self._sample(seed, (B, vocab, max_new_tokens, fill, tuple(eos), min_new_tokens, repetition_penalty, float(temperature),
-                                       top_k or 0, float(top_p), str(dev)), *loop_args)
+                                       top_k or 0, float(top_p), str(dev), no_repeat_ngram_size), *loop_args)
         state = self._search_state("_beam_states", _BeamState, B, nb, vocab, max_new_tokens, fill, tuple(eos), min_new_tokens,
-                                   repetition_penalty, length_penalty, early_stopping, str(dev))
+                                   repetition_penalty, length_penalty, early_stopping, str(dev), no_repeat_ngram_size)
         return self._search(state, *loop_args)
