@@ -13,8 +13,10 @@
 // totals, writes *unfinished and *cur and clears the word (no fence: nothing but the atomic's own value crosses workgroups).
 // Per element: (1) online max / sum-exp of every beam row (32
 // independent loads in flight per thread: a single workgroup is latency-, not bandwidth-limited on 384 KB of logits), (2) every
-// thread keeps the `keep` best penalised candidates of its strided share, history membership through an LDS bitmap,
-// (3) `keep` rounds of a block arg-max merge them, (4) a few lanes do the bookkeeping on the `keep` survivors.
+// thread keeps the two best penalised candidates of its strided share (cand_value into offer(Top2, ...)), history membership through an
+// LDS bitmap of the tile (build_tile_bitmaps), (3) `keep` rounds of a block arg-max merge them (block_top_keep; a thread that owned
+// more than two winners is repaired through surv_offer / merge_survivors), (4) a few lanes do the bookkeeping on the `keep` survivors.
+// The split-vocabulary layout (beam_cand_kernel) runs (2) and (3) per slice through the SAME functions: one copy of the arithmetic.
 // no_repeat_ngram_size = n > 0 (HF NoRepeatNGramLogitsProcessor, include/mxvl.h): every window of a row's history that equals its last
 // n - 1 tokens bans the token that followed it -- a list of at most max_new followers per row in LDS (ban_followers), turned into a
 // second bitmap of the tile next to the penalty's (mark_ban); a banned candidate is -inf after the penalty, the way a masked EOS is.
@@ -79,6 +81,130 @@ __device__ inline void mark_ban(const int* ban, unsigned int* banmap, int nb, in
   }
 }
 
+// ---- candidate selection: the pieces beam_cand_kernel (one vocabulary slice) and beam_step_kernel (the whole row) share ---------------
+// What a candidate's value depends on besides its row's statistics, and the LDS the selection works in.  Workgroup-uniform; each
+// kernel declares the arrays (s_red / s_redi: one entry per wave) and fills one of these.
+struct CandCtx {
+  unsigned int *bitmap, *banmap;      // [nb][words] each: history membership / n-gram-banned tokens of the tile being swept
+  const int* ban;                     // [nb][max_new] banned followers (ban_followers)
+  int nb, words, cur, max_new;
+  bool ban_on, mask_eos;
+  float rep_pen;
+  int eos32[kMaxEos];                 // the EOS ids live in registers: they are tested against every candidate
+  float* red; int* redi;              // block arg-max: one (value, index) per wave
+  float* top_lp; int* top_ix;         // [keep] winners, best first
+  float* surv_v; int* surv_i; int* nsurv;   // [kMaxSurv] candidates a rescan found above the keep-th winner
+};
+
+// History bitmap and ban bitmap of the tile [t0, t0 + tile) below vend; hist = [nb][max_new] live sequences (global or LDS).
+// Workgroup-uniform call: it synchronises (before: the last tile's readers; after: the bitmaps are complete).
+template <int kThreads>
+__device__ __forceinline__ void build_tile_bitmaps(const CandCtx& c, const long long* hist, int t0, int tile, int vend) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  for (int i = tid; i < c.nb * c.words * (c.ban_on ? 2 : 1); i += kThreads) c.bitmap[i] = 0u;      // (banmap follows bitmap)
+  __syncthreads();
+  if (c.ban_on) mark_ban(c.ban, c.banmap, c.nb, c.max_new, c.words, t0, tile, vend, kThreads);
+  if (c.rep_pen != 1.0f && c.cur > 0)
+    for (int i = tid; i < c.nb * c.cur; i += kThreads) {
+      const int r = i / c.cur, t = i - r * c.cur;
+      const long long tk = hist[r * c.max_new + t];
+      const int v = (int)tk - t0;
+      if (tk >= t0 && v < tile && tk < vend) atomicOr(&c.bitmap[r * c.words + (v >> 5)], 1u << (v & 31));
+    }
+  __syncthreads();
+}
+
+// Penalised, score-shifted value of token v of beam row r (raw logit `raw`, tile at t0).  The order of the fp32 operations is the
+// contract with report_decoder._BeamState.advance_torch: log-softmax, repetition penalty, n-gram ban, EOS mask, + running score.
+__device__ __forceinline__ float cand_value(const CandCtx& c, int r, int v, int t0, float raw, float rowmax, float logz, float rscore) {
+  float x = (raw - rowmax) - logz;                                          // log_softmax
+  // (the penalty behind a wave-uniform test: as a select, hipcc ran the fp32 division sequence for every word of the vocabulary)
+  const bool hit = (c.bitmap[r * c.words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u;
+  if (__any(hit)) x = hit ? (x < 0.0f ? x * c.rep_pen : x / c.rep_pen) : x;
+  if (c.ban_on && ((c.banmap[r * c.words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u)) x = -INFINITY;
+  if (c.mask_eos) {
+#pragma unroll
+    for (int e = 0; e < kMaxEos; ++e)
+      if (c.eos32[e] == v) x = -INFINITY;
+  }
+  return x + rscore;
+}
+
+// A thread's TWO best candidates.  A sorted `keep`-deep list per thread costs a wave-wide insertion for almost every element (some
+// lane always inserts): 100 us.  Two entries are exact unless one thread owns three of the final `keep` -- the callers detect that
+// (head == 2 after block_top_keep) and repair it by a rescan of that thread's share (practically never taken).
+struct Top2 { float v1, v2; int i1, i2; };
+// (a plain aggregate, set field by field and passed by value: with member initialisers or member functions hipcc promotes it to
+//  registers only after inlining, and the one-workgroup kernel came out three VGPRs above the 128 of four waves per SIMD)
+__device__ __forceinline__ Top2 offer(Top2 t, float x, int idx) {
+  if (x >= t.v2) {           // below the thread's second entry nothing changes: the (branch-free) insertion is the rare path
+    const bool b1 = better(x, idx, t.v1, t.i1), b2 = better(x, idx, t.v2, t.i2);
+    t.v2 = b1 ? t.v1 : (b2 ? x : t.v2);
+    t.i2 = b1 ? t.i1 : (b2 ? idx : t.i2);
+    t.v1 = b1 ? x : t.v1;
+    t.i1 = b1 ? idx : t.i1;
+  }
+  return t;
+}
+
+// `keep` rounds of block arg-max over the thread-local heads into c.top_lp / c.top_ix (best first); returns how many of the
+// thread's entries won.  Workgroup-uniform call: it synchronises.
+template <int kWaves>
+__device__ __forceinline__ int block_top_keep(const CandCtx& c, Top2 t, int keep) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int head = 0;
+  for (int round = 0; round < keep; ++round) {
+    float v = head == 0 ? t.v1 : head == 1 ? t.v2 : -INFINITY;
+    int ix = head == 0 ? t.i1 : head == 1 ? t.i2 : 0x7fffffff;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(v, off, 64);
+      const int oi = __shfl_xor(ix, off, 64);
+      if (better(ov, oi, v, ix)) { v = ov; ix = oi; }
+    }
+    if (lane == 0) { c.red[wave] = v; c.redi[wave] = ix; }
+    __syncthreads();
+    if (tid == 0) {
+      float bv = c.red[0];
+      int bi = c.redi[0];
+      for (int w = 1; w < kWaves; ++w)
+        if (better(c.red[w], c.redi[w], bv, bi)) { bv = c.red[w]; bi = c.redi[w]; }
+      c.top_lp[round] = bv;
+      c.top_ix[round] = bi;
+    }
+    __syncthreads();
+    const int win = c.top_ix[round];
+    if ((head == 0 && t.i1 == win) || (head == 1 && t.i2 == win)) ++head;
+  }
+  return head;
+}
+
+// Survivor repair.  surv_offer: a rescanned candidate that beats the keep-th winner (tau, tau_ix) goes into the survivor list;
+// merge_survivors (workgroup-uniform: it synchronises): thread 0 inserts the (few) survivors into the sorted winners.
+__device__ __forceinline__ void surv_offer(const CandCtx& c, float x, int idx, float tau, int tau_ix) {
+  if (better(x, idx, tau, tau_ix)) {
+    const int slot = atomicAdd(c.nsurv, 1);
+    if (slot < kMaxSurv) { c.surv_v[slot] = x; c.surv_i[slot] = idx; }
+  }
+}
+__device__ __forceinline__ void merge_survivors(const CandCtx& c, int keep) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int ns = *c.nsurv < kMaxSurv ? *c.nsurv : kMaxSurv;
+    for (int q = 0; q < ns; ++q) {
+      float x = c.surv_v[q];
+      int ix = c.surv_i[q];
+      for (int k = 0; k < keep; ++k)
+        if (better(x, ix, c.top_lp[k], c.top_ix[k])) {
+          const float tv = c.top_lp[k]; c.top_lp[k] = x; x = tv;
+          const int ti = c.top_ix[k]; c.top_ix[k] = ix; ix = ti;
+        }
+    }
+  }
+  __syncthreads();
+}
+
 // ---- the vocabulary over workgroups (round 4) ---------------------------------------------------------------------------------------
 // One workgroup per sample reads its nb x V logits twice (statistics, candidates) through ONE CU: 384 KB at the 30-40 GB/s a CU
 // sustains is 2 x 10 us, and the per-word candidate test on 16 waves of one CU another 10 (profiles/r04_beam_phase_ablation2.txt).
@@ -141,20 +267,25 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
   __shared__ int s_surv_i[kMaxSurv];
   __shared__ int s_nsurv;
   if (*p.unfinished == 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int s = blockIdx.x, b = blockIdx.y, nb = p.nb, V = p.V, keep = p.keep, S = p.S, max_new = p.max_new;
   const int v0 = s * p.VS, v1 = v0 + p.VS < V ? v0 + p.VS : V;
   const int tile = p.VS < kCandTile ? p.VS : kCandTile;        // words of the vocabulary per bitmap tile
   const int words = (tile + 31) / 32;
   const int cur = (int)*p.cur;
-  unsigned int* bitmap = cand_smem;
-  unsigned int* banmap = bitmap + nb * words;
-  int* ban = (int*)(banmap + nb * words);
-  const bool ban_on = kBan && p.ngram > 0 && cur >= p.ngram && cur < max_new;      // no window start i <= cur - n before that
-  if (ban_on) ban_followers(p.run_seq + (size_t)b * nb * max_new, ban, nb, max_new, cur, p.ngram, V, kCandThreads);
-  int eos32[kMaxEos];
+  CandCtx c;
+  c.bitmap = cand_smem;
+  c.banmap = c.bitmap + nb * words;
+  int* ban = (int*)(c.banmap + nb * words);
+  c.ban = ban;
+  c.nb = nb; c.words = words; c.cur = cur; c.max_new = max_new; c.rep_pen = p.rep_pen;
+  c.ban_on = kBan && p.ngram > 0 && cur >= p.ngram && cur < max_new;      // no window start i <= cur - n before that
+  c.mask_eos = cur < p.min_new;
+  c.red = s_red; c.redi = s_redi; c.top_lp = s_top_lp; c.top_ix = s_top_ix; c.surv_v = s_surv_v; c.surv_i = s_surv_i; c.nsurv = &s_nsurv;
+  const long long* hist = p.run_seq + (size_t)b * nb * max_new;
+  if (c.ban_on) ban_followers(hist, ban, nb, max_new, cur, p.ngram, V, kCandThreads);      // (build_tile_bitmaps synchronises)
 #pragma unroll
-  for (int e = 0; e < kMaxEos; ++e) eos32[e] = e < p.n_eos ? (int)p.eos[e] : -1;
+  for (int e = 0; e < kMaxEos; ++e) c.eos32[e] = e < p.n_eos ? (int)p.eos[e] : -1;
   // log-softmax statistics of the nb rows from the S partial results: lane k holds slice k, a shuffle tree combines them (the same
   // tree in every workgroup of the sample: identical log Z everywhere)
   for (int r = 0; r < nb; ++r) {
@@ -168,89 +299,28 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
     if (tid == 0) { s_rowmax[r] = mx; s_logz[r] = logf(ss); s_rscore[r] = p.run_score[b * nb + r]; }
   }
-  // bitmap of the history tokens that fall into [t0, t0 + tile) (workgroup-uniform call: it synchronises)
-  auto build_bitmap = [&](int t0) {
-    __syncthreads();
-    for (int i = tid; i < nb * words * (ban_on ? 2 : 1); i += kCandThreads) bitmap[i] = 0u;      // (banmap follows bitmap)
-    __syncthreads();
-    if (ban_on) mark_ban(ban, banmap, nb, max_new, words, t0, tile, v1, kCandThreads);
-    if (p.rep_pen != 1.0f && cur > 0) {
-      const long long* rs = p.run_seq + (size_t)b * nb * max_new;
-      for (int i = tid; i < nb * cur; i += kCandThreads) {
-        const int r = i / cur, t = i - r * cur;
-        const long long tk = rs[r * max_new + t];
-        const int v = (int)tk - t0;
-        if (tk >= t0 && v < tile && tk < v1) atomicOr(&bitmap[r * words + (v >> 5)], 1u << (v & 31));
-      }
-    }
-    __syncthreads();
-  };
-  const bool mask_eos = cur < p.min_new;
-  auto cand_value = [&](int r, int v, float raw, int t0) -> float {
-    float x = (raw - s_rowmax[r]) - s_logz[r];                              // log_softmax
-    const bool hit = (bitmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u;
-    if (__any(hit)) x = hit ? (x < 0.0f ? x * p.rep_pen : x / p.rep_pen) : x;
-    if (ban_on && ((banmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u)) x = -INFINITY;
-    if (mask_eos) {
-#pragma unroll
-      for (int e = 0; e < kMaxEos; ++e)
-        if (eos32[e] == v) x = -INFINITY;
-    }
-    return x + s_rscore[r];
-  };
-  float v1st = -INFINITY, v2nd = -INFINITY;
-  int i1 = 0x7fffffff, i2 = 0x7fffffff;
+  Top2 top;
+  top.v1 = top.v2 = -INFINITY; top.i1 = top.i2 = 0x7fffffff;
   for (int t0 = v0; t0 < v1; t0 += tile) {
-  build_bitmap(t0);
-  const int t1 = t0 + tile < v1 ? t0 + tile : v1;
-  for (int r = 0; r < nb; ++r) {
-    const float* row = p.logits + (size_t)(b * nb + r) * V;
-    for (int vb = t0 + tid; vb < t1; vb += 4 * kCandThreads) {      // four words of the thread in flight per trip
-      float raw[4];
+    build_tile_bitmaps<kCandThreads>(c, hist, t0, tile, v1);
+    const int t1 = t0 + tile < v1 ? t0 + tile : v1;
+    for (int r = 0; r < nb; ++r) {
+      const float* row = p.logits + (size_t)(b * nb + r) * V;
+      const float mx = s_rowmax[r], lz = s_logz[r], sc = s_rscore[r];
+      for (int vb = t0 + tid; vb < t1; vb += 4 * kCandThreads) {      // four words of the thread in flight per trip
+        float raw[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) raw[u] = vb + u * kCandThreads < t1 ? row[vb + u * kCandThreads] : -INFINITY;
+        for (int u = 0; u < 4; ++u) raw[u] = vb + u * kCandThreads < t1 ? row[vb + u * kCandThreads] : -INFINITY;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = vb + u * kCandThreads;
-        if (v >= t1) continue;
-        const float x = cand_value(r, v, raw[u], t0);
-        if (x >= v2nd) {
-          const int idx = r * V + v;
-          const bool b1 = better(x, idx, v1st, i1), b2 = better(x, idx, v2nd, i2);
-          v2nd = b1 ? v1st : (b2 ? x : v2nd);
-          i2 = b1 ? i1 : (b2 ? idx : i2);
-          v1st = b1 ? x : v1st;
-          i1 = b1 ? idx : i1;
+        for (int u = 0; u < 4; ++u) {
+          const int v = vb + u * kCandThreads;
+          if (v < t1) top = offer(top, cand_value(c, r, v, t0, raw[u], mx, lz, sc), r * V + v);
         }
       }
     }
   }
-  }
-  int head = 0;
-  for (int round = 0; round < keep; ++round) {
-    float v = head == 0 ? v1st : head == 1 ? v2nd : -INFINITY;
-    int ix = head == 0 ? i1 : head == 1 ? i2 : 0x7fffffff;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(v, off, 64);
-      const int oi = __shfl_xor(ix, off, 64);
-      if (better(ov, oi, v, ix)) { v = ov; ix = oi; }
-    }
-    if (lane == 0) { s_red[wave] = v; s_redi[wave] = ix; }
-    __syncthreads();
-    if (tid == 0) {
-      float bv = s_red[0];
-      int bi = s_redi[0];
-      for (int w = 1; w < kCandWaves; ++w)
-        if (better(s_red[w], s_redi[w], bv, bi)) { bv = s_red[w]; bi = s_redi[w]; }
-      s_top_lp[round] = bv;
-      s_top_ix[round] = bi;
-    }
-    __syncthreads();
-    const int win = s_top_ix[round];
-    if ((head == 0 && i1 == win) || (head == 1 && i2 == win)) ++head;
-  }
-  // exactness: a thread with both entries among the winners may hold more candidates above the keep-th value (as in beam_step_kernel)
+  const int head = block_top_keep<kCandWaves>(c, top, keep);
+  // exactness: a thread with both entries among the winners may hold more candidates above the keep-th value
   if (tid == 0) s_nsurv = 0;
   __syncthreads();
   const bool suspect = head == 2 && keep > 2;
@@ -258,37 +328,21 @@ __global__ __launch_bounds__(kCandThreads) void beam_cand_kernel(const BeamArgs 
     const float tau = s_top_lp[keep - 1];
     const int tau_ix = s_top_ix[keep - 1];
     for (int t0 = v0; t0 < v1; t0 += tile) {
-      if (v1 - v0 > tile) build_bitmap(t0);          // (a one-tile slice still holds its bitmap)
+      if (v1 - v0 > tile) build_tile_bitmaps<kCandThreads>(c, hist, t0, tile, v1);          // (a one-tile slice still holds its bitmap)
       const int t1 = t0 + tile < v1 ? t0 + tile : v1;
       if (suspect) {
         for (int r = 0; r < nb; ++r) {
           const float* row = p.logits + (size_t)(b * nb + r) * V;
-          for (int v = t0 + tid; v < t1; v += kCandThreads) {
+          const float mx = s_rowmax[r], lz = s_logz[r], sc = s_rscore[r];
+          for (int v = t0 + tid; v < t1; v += kCandThreads) {        // this thread's share of the tile, word by word
             const int idx = r * V + v;
-            if (idx == i1 || idx == i2) continue;
-            const float x = cand_value(r, v, row[v], t0);
-            if (better(x, idx, tau, tau_ix)) {
-              const int slot = atomicAdd(&s_nsurv, 1);
-              if (slot < kMaxSurv) { s_surv_v[slot] = x; s_surv_i[slot] = idx; }
-            }
+            if (idx == top.i1 || idx == top.i2) continue;
+            surv_offer(c, cand_value(c, r, v, t0, row[v], mx, lz, sc), idx, tau, tau_ix);
           }
         }
       }
     }
-    __syncthreads();
-    if (tid == 0) {
-      const int ns = s_nsurv < kMaxSurv ? s_nsurv : kMaxSurv;
-      for (int q = 0; q < ns; ++q) {
-        float x = s_surv_v[q];
-        int ix = s_surv_i[q];
-        for (int k = 0; k < keep; ++k)
-          if (better(x, ix, s_top_lp[k], s_top_ix[k])) {
-            const float tv = s_top_lp[k]; s_top_lp[k] = x; x = tv;
-            const int ti = s_top_ix[k]; s_top_ix[k] = ix; ix = ti;
-          }
-      }
-    }
-    __syncthreads();
+    merge_survivors(c, keep);
   }
   if (tid < keep) {
     p.ws_cand_v[((size_t)b * S + s) * keep + tid] = s_top_lp[tid];
@@ -327,18 +381,23 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
   const int cur = (int)*p.cur;
   const bool ban_lds = kBan && !merged && p.ngram > 0;                     // the launch reserved the ban bitmap and the follower list
   const bool ban_on = ban_lds && cur >= p.ngram && cur < max_new;  // no window start i <= cur - n before that
-  unsigned int* bitmap = smem_u;                                   // [nb][words] history membership of the tile being swept
-  unsigned int* banmap = bitmap + nb * words;                      // [nb][words] tokens the n-gram rule bans (ban_lds)
   long long* old_run = (long long*)(smem_u + ((nb * words * (ban_lds ? 2 : 1) + 1) & ~1));   // [nb][max_new]
   long long* old_fin = old_run + nb * max_new;                     // [nb][max_new]
   int* ban = (int*)(old_fin + nb * max_new);                       // [nb][max_new] banned followers (ban_lds)
+  CandCtx c;
+  c.bitmap = smem_u;                                               // [nb][words] history membership of the tile being swept
+  c.banmap = c.bitmap + nb * words;                                // [nb][words] tokens the n-gram rule bans (ban_lds)
+  c.ban = ban;
+  c.nb = nb; c.words = words; c.cur = cur; c.max_new = max_new; c.rep_pen = p.rep_pen;
+  c.ban_on = ban_on;
+  c.mask_eos = cur < p.min_new;
+  c.red = s_red; c.redi = s_redi; c.top_lp = s_top_lp; c.top_ix = s_top_ix; c.surv_v = s_surv_v; c.surv_i = s_surv_i; c.nsurv = &s_nsurv;
   // a search that has already stopped stays stopped: the stepper enqueues token k + 1 before the host has read token k's flag
   // (report_decoder._search_lookahead), and that speculative launch must leave the state as the last real one left it
   if (*p.unfinished == 0) return;
   if (tid == 0) { s_any_open = 0; s_all_hits = 1; s_all_done = 1; }
-  int eos32[kMaxEos];                  // the EOS ids live in registers: they are tested against every candidate
 #pragma unroll
-  for (int e = 0; e < kMaxEos; ++e) eos32[e] = e < p.n_eos ? (int)p.eos[e] : -1;
+  for (int e = 0; e < kMaxEos; ++e) c.eos32[e] = e < p.n_eos ? (int)p.eos[e] : -1;
 
   for (int b = blockIdx.x; b < p.batch; b += gridDim.x) {
     __syncthreads();
@@ -359,22 +418,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
     }
     for (int i = tid; i < nb * max_new; i += kBeamThreads) { old_run[i] = rs[i]; old_fin[i] = fs[i]; }
     __syncthreads();
-    if (ban_on) ban_followers(old_run, ban, nb, max_new, cur, p.ngram, V, kBeamThreads);      // (build_bitmap synchronises)
-    // bitmap of the history tokens in [t0, t0 + TILE) (workgroup-uniform call: it synchronises)
-    auto build_bitmap = [&](int t0) {
-      __syncthreads();
-      for (int i = tid; i < nb * words * (ban_on ? 2 : 1); i += kBeamThreads) bitmap[i] = 0u;      // (banmap follows bitmap)
-      __syncthreads();
-      if (ban_on) mark_ban(ban, banmap, nb, max_new, words, t0, TILE, V, kBeamThreads);
-      if (p.rep_pen != 1.0f && cur > 0)
-        for (int i = tid; i < nb * cur; i += kBeamThreads) {
-          const int r = i / cur, t = i - r * cur;
-          const long long tk = old_run[r * max_new + t];
-          const int v = (int)tk - t0;
-          if (tk >= t0 && v < TILE && tk < V) atomicOr(&bitmap[r * words + (v >> 5)], 1u << (v & 31));
-        }
-      __syncthreads();
-    };
+    if (ban_on) ban_followers(old_run, ban, nb, max_new, cur, p.ngram, V, kBeamThreads);      // (build_tile_bitmaps synchronises)
     // ---- (1) log-softmax statistics per beam row: one sweep, U independent loads in flight per thread --------------
     // word u of a thread's trip: four consecutive words per 16-byte load when the rows allow it (a quarter of the load instructions)
     auto vof = [&](int base, int u) {
@@ -437,80 +481,30 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
       __syncthreads();
     }
     if (MXVL_ABL(p.ablate == 1)) continue;
-    // ---- (2) every thread keeps its TWO best penalised, score-shifted candidates (branch-free insertion) ---------------
-    // A sorted `keep`-deep list per thread costs a wave-wide insertion for almost every element (some lane always
-    // inserts): 100 us.  Two entries per thread are exact unless one thread owns three of the final `keep` -- detected
-    // below and repaired by a rescan of that thread's share (practically never taken).
-    auto cand_value = [&](int r, int v, float raw, float mx, float lz, float sc, bool mask_eos, int t0) -> float {
-      float x = (raw - mx) - lz;                                              // log_softmax
-      // (the penalty behind a wave-uniform test: as a select, hipcc ran the fp32 division sequence for every word of the vocabulary)
-      const bool hit = (bitmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u;
-      if (__any(hit)) x = hit ? (x < 0.0f ? x * p.rep_pen : x / p.rep_pen) : x;
-      if (ban_on && ((banmap[r * words + ((v - t0) >> 5)] >> ((v - t0) & 31)) & 1u)) x = -INFINITY;
-      if (mask_eos) {
-#pragma unroll
-        for (int e = 0; e < kMaxEos; ++e)
-          if (eos32[e] == v) x = -INFINITY;
-      }
-      return x + sc;
-    };
-    float v1 = -INFINITY, v2 = -INFINITY;
-    int i1 = 0x7fffffff, i2 = 0x7fffffff;
+    // ---- (2) every thread keeps its TWO best penalised, score-shifted candidates (Top2) ---------------------------------
+    Top2 top;
+    top.v1 = top.v2 = -INFINITY; top.i1 = top.i2 = 0x7fffffff;
     if (merged && tid < p.S * keep) {     // one entry per thread: the `keep` best of every vocabulary slice of this sample
-      v1 = p.ws_cand_v[(size_t)b * p.S * keep + tid];
-      i1 = p.ws_cand_i[(size_t)b * p.S * keep + tid];
+      top.v1 = p.ws_cand_v[(size_t)b * p.S * keep + tid];
+      top.i1 = p.ws_cand_i[(size_t)b * p.S * keep + tid];
     }
     for (int base = 0; base < (merged ? 0 : V); base += TILE) {
-      build_bitmap(base);
+      build_tile_bitmaps<kBeamThreads>(c, old_run, base, TILE, V);
       for (int r = 0; r < nb; ++r) {
         const float* row = lg + (size_t)r * V;
         const float mx = s_rowmax[r], lz = s_logz[r], sc = s_in_rscore[r];
-        const bool mask_eos = cur < p.min_new;
         float xs[U];
         load_trip(row, base, xs);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int v = vof(base, u);
-          if (v < V) {
-            const float x = cand_value(r, v, xs[u], mx, lz, sc, mask_eos, base);
-            if (x >= v2) {           // below the thread's second entry nothing changes: the insertion is the rare path
-              const int idx = r * V + v;
-              const bool b1 = better(x, idx, v1, i1), b2 = better(x, idx, v2, i2);
-              v2 = b1 ? v1 : (b2 ? x : v2);
-              i2 = b1 ? i1 : (b2 ? idx : i2);
-              v1 = b1 ? x : v1;
-              i1 = b1 ? idx : i1;
-            }
-          }
+          if (v < V) top = offer(top, cand_value(c, r, v, base, xs[u], mx, lz, sc), r * V + v);
         }
       }
     }
     if (MXVL_ABL(p.ablate == 2)) continue;
     // ---- (3) `keep` rounds of block arg-max over the thread-local heads --------------------------------------------------
-    int head = 0;
-    for (int round = 0; round < keep; ++round) {
-      float v = head == 0 ? v1 : head == 1 ? v2 : -INFINITY;
-      int ix = head == 0 ? i1 : head == 1 ? i2 : 0x7fffffff;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(ix, off, 64);
-        if (better(ov, oi, v, ix)) { v = ov; ix = oi; }
-      }
-      if (lane == 0) { s_red[wave] = v; s_redi[wave] = ix; }
-      __syncthreads();
-      if (tid == 0) {
-        float bv = s_red[0];
-        int bi = s_redi[0];
-        for (int w = 1; w < kBeamWaves; ++w)
-          if (better(s_red[w], s_redi[w], bv, bi)) { bv = s_red[w]; bi = s_redi[w]; }
-        s_top_lp[round] = bv;
-        s_top_ix[round] = bi;
-      }
-      __syncthreads();
-      const int win = s_top_ix[round];
-      if ((head == 0 && i1 == win) || (head == 1 && i2 == win)) ++head;
-    }
+    const int head = block_top_keep<kBeamWaves>(c, top, keep);
     // exactness: a thread with both entries among the winners may hold more candidates above the keep-th value
     if (tid == 0) s_nsurv = 0;
     __syncthreads();
@@ -519,7 +513,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
       const float tau = s_top_lp[keep - 1];
       const int tau_ix = s_top_ix[keep - 1];
       for (int base = 0; base < (merged ? 0 : V); base += TILE) {
-        if (V > TILE) build_bitmap(base);            // (a one-tile vocabulary still holds its bitmap)
+        if (V > TILE) build_tile_bitmaps<kBeamThreads>(c, old_run, base, TILE, V);            // (a one-tile vocabulary still holds its bitmap)
         if (suspect) {
           for (int r = 0; r < nb; ++r) {
             const float* row = lg + (size_t)r * V;
@@ -528,30 +522,13 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
               const int v = vof(base, u);
               if (v >= V) continue;
               const int idx = r * V + v;
-              if (idx == i1 || idx == i2) continue;
-              const float x = cand_value(r, v, row[v], mx, lz, sc, cur < p.min_new, base);
-              if (better(x, idx, tau, tau_ix)) {
-                const int slot = atomicAdd(&s_nsurv, 1);
-                if (slot < kMaxSurv) { s_surv_v[slot] = x; s_surv_i[slot] = idx; }
-              }
+              if (idx == top.i1 || idx == top.i2) continue;
+              surv_offer(c, cand_value(c, r, v, base, row[v], mx, lz, sc), idx, tau, tau_ix);
             }
           }
         }
       }
-      __syncthreads();
-      if (tid == 0) {     // insertion of the (few) survivors into the sorted winners
-        const int ns = s_nsurv < kMaxSurv ? s_nsurv : kMaxSurv;
-        for (int q = 0; q < ns; ++q) {
-          float x = s_surv_v[q];
-          int ix = s_surv_i[q];
-          for (int k = 0; k < keep; ++k)
-            if (better(x, ix, s_top_lp[k], s_top_ix[k])) {
-              const float tv = s_top_lp[k]; s_top_lp[k] = x; x = tv;
-              const int ti = s_top_ix[k]; s_top_ix[k] = ix; ix = ti;
-            }
-        }
-      }
-      __syncthreads();
+      merge_survivors(c, keep);
     }
     if (MXVL_ABL(p.ablate == 3)) continue;
     // ---- (4) bookkeeping on the survivors (one lane; everything here is `keep` <= 8 wide) -----------------------------
@@ -578,7 +555,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(const BeamArgs 
         ntok[k] = s_top_ix[k] - src[k] * V;
         bool h = cur + 1 >= max_new;
 #pragma unroll
-        for (int e = 0; e < kMaxEos; ++e) h = h || (eos32[e] == ntok[k]);
+        for (int e = 0; e < kMaxEos; ++e) h = h || (c.eos32[e] == ntok[k]);
         hits[k] = h ? 1 : 0;
         if (!h) s_all_hits = 0;
         live_lp[k] = top_lp[k] + (h ? 1.0f : 0.0f) * -1e9f;

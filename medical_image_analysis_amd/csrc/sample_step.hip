@@ -92,26 +92,78 @@ __device__ __forceinline__ u64 wave_incl_scan(u64 v) {
   return v;
 }
 
-// One level of the descent over hist[kBins] (complete, barrier passed): the smallest digit d with above + sum(hist[> d]) < limit.
-// Leaves d in *s_digit, above + sum(hist[> d]) in *s_above and above + sum(hist[>= d]) in *s_incl (read after the barrier it ends
-// with).  sum(hist) + above >= limit is NOT required: when every digit passes, d = 0.
-__device__ __forceinline__ void descend(const u64* hist, u64 above, u64 limit, int* s_digit, u64* s_above, u64* s_incl, u64* s_wtot) {
+// The LDS the radix selection works in: a histogram of one digit and what descend leaves behind.
+struct RadixLds { u64* hist; u64* wtot; u64* above; u64* incl; int* digit; };
+
+// Thread t owns the digits hi = kBins - 1 - 2t and hi - 1 of L.hist (complete, barrier passed): thread order = descending digit
+// order.  Returns the wave's inclusive scan of a + b and leaves every wave's total in L.wtot (a barrier passed).
+__device__ __forceinline__ u64 hist_scan(const RadixLds& L, int hi, u64& a, u64& b) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  // thread t owns the digits hi = kBins - 1 - 2t and hi - 1: thread order = descending digit order
-  const int hi = kBins - 1 - 2 * tid;
-  const u64 a = hist[hi], b = hist[hi - 1];
+  a = L.hist[hi]; b = L.hist[hi - 1];
   const u64 inc = wave_incl_scan(a + b);
-  if (lane == kWave - 1) s_wtot[wave] = inc;
+  if (lane == kWave - 1) L.wtot[wave] = inc;
   __syncthreads();
+  return inc;
+}
+
+// sum(L.hist); ends with the barrier that lets L.wtot be written again
+__device__ __forceinline__ u64 hist_total(const RadixLds& L) {
+  u64 a, b, z = 0;
+  hist_scan(L, kBins - 1 - 2 * (int)threadIdx.x, a, b);
+  for (int w = 0; w < kSampWaves; ++w) z += L.wtot[w];
+  __syncthreads();
+  return z;
+}
+
+// One level of the descent over L.hist (complete, barrier passed): the smallest digit d with above + sum(hist[> d]) < limit.
+// Leaves d in *L.digit, above + sum(hist[> d]) in *L.above and above + sum(hist[>= d]) in *L.incl (read after the barrier it ends
+// with).  sum(hist) + above >= limit is NOT required: when every digit passes, d = 0.
+__device__ __forceinline__ void descend(const RadixLds& L, u64 above, u64 limit) {
+  const int wave = threadIdx.x / kWave, hi = kBins - 1 - 2 * (int)threadIdx.x;
+  u64 a, b;
+  const u64 inc = hist_scan(L, hi, a, b);
   u64 before = above;
-  for (int w = 0; w < wave; ++w) before += s_wtot[w];
+  for (int w = 0; w < wave; ++w) before += L.wtot[w];
   const u64 gt_hi = before + inc - (a + b);       // above + mass of the digits > hi
   const u64 gt_lo = gt_hi + a;                    // ... > hi - 1
   const u64 ge_lo = gt_lo + b;
   // digit d is the answer iff (above + M_>(d) < limit) and (d == 0 or above + M_>=(d) >= limit): exactly one digit qualifies
-  if (gt_hi < limit && gt_lo >= limit) { *s_digit = hi; *s_above = gt_hi; *s_incl = gt_lo; }
-  if (gt_lo < limit && (ge_lo >= limit || hi - 1 == 0)) { *s_digit = hi - 1; *s_above = gt_lo; *s_incl = ge_lo; }
+  if (gt_hi < limit && gt_lo >= limit) { *L.digit = hi; *L.above = gt_hi; *L.incl = gt_lo; }
+  if (gt_lo < limit && (ge_lo >= limit || hi - 1 == 0)) { *L.digit = hi - 1; *L.above = gt_lo; *L.incl = ge_lo; }
   __syncthreads();
+}
+
+// Histogram of radix digit `level` (0 / 1 / 2: 11 + 11 + 10 bits of the key, top down) over the scores whose higher digits equal
+// `prefix`'s: L.hist[digit] = sum of weight(score, key).  Zeroes first; ends with the barrier that completes the histogram.
+template <typename W>
+__device__ __forceinline__ void radix_fill(const RadixLds& L, const float* sc, int V, int vec4, int level, uint32_t prefix, W weight) {
+  for (int i = threadIdx.x; i < kBins; i += kSampThreads) L.hist[i] = 0;
+  __syncthreads();
+  const int shift = level == 0 ? 21 : level == 1 ? 10 : 0, up = level == 1 ? 21 : 10;
+  const uint32_t mask = level == 2 ? 0x3FFu : 0x7FFu;
+  sweep(sc, V, vec4, [&](int, float s) {
+    const uint32_t k = score_key(s);
+    if (level == 0 || (k >> up) == (prefix >> up)) { const u64 w = weight(s, k); if (w) atomicAdd(&L.hist[(k >> shift) & mask], w); }
+  });
+  __syncthreads();
+}
+
+// The smallest 32-bit key t with weight{key > t} < limit, by three radix levels.  PREFILLED: L.hist must already hold the first
+// level, as radix_fill(level 0, weight) leaves it (top-k fuses those sums into the row-max sweep; top-p fills it to take Z from
+// its total before it knows `limit`) -- levels 1 and 2 are filled here.
+template <typename W>
+__device__ __forceinline__ uint32_t radix_select_prefilled(const RadixLds& L, const float* sc, int V, int vec4, u64 limit, W weight) {
+  uint32_t prefix = 0;
+  u64 above = 0;
+#pragma unroll
+  for (int level = 0; level < 3; ++level) {
+    if (level > 0) radix_fill(L, sc, V, vec4, level, prefix, weight);
+    descend(L, above, limit);
+    prefix |= (uint32_t)*L.digit << (level == 0 ? 21 : level == 1 ? 10 : 0);
+    above = *L.above;
+    __syncthreads();
+  }
+  return prefix;
 }
 
 __global__ __launch_bounds__(kSampThreads) void sample_step_kernel(SampleArgs p) {
@@ -210,91 +262,27 @@ __global__ __launch_bounds__(kSampThreads) void sample_step_kernel(SampleArgs p)
 #pragma unroll
   for (int w = 1; w < kSampWaves; ++w) mx = fmaxf(mx, s_wmax[w]);
 
-  // ---- top-k: the k-th largest key, three levels ----------------------------------------------------------------------------------
+  // ---- top-k: the k-th largest key -------------------------------------------------------------------------------------------------
+  const RadixLds L = {s_hist, s_wtot, &s_above, &s_incl, &s_digit};
   uint32_t key_min = 0;                           // kept <=> key >= key_min
-  if (use_k) {
-    const u64 limit = (u64)p.top_k;
-    descend(s_hist, 0, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    uint32_t prefix = (uint32_t)s_digit << 21;
-    u64 above = s_above;
-    __syncthreads();
-    for (int i = tid; i < kBins; i += kSampThreads) s_hist[i] = 0;
-    __syncthreads();
-    sweep(sc, V, vec4, [&](int, float s) {
-      const uint32_t k = score_key(s);
-      if ((k >> 21) == (prefix >> 21)) atomicAdd(&s_hist[(k >> 10) & 0x7FFu], (u64)1);
-    });
-    __syncthreads();
-    descend(s_hist, above, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    prefix |= (uint32_t)s_digit << 10;
-    above = s_above;
-    __syncthreads();
-    for (int i = tid; i < kBins; i += kSampThreads) s_hist[i] = 0;
-    __syncthreads();
-    sweep(sc, V, vec4, [&](int, float s) {
-      const uint32_t k = score_key(s);
-      if ((k >> 10) == (prefix >> 10)) atomicAdd(&s_hist[k & 0x3FFu], (u64)1);
-    });
-    __syncthreads();
-    descend(s_hist, above, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    key_min = prefix | (uint32_t)s_digit;
-    __syncthreads();
-  }
+  if (use_k) key_min = radix_select_prefilled(L, sc, V, vec4, (u64)p.top_k, [](float, uint32_t) -> u64 { return 1; });
 
   // mass of a kept score in units of 2^-qbits (truncated): an integer, so sums of it do not depend on their order
   const float mscale = p.mass_scale;
   auto mass = [&](float s) -> u64 { return (u64)(fast_exp2((s - mx) * kLog2e) * mscale); };
 
-  // ---- top-p: the smallest key t with mass{key > t} < top_p * Z, three levels with a mass per bucket ----------------------------
+  // ---- top-p: the smallest key t with mass{key > t} < top_p * Z, a mass per bucket instead of a count --------------------------
   if (use_p) {
-    for (int i = tid; i < kBins; i += kSampThreads) s_hist[i] = 0;
-    __syncthreads();
-    sweep(sc, V, vec4, [&](int, float s) {
-      const uint32_t k = score_key(s);
-      if (k >= key_min) { const u64 m = mass(s); if (m) atomicAdd(&s_hist[k >> 21], m); }
-    });
-    __syncthreads();
-    // Z = the whole histogram: one more descent-style reduction (limit 0 never passes; take the total from thread-order sums)
-    {
-      const int hi = kBins - 1 - 2 * tid;
-      const u64 inc = wave_incl_scan(s_hist[hi] + s_hist[hi - 1]);
-      if (lane == kWave - 1) s_wtot[wave] = inc;
-      __syncthreads();
-    }
-    u64 Z = 0;
-    for (int w = 0; w < kSampWaves; ++w) Z += s_wtot[w];
-    __syncthreads();
+    auto kept_mass = [&](float s, uint32_t k) -> u64 { return k >= key_min ? mass(s) : 0; };
+    radix_fill(L, sc, V, vec4, 0, 0u, kept_mass);
+    const u64 Z = hist_total(L);
     // top_p * Z, rounded up: mass{key > t} is an integer, so `< top_p * Z` is `< ceil(top_p * Z)`
     const double pz = (double)p.top_p * (double)Z;
     u64 limit = (u64)pz;
     if ((double)limit < pz) ++limit;
     if (limit == 0) limit = 1;                    // the largest score is always kept
-    descend(s_hist, 0, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    uint32_t prefix = (uint32_t)s_digit << 21;
-    u64 above = s_above;
-    __syncthreads();
-    for (int i = tid; i < kBins; i += kSampThreads) s_hist[i] = 0;
-    __syncthreads();
-    sweep(sc, V, vec4, [&](int, float s) {
-      const uint32_t k = score_key(s);
-      if (k >= key_min && (k >> 21) == (prefix >> 21)) { const u64 m = mass(s); if (m) atomicAdd(&s_hist[(k >> 10) & 0x7FFu], m); }
-    });
-    __syncthreads();
-    descend(s_hist, above, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    prefix |= (uint32_t)s_digit << 10;
-    above = s_above;
-    __syncthreads();
-    for (int i = tid; i < kBins; i += kSampThreads) s_hist[i] = 0;
-    __syncthreads();
-    sweep(sc, V, vec4, [&](int, float s) {
-      const uint32_t k = score_key(s);
-      if (k >= key_min && (k >> 10) == (prefix >> 10)) { const u64 m = mass(s); if (m) atomicAdd(&s_hist[k & 0x3FFu], m); }
-    });
-    __syncthreads();
-    descend(s_hist, above, limit, &s_digit, &s_above, &s_incl, s_wtot);
-    const uint32_t t = prefix | (uint32_t)s_digit;
+    const uint32_t t = radix_select_prefilled(L, sc, V, vec4, limit, kept_mass);
     key_min = t > key_min ? t : key_min;
-    __syncthreads();
   }
 
   // ---- final: kept mass of the 16 contiguous parts (wave w owns blocks of 256 tokens [w * bpw, (w + 1) * bpw)), then the draw ----
