@@ -212,6 +212,21 @@ typedef struct mxvl_conv1d_bwd_desc {
  * projection -- y = rsqrt(mean(x^2) + eps)[m] * sum_k W[n][k] * dtype(norm_weight[k] * x[m][k]): the gain rides on the activation
  * fragments, the squares are summed beside the MFMAs, the row statistic scales the fp32 sums in the epilogue.  One 16-bit rounding
  * less than the modules' dtype(dtype(x * rstd) * g) (not bit-equal; within two ulp of the output type). */
+/* Int8 weights (W8A16): `dtype | MXVL_W_INT8`.  W / W2 are then (N, K) int8 row-major codes CB of a row-wise absmax quantisation
+ * (bitsandbytes' Int8Params storage: SCB[n] = max_k |W[n][k]|, CB[n][k] = round(W[n][k] * 127 / SCB[n])), w_scale / w2_scale the (N)
+ * fp32 SCB; x, bias, residual, y stay `dtype & ~MXVL_W_INT8`:
+ *   y[m][n] = epi( s[n] * fp32( sum_k float(CB[n][k]) * float(x[m][k]) ) ),   s[n] = w_scale[n] / 127
+ * Code -> element conversion and every product are exact; only the order of the fp32 sum and the final rounding are the kernel's.
+ * epi: + bias, + residual, swiglu = silu(s acc) * (s2 acc2), split_acc planes (plane p holds s[n] * its partial sum, so
+ * mxvl_decode_rmsnorm folds them unchanged).  rows 1..80, K % 64 == 0, K >= 64, norm_weight == NULL, out_f32 == 0 (MXVL_ERR_SHAPE
+ * otherwise, before any launch); a NULL w_scale (w2_scale with swiglu) is MXVL_ERR_NULL.  One matrix-core kernel serves every row
+ * count and k_splits value (csrc/decode_gemm.h decode_gemm_w8_kernel): there is no int8 form of the <= 8-row GEMV.
+ * The flag is one high bit of `dtype`, so every value a caller could have stored there before still means what it meant (1, 2, 0)
+ * or is still refused with MXVL_ERR_DTYPE (`dtype & ~MXVL_W_INT8` is validated as `dtype` was).
+ * w_scale / w2_scale are TRAILING fields added without a new ABI version: the library reads them only when the flag is set, and a
+ * caller built against the shorter struct never sets it -- its descriptor stays valid as it is (the argument of the `reserved0`
+ * reuse in mxvl_beam_desc / mxvl_sample_desc). */
+#define MXVL_W_INT8 0x100
 typedef struct mxvl_gemv_desc {
   int32_t rows, K, N;
   int32_t swiglu, out_f32;
@@ -237,6 +252,7 @@ typedef struct mxvl_gemv_desc {
                                fp16 (|x| <= 65504 already), and a layer of uniformly small gains (Llama's first input_layernorm: 1e-2 ..
                                1e-3) no longer pushes g * x into fp16's subnormals.  The modules normalise in fp32 FIRST (x * rstd is O(1)),
                                so they never had either failure; bf16 has fp32's exponent range and does not need it. */
+  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8 only (never read otherwise): (N) fp32 row-wise absmax of W / W2; w2_scale with swiglu */
 } mxvl_gemv_desc;
 
 /*
@@ -344,8 +360,9 @@ typedef struct mxvl_rmsnorm_desc {
 int mxvl_set_decode_gemm_wide(int on);
 /* Diagnostic (ABI v8): which kernel mxvl_decode_gemv would launch for a descriptor -- the dispatch as a pure function, nothing is launched
  * and no GPU is needed.  out[0] = 2 the per-row GEMV kernel (<= 8 rows, k_splits == 0), 1 = decode_gemm_wide_kernel, 0 = the K-split
- * matrix-core kernels; for 1: out[1] waves per workgroup, out[2] weight tiles per wave, out[3] LDS ring stages, out[4] workgroups.
- * Same argument checks and error codes as mxvl_decode_gemv. */
+ * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count); for 1 and 3: out[1] waves per
+ * workgroup, out[2] weight tiles per wave, out[3] LDS ring stages, out[4] workgroups.  Same argument checks and error codes as
+ * mxvl_decode_gemv. */
 int mxvl_decode_gemm_plan(const mxvl_gemv_desc *desc, int32_t out[5]);
 int mxvl_decode_rmsnorm(const mxvl_rmsnorm_desc *desc, void *hip_stream);
 int mxvl_decode_prologue(const mxvl_decode_prologue_desc *desc, void *hip_stream);

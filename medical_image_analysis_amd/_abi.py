@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libmxvl.so")
 ABI_VERSION = 13
 
 MXVL_F32, MXVL_BF16, MXVL_F16 = 0, 1, 2
+MXVL_W_INT8 = 0x100      # mxvl_gemv_desc.dtype flag: W / W2 are int8 codes, w_scale / w2_scale their row-wise absmax
 SCAN_DELTA_SOFTPLUS = 1
 SCAN_OUT_F32 = 2          # out / dout fp32 whatever io_dtype is (the oflex i16o32 mode)
 SCAN_FOLD_BATCH = 4       # the batch folded into the sequence (short rows; ask mxvl_scan_fold_ok)
@@ -121,6 +122,7 @@ class GemvDesc(ctypes.Structure):
         ("x", c_void_p), ("norm_weight", c_void_p), ("W", c_void_p), ("W2", c_void_p), ("bias", c_void_p),
         ("residual", c_void_p), ("y", c_void_p), ("split_acc", c_void_p), ("k_splits", c_int32), ("dtype", c_int32),
         ("norm_gain_scale", ctypes.c_float),
+        ("w_scale", c_void_p), ("w2_scale", c_void_p),
     ]
 
 

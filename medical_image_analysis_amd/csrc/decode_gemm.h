@@ -38,6 +38,7 @@ struct DecodeGemmArgs {
   const uint16_t* g;    // RMSNorm gain (K) of the activation rows, fused (NORM instantiations of the LDS-DMA kernel); else NULL
   float eps;
   float g_scale, g_inv;   // NORM: power-of-two scale on the gain (mxvl_gemv_desc.norm_gain_scale) and its reciprocal, folded into rstd
+  const float *ws, *ws2;  // MXVL_W_INT8: W / W2 are (N, K) int8 codes, ws / ws2 (N) their row-wise absmax (decode_gemm_w8_kernel); else NULL
 };
 
 // Reduction over the waves' K split + the epilogue of mxvl_decode_gemv, one round per output tile (SwiGLU: per gate / up pair).
@@ -367,6 +368,73 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_dma_kernel(const DecodeGe
   }
 }
 
+// Epilogue of the kernels whose waves own their columns over the whole K range (no cross-wave reduction): straight from the
+// accumulators, lane (l16 -> activation row, 4 q + v -> column of the tile), a lane's four columns of a row as ONE 16- / 8-byte store.
+template <typename E, int MT, int R>
+__device__ __forceinline__ void dgw_epilogue(const DecodeGemmArgs& p, const dg_f32x4 (&acc)[R][MT], int n0, int l16, int q) {
+  const int N = p.N;
+  const int tiles = p.swiglu ? R / 2 : R;
+#pragma unroll
+  for (int t = 0; t < (R > 1 ? R : 1); ++t) {
+    if (t >= tiles) break;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = mt * 16 + l16;
+      if (m >= p.rows) continue;
+      const int nq = n0 + t * 16 + 4 * q;
+      if ((N & 3) == 0 && nq + 3 < N) {             // the lane's four columns as one store (16 bytes of a plane, 8 of a 16-bit row)
+        const size_t o = (size_t)m * N + nq;
+        const dg_f32x4 s0 = acc[t][mt];
+        if (p.split_acc) {
+          *(dg_f32x4*)(p.split_acc + (size_t)blockIdx.y * p.rows * N + o) = s0;
+        } else if (p.swiglu) {
+          const dg_f32x4 s1 = acc[(t + R / 2) < R ? t + R / 2 : t][mt];
+          uint16_t h[4];
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const float gte = E::rr(s0[v]), up = E::rr(s1[v]);
+            h[v] = E::r(E::rr(gte * sigmoid(gte)) * up);
+          }
+          *(uint2*)((uint16_t*)p.y + o) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
+        } else {
+          float val[4] = {s0[0], s0[1], s0[2], s0[3]};
+          if (p.bias) {
+            const uint2 bw = *(const uint2*)(p.bias + nq);
+            val[0] += E::lo(bw.x); val[1] += E::hi(bw.x); val[2] += E::lo(bw.y); val[3] += E::hi(bw.y);
+          }
+          if (p.res) {
+            const uint2 rw = *(const uint2*)(p.res + o);
+            val[0] = E::rr(val[0]) + E::lo(rw.x); val[1] = E::rr(val[1]) + E::hi(rw.x);
+            val[2] = E::rr(val[2]) + E::lo(rw.y); val[3] = E::rr(val[3]) + E::hi(rw.y);
+          }
+          if (p.out_f32) *(dg_f32x4*)((float*)p.y + o) = dg_f32x4{val[0], val[1], val[2], val[3]};
+          else *(uint2*)((uint16_t*)p.y + o) = make_uint2((uint32_t)E::r(val[0]) | ((uint32_t)E::r(val[1]) << 16), (uint32_t)E::r(val[2]) | ((uint32_t)E::r(val[3]) << 16));
+        }
+        continue;
+      }
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int n = n0 + t * 16 + 4 * q + v;
+        if (n >= N) continue;
+        const float s0 = acc[t][mt][v];
+        const size_t o = (size_t)m * N + n;
+        if (p.split_acc) {
+          p.split_acc[(size_t)blockIdx.y * p.rows * N + o] = s0;
+        } else if (p.swiglu) {
+          const float s1 = acc[(t + R / 2) < R ? t + R / 2 : t][mt][v];
+          const float gte = E::rr(s0), up = E::rr(s1);
+          ((uint16_t*)p.y)[o] = E::r(E::rr(gte * sigmoid(gte)) * up);
+        } else {
+          float val = s0;
+          if (p.bias) val += E::f(p.bias[n]);
+          if (p.res) val = E::rr(val) + E::f(p.res[o]);
+          if (p.out_f32) ((float*)p.y)[o] = val; else ((uint16_t*)p.y)[o] = E::r(val);
+        }
+      }
+    }
+  }
+}
+
 // ---- 17..80 rows (MT >= 2): the waves split N, the activations are shared through LDS (round 5) ------------------------------------
 // With the waves of a workgroup splitting K every wave fetches its own activation fragments from L2: MT / R bytes per weight byte,
 // 1.25x the weight stream at 80 rows -- and at MT = 5 only two stages fit the registers.  Measured in round 4
@@ -507,67 +575,207 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(const DecodeG
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
 
-  // ---- epilogue from registers: lane (l16 -> activation row, 4 q + v -> column of the tile) -------------------------------------------
-  const int tiles = p.swiglu ? R / 2 : R;
+  dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
+}
+
+// ---- MXVL_W_INT8: row-wise absmax int8 weights (bitsandbytes' Int8Params storage), 16-bit activations, rows 1..80 ------------------
+//   y[m][n] = epi( s[n] * fp32( sum_k float(CB[n][k]) * float(x[m][k]) ) ),   s[n] = ws[n] / 127
+// The wide kernel's decomposition at every row count (waves own their columns over the workgroup's K range, activations shared
+// through LDS, epilogue from registers), on chunks of 128 columns so that a weight row still arrives as whole 128-byte lines: the
+// weight image of a stage is byte for byte the one of the 16-bit kernels (16 rows x 128 bytes per tile, two DMA instructions, same
+// XOR swizzle), the activation image is two of theirs (columns 0..63 and 64..127 of the chunk, 4 MT one-kilobyte pieces).
+// One ds_read_b128 of the weight image is 16 codes of row l16: columns 16 u .. 16 u + 15 of the chunk, u = 4 j + q.  They are widened
+// in registers to two A operands (codes 0..7 and 8..15); the matching B operands are columns 16 u + 8 h .. + 7 of the activation
+// rows -- the MFMA only needs lane group q to hold the SAME eight k in A and B, so the order of k inside a chunk is free.
+// Int8 -> element conversion is exact (|code| <= 128 has 8 significant bits) and so is every product in fp32; the row scale is
+// applied to the fp32 sums (the planes of a K split hold s[n] * partial sum, mxvl_decode_rmsnorm folds them as before).
+// K % 128 == 64: the last chunk has one half.  Its DMA sources are pulled back inside the rows (weight units 4..7 re-read units
+// 0..3, the activation pieces of the second half re-read the first) and the j = 1 products are skipped.
+template <typename E> struct W8Cvt;
+template <> struct W8Cvt<EltBf16> {
+  // four codes (one word) -> four bf16 as two packed words: v_cvt_f32_ubyteN of (code + 128), - 128, keep the upper halves (the
+  // lower ones are zero: integers of at most 8 bits)
+  __host__ __device__ static inline void cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+    const uint32_t u = w ^ 0x80808080u;
+    const float f0 = (float)(u & 0xffu) - 128.0f, f1 = (float)((u >> 8) & 0xffu) - 128.0f;
+    const float f2 = (float)((u >> 16) & 0xffu) - 128.0f, f3 = (float)(u >> 24) - 128.0f;
+    lo = (__builtin_bit_cast(uint32_t, f0) >> 16) | (__builtin_bit_cast(uint32_t, f1) & 0xffff0000u);
+    hi = (__builtin_bit_cast(uint32_t, f2) >> 16) | (__builtin_bit_cast(uint32_t, f3) & 0xffff0000u);
+  }
+};
+template <> struct W8Cvt<EltF16> {
+  // fp16 0x6400 | b = 1024 + b for a byte b: (code + 128) goes into the mantissa, one packed subtraction of 1152 leaves the code
+  __host__ __device__ static inline void cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const uint32_t u = w ^ 0x80808080u;
+    const uint32_t a = 0x64006400u | (u & 0xffu) | ((u << 8) & 0x00ff0000u);
+    const uint32_t b = 0x64006400u | ((u >> 16) & 0xffu) | ((u >> 8) & 0x00ff0000u);
+    const h2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+    lo = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, a) - off);
+    hi = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, b) - off);
+  }
+};
+
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w8_kernel(const DecodeGemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char dg8_smem[];
+  constexpr int AHALF = MT * 2048, ACT = 2 * AHALF, WST = R * 2048, STAGE = ACT + NW * WST;
+  constexpr int AI = (4 * MT + NW - 1) / NW;           // activation DMA instructions per wave and stage
+  constexpr int OPS = 2 * R + AI;
+  static_assert(PF >= 2 && (PF - 1) * OPS <= 63, "vmcnt is a 6-bit field");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l16 = lane & 15, q = lane >> 4;
+  const int K = p.K, N = p.N;
+  const int cols_per_wave = (p.swiglu ? R / 2 : R) * 16;
+  const int n0 = (blockIdx.x * NW + wave) * cols_per_wave;       // this wave's first output column
+  const int rl = lane >> 3, ul = lane & 7;
+  const char* wsrc[R][2];
 #pragma unroll
-  for (int t = 0; t < (R > 1 ? R : 1); ++t) {
-    if (t >= tiles) break;
+  for (int r = 0; r < R; ++r) {
+    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
+    const char* base = (const char*)((p.swiglu && r >= R / 2) ? p.W2 : p.W);
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = mt * 16 + l16;
-      if (m >= p.rows) continue;
-      const int nq = n0 + t * 16 + 4 * q;
-      if ((N & 3) == 0 && nq + 3 < N) {             // the lane's four columns as one store (16 bytes of a plane, 8 of a 16-bit row)
-        const size_t o = (size_t)m * N + nq;
-        const dg_f32x4 s0 = acc[t][mt];
-        if (p.split_acc) {
-          *(dg_f32x4*)(p.split_acc + (size_t)blockIdx.y * p.rows * N + o) = s0;
-        } else if (p.swiglu) {
-          const dg_f32x4 s1 = acc[(t + R / 2) < R ? t + R / 2 : t][mt];
-          uint16_t h[4];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const float gte = E::rr(s0[v]), up = E::rr(s1[v]);
-            h[v] = E::r(E::rr(gte * sigmoid(gte)) * up);
-          }
-          *(uint2*)((uint16_t*)p.y + o) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-        } else {
-          float val[4] = {s0[0], s0[1], s0[2], s0[3]};
-          if (p.bias) {
-            const uint2 bw = *(const uint2*)(p.bias + nq);
-            val[0] += E::lo(bw.x); val[1] += E::hi(bw.x); val[2] += E::lo(bw.y); val[3] += E::hi(bw.y);
-          }
-          if (p.res) {
-            const uint2 rw = *(const uint2*)(p.res + o);
-            val[0] = E::rr(val[0]) + E::lo(rw.x); val[1] = E::rr(val[1]) + E::hi(rw.x);
-            val[2] = E::rr(val[2]) + E::lo(rw.y); val[3] = E::rr(val[3]) + E::hi(rw.y);
-          }
-          if (p.out_f32) *(dg_f32x4*)((float*)p.y + o) = dg_f32x4{val[0], val[1], val[2], val[3]};
-          else *(uint2*)((uint16_t*)p.y + o) = make_uint2((uint32_t)E::r(val[0]) | ((uint32_t)E::r(val[1]) << 16), (uint32_t)E::r(val[2]) | ((uint32_t)E::r(val[3]) << 16));
-        }
-        continue;
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int n = n0 + t * 16 + 4 * q + v;
-        if (n >= N) continue;
-        const float s0 = acc[t][mt][v];
-        const size_t o = (size_t)m * N + n;
-        if (p.split_acc) {
-          p.split_acc[(size_t)blockIdx.y * p.rows * N + o] = s0;
-        } else if (p.swiglu) {
-          const float s1 = acc[(t + R / 2) < R ? t + R / 2 : t][mt][v];
-          const float gte = E::rr(s0), up = E::rr(s1);
-          ((uint16_t*)p.y)[o] = E::r(E::rr(gte * sigmoid(gte)) * up);
-        } else {
-          float val = s0;
-          if (p.bias) val += E::f(p.bias[n]);
-          if (p.res) val = E::rr(val) + E::f(p.res[o]);
-          if (p.out_f32) ((float*)p.y)[o] = val; else ((uint16_t*)p.y)[o] = E::r(val);
-        }
-      }
+    for (int h = 0; h < 2; ++h) {
+      const int row = h * 8 + rl;
+      int n = n0 + t * 16 + row;
+      n = n < N ? n : N - 1;
+      wsrc[r][h] = base + (size_t)n * K + ((ul ^ dg_key(row)) << 4);
     }
   }
+  // bit 2 of a lane's source unit (ul ^ dg_key(row)) depends on bit 1 of the row only: the same for both DMA calls of a tile
+  const int wback = ((ul ^ dg_key(rl)) & 4) ? 64 : 0;
+  const char* asrc[AI];
+  unsigned adst[AI];
+  int aback[AI];
+#pragma unroll
+  for (int i = 0; i < AI; ++i) {
+    int a = wave + NW * i;
+    a = a < 4 * MT ? a : 4 * MT - 1;
+    const int half = a / (2 * MT), ap = a - half * 2 * MT;
+    const int row = ap * 8 + rl;                                   // row of the padded MT x 16 tile
+    const int m = row < p.rows ? row : p.rows - 1;
+    asrc[i] = (const char*)(p.x + (size_t)m * K) + half * 128 + ((ul ^ dg_key(row & 15)) << 4);
+    adst[i] = (unsigned)(half * AHALF + ap * 1024);
+    aback[i] = half * 128;
+  }
+  const int chunks = (K + 127) >> 7;
+  const bool half_tail = (K & 64) != 0;                            // the last chunk holds 64 columns
+  const int cpw = (chunks + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int c_begin = blockIdx.y * cpw;
+  const int c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
+  const int n_it = c_end - c_begin;
+
+  dg_f32x4 acc[R][MT];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[r][mt] = dg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dg8_smem;
+
+  // the walk over K staggered per workgroup, as in decode_gemm_wide_kernel
+  const int stag = n_it > 0 ? (int)((blockIdx.x * 5u) % (unsigned)n_it) : 0;
+  auto chunk_at = [&](int c) {
+    int j = c - c_begin + stag;
+    j = j >= n_it ? j - n_it : j;
+    const int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads
+    return cc < chunks ? cc : chunks - 1;
+  };
+  auto issue = [&](int slot, int c) {
+    const int cc = chunk_at(c);
+    const bool tail = half_tail && cc == chunks - 1;               // (uniform)
+    const unsigned sbase = lds0 + (unsigned)slot * STAGE;
+#pragma unroll
+    for (int i = 0; i < AI; ++i) {
+      unsigned keep;
+      const char* g = asrc[i] + ((long)cc * 256 - (tail ? aback[i] : 0));
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(sbase + adst[i])), "v"(g) : "memory", "scc");
+    }
+    const unsigned wdst = sbase + ACT + (unsigned)wave * WST;
+    const long woff = (long)cc * 128 - (tail ? wback : 0);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
+                   "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(wdst + r * 2048)), "v"(wsrc[r][0] + woff), "v"(wsrc[r][1] + woff) : "memory", "scc");
+    }
+  };
+  auto consume = [&](int slot, int c) {
+    const bool tail = half_tail && chunk_at(c) == chunks - 1;      // (uniform)
+    const char* act = dg8_smem + slot * STAGE;
+    const char* wt = act + ACT + wave * WST;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j == 1 && tail) break;
+      const int wunit = ((j * 4 + q) ^ dg_key(l16)) << 4;
+      dg_u32x4 cv[R][2];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
+        uint32_t o[8];
+        W8Cvt<E>::cvt4(av.x, o[0], o[1]);
+        W8Cvt<E>::cvt4(av.y, o[2], o[3]);
+        W8Cvt<E>::cvt4(av.z, o[4], o[5]);
+        W8Cvt<E>::cvt4(av.w, o[6], o[7]);
+        cv[r][0] = dg_u32x4{o[0], o[1], o[2], o[3]};
+        cv[r][1] = dg_u32x4{o[4], o[5], o[6], o[7]};
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int aunit = ((q * 2 + h) ^ dg_key(l16)) << 4;
+        dg_u32x4 bf[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(act + j * AHALF + (mt * 16 + l16) * 128 + aunit);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][h], bf[mt], acc[r][mt]);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+#pragma unroll
+  for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
+  int slot = 0, fill = PF - 1;
+  const int n_main = n_it - (PF - 1);                  // iterations that still have a stage to ask for
+  for (int i = 0; i < n_main; ++i) {
+    dg_wait_vm<(PF - 2) * OPS>();                      // stage i has landed (this wave's pieces); PF - 2 younger stages stay in flight
+    __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with the slot of stage i - 1
+    asm volatile("" ::: "memory");
+    issue(fill, c_begin + i + PF - 1);
+    consume(slot, c_begin + i);
+    slot = slot + 1 == PF ? 0 : slot + 1;
+    fill = fill + 1 == PF ? 0 : fill + 1;
+  }
+  const int i_tail = n_main > 0 ? n_main : 0;
+  dg_static_for<PF - 1>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    if (i_tail + t < n_it) {                            // (uniform)
+      dg_wait_vm<(PF - 2 - t) * OPS>();
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      consume(slot, c_begin + i_tail + t);
+      slot = slot + 1 == PF ? 0 : slot + 1;
+    }
+  });
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
+
+  // the row scales on the fp32 sums, then the epilogue of the wide kernel
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
+    const float* sp = (p.swiglu && r >= R / 2) ? p.ws2 : p.ws;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int n = n0 + t * 16 + 4 * q + v;
+      const float sc = n < N ? sp[n] / 127.0f : 0.0f;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[r][mt][v] *= sc;
+    }
+  }
+  dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
 }
 
 // RMSNorm of the activation rows ahead of a projection (Qwen2RMSNorm / LlamaRMSNorm, EMRRG/models/hybrid_decoder_layer.py:185-199):

@@ -104,8 +104,54 @@ static bool wide_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl)
   return pl.g >= g_wide_min_g;
 }
 
+// ---- MXVL_W_INT8 (decode_gemm_w8_kernel): one kernel at every row count -------------------------------------------------------------
+// ring depth: as many stages of (two activation half-tiles + NW x R weight tiles) as 150 KB of LDS hold, capped by vmcnt and at 8
+constexpr int w8_pf(int MT, int R, int NW) {
+  const int stage = MT * 4096 + NW * R * 2048, ops = 2 * R + (4 * MT + NW - 1) / NW;
+  int pf = (150 * 1024) / stage;
+  while (pf > 2 && (pf - 1) * ops > 63) --pf;
+  return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
+}
+constexpr int kW8Waves = 4;
+// The wide kernel's estimate with the weight bytes halved: a workgroup pulls 1 + 2 MT / (NW R) bytes per weight byte, the launch is
+// as long as its busiest CU.  (A starting point: the 16-bit kernels' model, not a measurement of half-size tiles.)
+static WidePlan w8_plan(int MT, const DecodeGemmArgs& a, int splits) {
+  WidePlan pl{kW8Waves, a.swiglu ? 2 : 1, 0};
+  double best = 1e30;
+  for (int r : {1, 2}) {            // (four tiles per wave leave the ring two or three stages at 33..80 rows and no registers for the widened operands)
+    if (a.swiglu && (r & 1)) continue;
+    const int cols = kW8Waves * (a.swiglu ? r / 2 : r) * 16;
+    const long g = (long)((a.N + cols - 1) / cols) * splits;
+    const double est = (1.0 + 2.0 * MT / (kW8Waves * r)) * (double)((g + 255) / 256) / (double)g;
+    if (est < best - 1e-12) { best = est; pl = WidePlan{kW8Waves, r, g}; }
+  }
+  return pl;
+}
+
+template <typename E, int MT, int R>
+static int launch_w8_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  constexpr int NW = kW8Waves, PF = w8_pf(MT, R, NW);
+  const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
+  const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
+  const size_t lds = (size_t)PF * (MT * 4096 + NW * R * 2048);
+  auto kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
+    return MXVL_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
+  return launch_status();
+}
+
+template <typename E, int MT>
+static int launch_w8(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  switch (w8_plan(MT, a, splits).r) {
+    case 2: return launch_w8_r<E, MT, 2>(a, splits, s);
+    default: return launch_w8_r<E, MT, 1>(a, splits, s);
+  }
+}
+
 template <typename E, int MT>
 static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  if (a.ws) return launch_w8<E, MT>(a, splits, s);
   {
     WidePlan pl;
     if (wide_plan(MT, a, splits, pl)) {
@@ -166,7 +212,7 @@ int decode_gemm_dispatch(const mxvl_gemv_desc* d, hipStream_t s) {
   int splits = 1;
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
-  return decode_dtype(d->dtype) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
+  return decode_dtype(d->dtype & ~MXVL_W_INT8) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
 }
 
 // the wide kernel's ring depth for a plan, as launch_wide picks it
@@ -183,6 +229,11 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
   const int MT = (a.rows + 15) / 16 > 5 ? 5 : (a.rows + 15) / 16;
+  if (a.ws) {                       // MXVL_W_INT8: out[0] = 3, then waves, tiles per wave, ring stages, workgroups of decode_gemm_w8_kernel
+    const WidePlan w = w8_plan(MT, a, splits);
+    out[0] = 3; out[1] = w.nw; out[2] = w.r; out[3] = w8_pf(MT, w.r, kW8Waves); out[4] = (int32_t)w.g;
+    return MXVL_OK;
+  }
   WidePlan pl;
   const bool wide = wide_plan(MT, a, splits, pl);
   out[0] = wide ? 1 : 0;
@@ -195,8 +246,11 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
 
 // argument checks of mxvl_decode_gemv + the kernel-side argument block (nothing is launched here)
 static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& splits) {
-  if (!decode_dtype_ok(d->dtype)) return MXVL_ERR_DTYPE;
+  if (!decode_dtype_ok(d->dtype & ~MXVL_W_INT8)) return MXVL_ERR_DTYPE;
+  const bool w8 = (d->dtype & MXVL_W_INT8) != 0;            // w_scale / w2_scale exist in the caller's struct only behind this flag
+  if (w8 && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
+  if (w8 && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no int8 form of these
   if (d->K % 8 != 0) return MXVL_ERR_UNSUPPORTED;                      // 16-byte fragments
   if (d->swiglu && (!d->W2 || d->out_f32)) return MXVL_ERR_UNSUPPORTED;
   // RMSNorm fused into the projection (ABI v8): the LDS-DMA kernel only (K % 64 == 0); elsewhere rows come from mxvl_decode_rmsnorm
@@ -208,6 +262,8 @@ static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& spl
   a.split_acc = (float*)d->split_acc;
   a.g = (const uint16_t*)d->norm_weight; a.eps = d->eps;
   a.g_scale = 1.0f; a.g_inv = 1.0f;
+  a.ws = w8 ? (const float*)d->w_scale : nullptr;
+  a.ws2 = (w8 && d->swiglu) ? (const float*)d->w2_scale : nullptr;
   if (d->norm_weight && d->norm_gain_scale != 0.0f) {
     int e = 0;
     const float m = frexpf(d->norm_gain_scale, &e);

@@ -11,8 +11,11 @@ Differences, all at the edges of the hot path:
     pretrain_engine.PretrainEngine / the caller's;
   * the LLM is report_decoder.ReportDecoder (HF key names; HIP decode step) built from an HF `config.json` +
     safetensors directory, or injected; tokenizers are injected or loaded from a LOCAL directory -- nothing is fetched;
-  * PEFT-LoRA wrappers (`vis_use_lora`, `llm_use_lora`) and 8-bit loading (`low_resource`) are not built: they wrap
-    third-party modules outside the path and raise NotImplementedError when requested.
+  * `low_resource` (the reference loads the frozen LLM with load_in_8bit=True, MambaXrayVL_DownStream.py:82-92) stores the layer
+    projections of the LLM as row-wise absmax int8 -- bitsandbytes' weight format -- served by this build's own kernels
+    (ReportDecoder.quantize_int8_, int8_linear.py; W8A16: activations stay 16-bit, no bitsandbytes needed);
+  * PEFT-LoRA wrappers (`vis_use_lora`, `llm_use_lora`) are not built: they wrap third-party modules outside the path and raise
+    NotImplementedError when requested.
 """
 from __future__ import annotations
 
@@ -41,9 +44,9 @@ def _get(args, name, default=None):
     return getattr(args, name, default)
 
 
-def build_report_decoder(source=None, dtype=torch.float16, **overrides):
+def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
-    a local HF checkpoint directory (config.json + *.safetensors)."""
+    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading."""
     sd = None
     if source is None or source == "llama2-7b":
         cfg = dict(LLAMA2_7B)
@@ -69,6 +72,8 @@ def build_report_decoder(source=None, dtype=torch.float16, **overrides):
         if "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
             sd["lm_head.weight"] = sd["model.embed_tokens.weight"]          # tied embeddings
         llm.load_hf_state_dict(sd)
+    if low_resource:
+        llm.quantize_int8_()
     return llm
 
 
@@ -81,9 +86,9 @@ def _load_tokenizer(path):
 
 
 def _reject_unbuilt(args):
-    for flag in ("vis_use_lora", "llm_use_lora", "low_resource"):
+    for flag in ("vis_use_lora", "llm_use_lora"):
         if _get(args, flag, False):
-            raise NotImplementedError(f"args.{flag}: PEFT / bitsandbytes wrappers are outside the MI355X path and not built")
+            raise NotImplementedError(f"args.{flag}: PEFT wrappers are outside the MI355X path and not built")
 
 
 def _build_encoder(args, large):
@@ -145,6 +150,8 @@ class MambaXrayVLDownStream(nn.Module):
                           cross_attn_implementation=_get(args, "cross_attn_implementation", "text-only-vanilla"),
                           cross_attn_gating_type=_get(args, "cross_attn_gating_type", "channel-wise-dynamic-sigmoid"))
         self.llama_model = llm if llm is not None else build_report_decoder(source, **hybrid)
+        if _get(args, "low_resource", False) and not self.llama_model.is_int8():
+            self.llama_model.quantize_int8_()
         self.llama_tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(_get(args, "llama_model"))
         self.llama_tokenizer.pad_token_id = 0
         if iu:

@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
+from .int8_linear import DequantScratch, Int8Linear
 
 
 class KVCache:
@@ -566,6 +567,8 @@ class _KernelStepper(_Stepper):
         mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and cfg.hidden_size <= 16384
         fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
             (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
+        if model.is_int8() and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
+            return False         # int8 projections (MXVL_W_INT8): K % 64 == 0 on the one kernel they have
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
@@ -592,13 +595,16 @@ class _KernelStepper(_Stepper):
         # rows > 8 need the matrix-core projections; below that they are still ~3 % faster per token than the GEMV kernels wherever
         # their LDS-DMA form applies (K % 64 == 0: every real decoder width) -- 5.2-6.2 TB/s against 4.4-5 of the weight stream
         self.batched = rows > 8 or (self.hidden % 64 == 0 and self.inter % 64 == 0 and (self.H * self.D) % 64 == 0)
+        # int8 layer projections (ReportDecoder.quantize_int8_): the matrix-core kernel at every row count, explicit norm launches
+        # ("split" mode) -- there is no int8 form of the fused RMSNorm; lm_head and the embedding stay 16-bit
+        self.int8 = model.is_int8()
         # rows <= 8: RMSNorm fused into the MFMA projection that consumes the rows (csrc/decode_gemm.h NORM, K % 64 == 0): no
         # mxvl_decode_rmsnorm launches (65 of a token's 229), o_proj / down_proj add their residual in their own epilogue instead of
         # splitting K.  Measured in one call (profiles/r05_decode_norm_ab.txt): batch 1 x beam 3 332.7 -> 361.1 tok/s, Qwen-1.8B 1 x 5
         # 755.7 -> 809.6; at 18 / 48 / 80 rows the unsplit o_proj / down_proj (256 workgroups of ONE 16-column tile: activation
         # re-reads = rows / 16 x the weight bytes) cost more than the launches save (1638 -> 1575, 2894 -> 2656, 2212 -> 1852
         # tok/s): those keep the K-split sums folded by an explicit norm launch ("split"; norm_mode is the A/B switch of bench.py)
-        self.fused_norm = self.batched and self.norm_mode == "fused" and rows <= 8 and self.hidden % 64 == 0 and self.hidden >= 256 \
+        self.fused_norm = self.batched and not self.int8 and self.norm_mode == "fused" and rows <= 8 and self.hidden % 64 == 0 and self.hidden >= 256 \
             and self.inter % 64 == 0 and self.inter >= 256 and (self.H * self.D) % 64 == 0 and self.H * self.D >= 256
         # fp16 only (bf16 has fp32's exponent range): a power-of-two scale per RMSNorm gain, 2^-ceil(log2 max|g|), so that the fused
         # projection's dtype(g * s * x) can neither overflow nor sink into subnormals where the modules' dtype(dtype(x * rstd) * g) --
@@ -708,9 +714,12 @@ class _KernelStepper(_Stepper):
         _abi.launch("mxvl_decode_rmsnorm", n, device=self.x.device)
         return self.xn
 
-    def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0):
+    def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0, scale=None, scale2=None):
         d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
+        if scale is not None:                   # W / W2 are int8 codes, scale / scale2 their row-wise absmax (SCB)
+            d.dtype |= _abi.MXVL_W_INT8
+            d.w_scale, d.w2_scale = scale.data_ptr(), _abi.ptr(scale2)
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
         d.x, d.norm_weight, d.W = x.data_ptr(), _abi.ptr(norm), W.data_ptr()
         if norm is not None and self._gain_scale:
@@ -774,7 +783,7 @@ class _KernelStepper(_Stepper):
             if batched:
                 xin = self._rmsnorm(self.x, ln1.weight, ln1.variance_epsilon, self.hidden,
                                     fold_res=self.x2 if i else None, x_out=self.x, splits=sd)      # layer i - 1's down_proj sums + residual
-                self._gemv(xin, at.qkv_weight, self.qkv, self.hidden, self.qkv.shape[1], bias=at.qkv_bias)
+                self._gemv(xin, at.qkv_weight, self.qkv, self.hidden, self.qkv.shape[1], bias=at.qkv_bias, scale=getattr(at, "qkv_scale", None))
             else:
                 self._gemv(self.x, at.qkv_weight, self.qkv, self.hidden, self.qkv.shape[1], norm=ln1.weight, eps=ln1.variance_epsilon,
                            bias=at.qkv_bias)
@@ -786,10 +795,12 @@ class _KernelStepper(_Stepper):
                 self._cross_attn(i)
                 att = self.att2
             if batched:
-                self._gemv(att, at.o_proj.weight, None, self.H * self.D, self.hidden, split=so)
+                sc = (lambda lin: lin.SCB) if self.int8 else (lambda lin: None)
+                self._gemv(att, at.o_proj.weight, None, self.H * self.D, self.hidden, split=so, scale=sc(at.o_proj))
                 xin = self._rmsnorm(None, ln2.weight, ln2.variance_epsilon, self.hidden, fold_res=self.x, x_out=self.x2, splits=so)
-                self._gemv(xin, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter, W2=layer.mlp.up_proj.weight)
-                self._gemv(self.act, layer.mlp.down_proj.weight, None, self.inter, self.hidden, split=sd)
+                self._gemv(xin, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter, W2=layer.mlp.up_proj.weight,
+                           scale=sc(layer.mlp.gate_proj), scale2=sc(layer.mlp.up_proj))
+                self._gemv(self.act, layer.mlp.down_proj.weight, None, self.inter, self.hidden, split=sd, scale=sc(layer.mlp.down_proj))
             else:
                 self._gemv(att, at.o_proj.weight, self.x2, self.H * self.D, self.hidden, res=self.x)
                 self._gemv(self.x2, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter,
@@ -868,9 +879,43 @@ class ReportDecoder(nn.Module):
                 W = torch.cat([at.q_proj.weight, at.k_proj.weight, at.v_proj.weight], dim=0).contiguous()
                 b = torch.cat([at.q_proj.bias, at.k_proj.bias, at.v_proj.bias], dim=0).contiguous()
                 nq, nk = at.q_proj.weight.shape[0], at.k_proj.weight.shape[0]
-                at.q_proj.weight.data, at.k_proj.weight.data, at.v_proj.weight.data = W[:nq], W[nq:nq + nk], W[nq + nk:]
-                at.q_proj.bias.data, at.k_proj.bias.data, at.v_proj.bias.data = b[:nq], b[nq:nq + nk], b[nq + nk:]
+                if isinstance(at.q_proj, Int8Linear):
+                    # int8: the codes' rows and the per-row scales concatenate exactly; the buffers become views of the fused ones
+                    # (assigned, not .data: the unfused storage is released, no second copy of the bytes)
+                    S = torch.cat([at.q_proj.SCB, at.k_proj.SCB, at.v_proj.SCB], dim=0).contiguous()
+                    for lin, lo, hi in ((at.q_proj, 0, nq), (at.k_proj, nq, nq + nk), (at.v_proj, nq + nk, W.shape[0])):
+                        lin.weight, lin.SCB, lin.bias = W[lo:hi], S[lo:hi], b[lo:hi]
+                    at.qkv_scale = S
+                else:
+                    at.q_proj.weight.data, at.k_proj.weight.data, at.v_proj.weight.data = W[:nq], W[nq:nq + nk], W[nq + nk:]
+                    at.q_proj.bias.data, at.k_proj.bias.data, at.v_proj.bias.data = b[:nq], b[nq:nq + nk], b[nq + nk:]
+                    at.qkv_scale = None
             at.qkv_weight, at.qkv_bias = W, b
+
+    _INT8_TARGETS = (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj")))
+
+    def is_int8(self):
+        return isinstance(self.model.layers[0].mlp.down_proj, Int8Linear)
+
+    def quantize_int8_(self):
+        """The reference's `low_resource` (load_in_8bit=True): q/k/v/o_proj and gate/up/down_proj of every layer become Int8Linear
+        (row-wise absmax int8, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head (HF's 8-bit loader
+        skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The layers share
+        one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly."""
+        scratch = DequantScratch()
+        for layer in self.model.layers:
+            at = layer.self_attn
+            at.qkv_weight = at.qkv_bias = at.qkv_scale = None           # a fused 16-bit buffer would keep the old bytes alive
+            for owner, names in self._INT8_TARGETS:
+                mod = getattr(layer, owner)
+                for name in names:
+                    lin = getattr(mod, name)
+                    if not isinstance(lin, Int8Linear):
+                        setattr(mod, name, Int8Linear.from_linear(lin, scratch))
+                    scratch.reserve(lin.in_features * lin.out_features)        # the buffer is sized once, for the largest weight
+        self.__dict__.pop("_steppers", None)                            # captured steps name the old weights
+        self.__dict__.pop("_autocast_shadows", None)
+        return self
 
     def get_input_embeddings(self):
         return self.model.embed_tokens
