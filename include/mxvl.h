@@ -227,6 +227,20 @@ typedef struct mxvl_conv1d_bwd_desc {
  * caller built against the shorter struct never sets it -- its descriptor stays valid as it is (the argument of the `reserved0`
  * reuse in mxvl_beam_desc / mxvl_sample_desc). */
 #define MXVL_W_INT8 0x100
+/* MX-FP4 weights (W4A16): `dtype | MXVL_W_MXFP4`, OCP microscaling FP4.  W / W2 are then (N, K / 2) bytes of packed E2M1 codes (a
+ * nibble is sign | 2 exponent bits | 1 mantissa bit: 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives; the element of even k in the LOW
+ * nibble), w_scale / w2_scale the (N, K / 32) E8M0 bytes (bias 127), 4-byte aligned; x, bias, residual, y stay 16-bit:
+ *   y[m][n] = epi( fp32( sum_k v[n][k] * 2^(e[n][k / 32] - 127) * x[m][k] ) )
+ * Every E2M1 value times a power of two is exact in bf16, and in fp16 for e - 127 in [-15, 13]: inside that range the code -> element
+ * conversion and every product are exact, only the order of the fp32 sum and the final rounding are the kernel's.  Outside it
+ * (fp16; bf16 below its normal range) an element is what v_cvt_scalef32_pk_{f16,bf16}_fp4 gives; e = 255 (E8M0's NaN) is not handled.
+ * epi, shapes and error codes as MXVL_W_INT8: + bias, + residual, swiglu, split_acc planes; rows 1..80, K % 64 == 0, K >= 64,
+ * norm_weight == NULL, out_f32 == 0 (MXVL_ERR_SHAPE otherwise, before any launch); a NULL w_scale (w2_scale with swiglu) is
+ * MXVL_ERR_NULL; both weight flags set is MXVL_ERR_DTYPE.  One kernel serves every row count and k_splits value (csrc/decode_gemm.h
+ * decode_gemm_w4_kernel); it keeps its rows' scales in LDS, so the K range of one workgroup (K / k_splits, rounded up to 256) is at
+ * most 24320 columns, 12032 with swiglu: MXVL_ERR_UNSUPPORTED beyond.
+ * As with MXVL_W_INT8 the flag is one high bit of `dtype` and w_scale / w2_scale are read only behind it. */
+#define MXVL_W_MXFP4 0x200
 typedef struct mxvl_gemv_desc {
   int32_t rows, K, N;
   int32_t swiglu, out_f32;
@@ -252,7 +266,8 @@ typedef struct mxvl_gemv_desc {
                                fp16 (|x| <= 65504 already), and a layer of uniformly small gains (Llama's first input_layernorm: 1e-2 ..
                                1e-3) no longer pushes g * x into fp16's subnormals.  The modules normalise in fp32 FIRST (x * rstd is O(1)),
                                so they never had either failure; bf16 has fp32's exponent range and does not need it. */
-  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8 only (never read otherwise): (N) fp32 row-wise absmax of W / W2; w2_scale with swiglu */
+  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8 or MXVL_W_MXFP4 only (never read otherwise).  INT8: (N) fp32 row-wise absmax of W / W2;
+                                       MXFP4: (N, K / 32) E8M0 block scales of W / W2; w2_scale with swiglu */
 } mxvl_gemv_desc;
 
 /*
@@ -360,7 +375,8 @@ typedef struct mxvl_rmsnorm_desc {
 int mxvl_set_decode_gemm_wide(int on);
 /* Diagnostic (ABI v8): which kernel mxvl_decode_gemv would launch for a descriptor -- the dispatch as a pure function, nothing is launched
  * and no GPU is needed.  out[0] = 2 the per-row GEMV kernel (<= 8 rows, k_splits == 0), 1 = decode_gemm_wide_kernel, 0 = the K-split
- * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count); for 1 and 3: out[1] waves per
+ * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count), 4 = decode_gemm_w4_kernel (MXVL_W_MXFP4,
+ * likewise); for 1, 3 and 4: out[1] waves per
  * workgroup, out[2] weight tiles per wave, out[3] LDS ring stages, out[4] workgroups.  Same argument checks and error codes as
  * mxvl_decode_gemv. */
 int mxvl_decode_gemm_plan(const mxvl_gemv_desc *desc, int32_t out[5]);

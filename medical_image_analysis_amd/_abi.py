@@ -19,6 +19,7 @@ ABI_VERSION = 13
 
 MXVL_F32, MXVL_BF16, MXVL_F16 = 0, 1, 2
 MXVL_W_INT8 = 0x100      # mxvl_gemv_desc.dtype flag: W / W2 are int8 codes, w_scale / w2_scale their row-wise absmax
+MXVL_W_MXFP4 = 0x200     # mxvl_gemv_desc.dtype flag: W / W2 are packed E2M1 codes (N, K / 2), w_scale / w2_scale their E8M0 block scales (N, K / 32)
 SCAN_DELTA_SOFTPLUS = 1
 SCAN_OUT_F32 = 2          # out / dout fp32 whatever io_dtype is (the oflex i16o32 mode)
 SCAN_FOLD_BATCH = 4       # the batch folded into the sequence (short rows; ask mxvl_scan_fold_ok)

@@ -39,7 +39,9 @@ struct DecodeGemmArgs {
   float eps;
   float g_scale, g_inv;   // NORM: power-of-two scale on the gain (mxvl_gemv_desc.norm_gain_scale) and its reciprocal, folded into rstd
   const float *ws, *ws2;  // MXVL_W_INT8: W / W2 are (N, K) int8 codes, ws / ws2 (N) their row-wise absmax (decode_gemm_w8_kernel); else NULL
+  const uint8_t *wx, *wx2; // MXVL_W_MXFP4: W / W2 are (N, K / 2) packed E2M1 codes, wx / wx2 (N, K / 32) their E8M0 block scales (decode_gemm_w4_kernel); else NULL
 };
+constexpr int kWeightFlags = MXVL_W_INT8 | MXVL_W_MXFP4;   // the weight-format bits of mxvl_gemv_desc.dtype
 
 // Reduction over the waves' K split + the epilogue of mxvl_decode_gemv, one round per output tile (SwiGLU: per gate / up pair).
 // acc[r][mt] is lane (col = l%16 -> activation row, 4 * (l/16) + v -> weight row) of the 16x16 tile (weight tile r, row tile mt).
@@ -775,6 +777,242 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_w8_kernel(const DecodeGem
       for (int mt = 0; mt < MT; ++mt) acc[r][mt][v] *= sc;
     }
   }
+  dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
+}
+
+// ---- MXVL_W_MXFP4: OCP microscaling FP4 weights (E2M1 codes, one E8M0 scale per 32 along K), 16-bit activations, rows 1..80 ---------
+//   y[m][n] = epi( fp32( sum_k v[n][k] * 2^(e[n][k / 32] - 127) * x[m][k] ) )
+// W / W2 are (N, K / 2) bytes, the element of even k in the low nibble; wx / wx2 the (N, K / 32) E8M0 bytes.
+// decode_gemm_w8_kernel's decomposition on chunks of 256 columns, so that a weight row still arrives as whole 128-byte lines: the
+// weight image of a stage is byte for byte the one of the other kernels (16 rows x 128 bytes per tile, two DMA instructions, same
+// XOR swizzle), the activation image is FOUR of the 16-bit kernels' (columns 64 a .. 64 a + 63 of the chunk, 8 MT one-kilobyte pieces).
+// One ds_read_b128 of the weight image is 32 codes of row l16 -- columns 32 u .. 32 u + 31 of the chunk, u = 4 j + q: exactly ONE scale
+// block, private to the lane.  Its four words become four A operands: v_cvt_scalef32_pk_{bf16,f16}_fp4 turns one byte (two codes)
+// into one packed word and multiplies by the block's 2^(e - 127) on the way, one VALU instruction per weight byte and nothing else.
+// Every E2M1 value times a power of two is exact in bf16 (and in fp16 inside its range: e - 127 in [-15, 13], the quantiser's
+// check), so conversion and products are exact; the order of the fp32 sum and the final rounding are the kernel's.
+// The B operand of word i is columns 32 u + 8 i .. + 7 of the activation rows (the MFMA only needs lane group q to hold the SAME
+// eight k in A and B): one K = 32 step covers eight columns of each of four scale blocks.
+// Scales: (N, K / 32) bytes have rows of 2-byte alignment only, so they do not ride the DMA ring.  Each wave copies the scale bytes
+// of ITS rows over the workgroup's whole K range into LDS once, behind the ring's prologue (plain loads of 4 bytes, 2 where K % 128
+// != 0), pitch = range + 4 bytes (an odd count of words: the 16 rows of a read fall on 16 banks), bytes past the row set to 127 (= 1.0).
+// K % 256 != 0: the last chunk has vq = (K / 64) % 4 quarters.  DMA sources past the row are pulled back inside it (weight units
+// >= 2 vq re-read unit 0, activation quarters >= vq re-read quarter 0); lanes whose block lies past the row convert zero codes
+// (0 * a real activation = 0), a j whose four blocks all do is skipped.
+template <typename E> struct W4Cvt;
+template <> struct W4Cvt<EltBf16> {
+  template <int B> __device__ static inline uint32_t cvt2(uint32_t w, float s) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, B));
+  }
+};
+template <> struct W4Cvt<EltF16> {
+  template <int B> __device__ static inline uint32_t cvt2(uint32_t w, float s) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, B));
+  }
+};
+// bytes of LDS per scale row for a K range of `cpw` chunks (host and kernel agree through this one function)
+__host__ __device__ constexpr int w4_scale_pitch(int cpw) { return cpw * 8 + 4; }
+
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char dg4_smem[];
+  constexpr int AQ = MT * 2048, ACT = 4 * AQ, WST = R * 2048, STAGE = ACT + NW * WST;
+  constexpr int AI = (8 * MT + NW - 1) / NW;           // activation DMA instructions per wave and stage
+  constexpr int OPS = 2 * R + AI;
+  static_assert(PF >= 2 && (PF - 1) * OPS <= 63, "vmcnt is a 6-bit field");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l16 = lane & 15, q = lane >> 4;
+  const int K = p.K, N = p.N;
+  const int KB = K >> 1, KS = K >> 5;                  // bytes of a weight row, of a scale row
+  const int cols_per_wave = (p.swiglu ? R / 2 : R) * 16;
+  const int n0 = (blockIdx.x * NW + wave) * cols_per_wave;       // this wave's first output column
+  const int rl = lane >> 3, ul = lane & 7;
+  const int vq = (K >> 6) & 3;                         // quarters of the last chunk; 0: it is whole
+  const char* wsrc[R][2];
+  int wback[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int su = ul ^ dg_key(h * 8 + rl);
+    wback[h] = su >= 2 * vq ? su << 4 : 0;
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
+    const char* base = (const char*)((p.swiglu && r >= R / 2) ? p.W2 : p.W);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = h * 8 + rl;
+      int n = n0 + t * 16 + row;
+      n = n < N ? n : N - 1;
+      wsrc[r][h] = base + (size_t)n * KB + ((ul ^ dg_key(row)) << 4);
+    }
+  }
+  const char* asrc[AI];
+  unsigned adst[AI];
+  int aback[AI];
+#pragma unroll
+  for (int i = 0; i < AI; ++i) {
+    int a = wave + NW * i;
+    a = a < 8 * MT ? a : 8 * MT - 1;
+    const int quarter = a / (2 * MT), ap = a - quarter * 2 * MT;
+    const int row = ap * 8 + rl;                                   // row of the padded MT x 16 tile
+    const int m = row < p.rows ? row : p.rows - 1;
+    asrc[i] = (const char*)(p.x + (size_t)m * K) + quarter * 128 + ((ul ^ dg_key(row & 15)) << 4);
+    adst[i] = (unsigned)(quarter * AQ + ap * 1024);
+    aback[i] = quarter >= vq ? quarter * 128 : 0;
+  }
+  const int chunks = (K + 255) >> 8;
+  const int cpw = (chunks + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int c_begin = blockIdx.y * cpw;
+  const int c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
+  const int n_it = c_end - c_begin;
+  const int pitch = w4_scale_pitch(cpw);
+  char* const sc_l = dg4_smem + PF * STAGE + wave * (R * 16 * pitch);
+
+  dg_f32x4 acc[R][MT];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[r][mt] = dg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dg4_smem;
+
+  // the walk over K staggered per workgroup, as in decode_gemm_wide_kernel
+  const int stag = n_it > 0 ? (int)((blockIdx.x * 5u) % (unsigned)n_it) : 0;
+  auto chunk_at = [&](int c) {
+    int j = c - c_begin + stag;
+    j = j >= n_it ? j - n_it : j;
+    const int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads
+    return cc < chunks ? cc : chunks - 1;
+  };
+  auto issue = [&](int slot, int c) {
+    const int cc = chunk_at(c);
+    const bool tail = vq != 0 && cc == chunks - 1;                 // (uniform)
+    const unsigned sbase = lds0 + (unsigned)slot * STAGE;
+#pragma unroll
+    for (int i = 0; i < AI; ++i) {
+      unsigned keep;
+      const char* g = asrc[i] + ((long)cc * 512 - (tail ? aback[i] : 0));
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(sbase + adst[i])), "v"(g) : "memory", "scc");
+    }
+    const unsigned wdst = sbase + ACT + (unsigned)wave * WST;
+    const long woff0 = (long)cc * 128 - (tail ? wback[0] : 0), woff1 = (long)cc * 128 - (tail ? wback[1] : 0);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
+                   "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(wdst + r * 2048)), "v"(wsrc[r][0] + woff0), "v"(wsrc[r][1] + woff1) : "memory", "scc");
+    }
+  };
+  auto consume = [&](int slot, int c) {
+    const int cc = chunk_at(c);
+    const bool tail = vq != 0 && cc == chunks - 1;                 // (uniform)
+    const char* act = dg4_smem + slot * STAGE;
+    const char* wt = act + ACT + wave * WST;
+    const char* sc = sc_l + (cc - c_begin) * 8 + l16 * pitch;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (tail && 2 * j >= vq) break;                              // blocks 4 j .. 4 j + 3 all lie past the row
+      const int u = 4 * j + q;
+      const bool dead = tail && u >= 2 * vq;                       // this lane's block lies past the row
+      const int wunit = (u ^ dg_key(l16)) << 4;
+      dg_u32x4 cv[R][4];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
+        const uint32_t e = *(const uint8_t*)(sc + r * 16 * pitch + u);
+        const float s = __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);      // 2^(e - 127); e = 0 is fp32's subnormal 2^-127
+        if (dead) av = dg_u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          cv[r][i] = dg_u32x4{W4Cvt<E>::template cvt2<0>(av[i], s), W4Cvt<E>::template cvt2<1>(av[i], s),
+                              W4Cvt<E>::template cvt2<2>(av[i], s), W4Cvt<E>::template cvt2<3>(av[i], s)};
+      }
+      const char* aq = act + (2 * j + (q >> 1)) * AQ + l16 * 128;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int aunit = ((4 * (q & 1) + i) ^ dg_key(l16)) << 4;
+        dg_u32x4 bf[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(aq + mt * 2048 + aunit);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][i], bf[mt], acc[r][mt]);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+#pragma unroll
+  for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
+
+  // this wave's scale bytes over the workgroup's K range: 4 rows x 16 lanes per pass.  (The loads' results are waited for with
+  // vmcnt(0), i.e. together with the ring's prologue, which the first iteration needs anyway.)
+  {
+    const int sbeg = c_begin * 8, sbytes = n_it * 8;
+    auto stage_scales = [&](auto unit) {
+      typedef decltype(unit) U;
+      constexpr int PASSES = R * 4, CB = 4, US = (int)sizeof(U);
+      const int upr = sbytes / US;                       // units per row; <= 0: this workgroup has no chunk
+      const int last = KS - sbeg - US;                   // the last unit inside the row (>= 0 whenever upr > 0)
+      const uint8_t* sp[PASSES];
+#pragma unroll
+      for (int ps = 0; ps < PASSES; ++ps) {
+        const int row = ps * 4 + (lane >> 4), r = row >> 4;
+        const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
+        int n = n0 + t * 16 + (row & 15);
+        n = n < N ? n : N - 1;
+        sp[ps] = ((p.swiglu && r >= R / 2) ? p.wx2 : p.wx) + (size_t)n * KS + sbeg;
+      }
+      // PASSES x CB loads in flight per wait (all of them up to a K range of 8192 columns): addresses clamped into the row instead
+      // of branches, so that the loads issue back to back
+      for (int cb = 0; cb < upr; cb += 16 * CB) {
+        U v[PASSES][CB];
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps)
+#pragma unroll
+          for (int k = 0; k < CB; ++k) {
+            const int b = (cb + (lane & 15) + 16 * k) * US;
+            v[ps][k] = *(const U*)(sp[ps] + (b < last ? b : last));
+          }
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps)
+#pragma unroll
+          for (int k = 0; k < CB; ++k) {
+            const int c = cb + (lane & 15) + 16 * k, b = c * US;
+            if (c < upr) *(U*)(sc_l + (ps * 4 + (lane >> 4)) * pitch + b) = b <= last ? v[ps][k] : (U)0x7f7f7f7fu;
+          }
+      }
+    };
+    if ((KS & 3) == 0) stage_scales(uint32_t{0}); else stage_scales(uint16_t{0});
+  }
+
+  int slot = 0, fill = PF - 1;
+  const int n_main = n_it - (PF - 1);                  // iterations that still have a stage to ask for
+  for (int i = 0; i < n_main; ++i) {
+    dg_wait_vm<(PF - 2) * OPS>();                      // stage i has landed (this wave's pieces); PF - 2 younger stages stay in flight
+    __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with the slot of stage i - 1
+    asm volatile("" ::: "memory");
+    issue(fill, c_begin + i + PF - 1);
+    consume(slot, c_begin + i);
+    slot = slot + 1 == PF ? 0 : slot + 1;
+    fill = fill + 1 == PF ? 0 : fill + 1;
+  }
+  const int i_tail = n_main > 0 ? n_main : 0;
+  dg_static_for<PF - 1>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    if (i_tail + t < n_it) {                            // (uniform)
+      dg_wait_vm<(PF - 2 - t) * OPS>();
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      consume(slot, c_begin + i_tail + t);
+      slot = slot + 1 == PF ? 0 : slot + 1;
+    }
+  });
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
+
   dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
 }
 

@@ -149,9 +149,57 @@ static int launch_w8(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   }
 }
 
+// ---- MXVL_W_MXFP4 (decode_gemm_w4_kernel): one kernel at every row count ------------------------------------------------------------
+// LDS: the ring gets 112 KB (stages of four activation quarter-tiles + NW x R weight tiles), the waves' scale rows up to 48 KB
+// (Llama-7B's K = 11008 unsplit at two tiles per wave needs 43.5).
+constexpr int kW4Waves = 4, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
+constexpr int w4_pf(int MT, int R, int NW) {
+  const int stage = MT * 8192 + NW * R * 2048, ops = 2 * R + (8 * MT + NW - 1) / NW;
+  int pf = kW4RingBytes / stage;
+  while (pf > 2 && (pf - 1) * ops > 63) --pf;
+  return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
+}
+static int w4_cpw(const DecodeGemmArgs& a, int splits) { return ((a.K + 255) / 256 + splits - 1) / splits; }
+static bool w4_fits(const DecodeGemmArgs& a, int splits, int r) { return kW4Waves * r * 16 * w4_scale_pitch(w4_cpw(a, splits)) <= kW4ScaleBytes; }
+// w8_plan's estimate with the weight bytes halved again: a workgroup pulls 1 + 4 MT / (NW R) bytes per weight byte.  Two tiles per
+// wave need the K range of a workgroup to be at most 12032 columns (the scale rows' share of LDS), one tile 24320.
+static bool w4_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
+  pl = WidePlan{kW4Waves, 0, 0};
+  double best = 1e30;
+  for (int r : {1, 2}) {
+    if ((a.swiglu && (r & 1)) || !w4_fits(a, splits, r)) continue;
+    const int cols = kW4Waves * (a.swiglu ? r / 2 : r) * 16;
+    const long g = (long)((a.N + cols - 1) / cols) * splits;
+    const double est = (1.0 + 4.0 * MT / (kW4Waves * r)) * (double)((g + 255) / 256) / (double)g;
+    if (est < best - 1e-12) { best = est; pl = WidePlan{kW4Waves, r, g}; }
+  }
+  return pl.r != 0;
+}
+
+template <typename E, int MT, int R>
+static int launch_w4_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  constexpr int NW = kW4Waves, PF = w4_pf(MT, R, NW);
+  const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
+  const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
+  const size_t lds = (size_t)PF * (MT * 8192 + NW * R * 2048) + (size_t)NW * R * 16 * w4_scale_pitch(w4_cpw(a, splits));
+  auto kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
+    return MXVL_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
+  return launch_status();
+}
+
+template <typename E, int MT>
+static int launch_w4(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  WidePlan pl;
+  if (!w4_plan(MT, a, splits, pl)) return MXVL_ERR_UNSUPPORTED;
+  return pl.r == 2 ? launch_w4_r<E, MT, 2>(a, splits, s) : launch_w4_r<E, MT, 1>(a, splits, s);
+}
+
 template <typename E, int MT>
 static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   if (a.ws) return launch_w8<E, MT>(a, splits, s);
+  if (a.wx) return launch_w4<E, MT>(a, splits, s);
   {
     WidePlan pl;
     if (wide_plan(MT, a, splits, pl)) {
@@ -212,7 +260,7 @@ int decode_gemm_dispatch(const mxvl_gemv_desc* d, hipStream_t s) {
   int splits = 1;
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
-  return decode_dtype(d->dtype & ~MXVL_W_INT8) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
+  return decode_dtype(d->dtype & ~kWeightFlags) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
 }
 
 // the wide kernel's ring depth for a plan, as launch_wide picks it
@@ -234,6 +282,12 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
     out[0] = 3; out[1] = w.nw; out[2] = w.r; out[3] = w8_pf(MT, w.r, kW8Waves); out[4] = (int32_t)w.g;
     return MXVL_OK;
   }
+  if (a.wx) {                       // MXVL_W_MXFP4: out[0] = 4, then the same four figures of decode_gemm_w4_kernel
+    WidePlan w;
+    if (!w4_plan(MT, a, splits, w)) return MXVL_ERR_UNSUPPORTED;
+    out[0] = 4; out[1] = w.nw; out[2] = w.r; out[3] = w4_pf(MT, w.r, kW4Waves); out[4] = (int32_t)w.g;
+    return MXVL_OK;
+  }
   WidePlan pl;
   const bool wide = wide_plan(MT, a, splits, pl);
   out[0] = wide ? 1 : 0;
@@ -246,11 +300,11 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
 
 // argument checks of mxvl_decode_gemv + the kernel-side argument block (nothing is launched here)
 static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& splits) {
-  if (!decode_dtype_ok(d->dtype & ~MXVL_W_INT8)) return MXVL_ERR_DTYPE;
-  const bool w8 = (d->dtype & MXVL_W_INT8) != 0;            // w_scale / w2_scale exist in the caller's struct only behind this flag
-  if (w8 && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
+  if (!decode_dtype_ok(d->dtype & ~kWeightFlags) || (d->dtype & kWeightFlags) == kWeightFlags) return MXVL_ERR_DTYPE;   // one weight format at most
+  const bool w8 = (d->dtype & MXVL_W_INT8) != 0, w4 = (d->dtype & MXVL_W_MXFP4) != 0;   // w_scale / w2_scale exist in the caller's struct only behind these flags
+  if ((w8 || w4) && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
-  if (w8 && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no int8 form of these
+  if ((w8 || w4) && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no quantised form of these
   if (d->K % 8 != 0) return MXVL_ERR_UNSUPPORTED;                      // 16-byte fragments
   if (d->swiglu && (!d->W2 || d->out_f32)) return MXVL_ERR_UNSUPPORTED;
   // RMSNorm fused into the projection (ABI v8): the LDS-DMA kernel only (K % 64 == 0); elsewhere rows come from mxvl_decode_rmsnorm
@@ -264,6 +318,8 @@ static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& spl
   a.g_scale = 1.0f; a.g_inv = 1.0f;
   a.ws = w8 ? (const float*)d->w_scale : nullptr;
   a.ws2 = (w8 && d->swiglu) ? (const float*)d->w2_scale : nullptr;
+  a.wx = w4 ? (const uint8_t*)d->w_scale : nullptr;
+  a.wx2 = (w4 && d->swiglu) ? (const uint8_t*)d->w2_scale : nullptr;
   if (d->norm_weight && d->norm_gain_scale != 0.0f) {
     int e = 0;
     const float m = frexpf(d->norm_gain_scale, &e);

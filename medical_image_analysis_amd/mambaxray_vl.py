@@ -13,7 +13,8 @@ Differences, all at the edges of the hot path:
     safetensors directory, or injected; tokenizers are injected or loaded from a LOCAL directory -- nothing is fetched;
   * `low_resource` (the reference loads the frozen LLM with load_in_8bit=True, MambaXrayVL_DownStream.py:82-92) stores the layer
     projections of the LLM as row-wise absmax int8 -- bitsandbytes' weight format -- served by this build's own kernels
-    (ReportDecoder.quantize_int8_, int8_linear.py; W8A16: activations stay 16-bit, no bitsandbytes needed);
+    (ReportDecoder.quantize_int8_, int8_linear.py; W8A16: activations stay 16-bit, no bitsandbytes needed); `low_resource="mxfp4"`
+    (this build's own option) stores them as OCP MXFP4 instead (ReportDecoder.quantize_mxfp4_, mxfp4_linear.py; W4A16);
   * PEFT-LoRA wrappers (`vis_use_lora`, `llm_use_lora`) are not built: they wrap third-party modules outside the path and raise
     NotImplementedError when requested.
 """
@@ -46,7 +47,7 @@ def _get(args, name, default=None):
 
 def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
-    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading."""
+    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading, "mxfp4": MXFP4 ones (quantize_mxfp4_)."""
     sd = None
     if source is None or source == "llama2-7b":
         cfg = dict(LLAMA2_7B)
@@ -72,7 +73,9 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         if "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
             sd["lm_head.weight"] = sd["model.embed_tokens.weight"]          # tied embeddings
         llm.load_hf_state_dict(sd)
-    if low_resource:
+    if low_resource == "mxfp4":
+        llm.quantize_mxfp4_()
+    elif low_resource:
         llm.quantize_int8_()
     return llm
 
@@ -150,7 +153,11 @@ class MambaXrayVLDownStream(nn.Module):
                           cross_attn_implementation=_get(args, "cross_attn_implementation", "text-only-vanilla"),
                           cross_attn_gating_type=_get(args, "cross_attn_gating_type", "channel-wise-dynamic-sigmoid"))
         self.llama_model = llm if llm is not None else build_report_decoder(source, **hybrid)
-        if _get(args, "low_resource", False) and not self.llama_model.is_int8():
+        low = _get(args, "low_resource", False)
+        if low == "mxfp4":                      # OCP MXFP4 layer projections (mxfp4_linear.py); every other truthy value is the reference's int8
+            if not self.llama_model.is_mxfp4():
+                self.llama_model.quantize_mxfp4_()
+        elif low and not self.llama_model.is_int8():
             self.llama_model.quantize_int8_()
         self.llama_tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(_get(args, "llama_model"))
         self.llama_tokenizer.pad_token_id = 0

@@ -32,6 +32,7 @@ import torch.nn as nn
 from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
 from .int8_linear import DequantScratch, Int8Linear
+from .mxfp4_linear import MxFp4Linear
 
 
 class KVCache:
@@ -567,8 +568,8 @@ class _KernelStepper(_Stepper):
         mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and cfg.hidden_size <= 16384
         fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
             (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
-        if model.is_int8() and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
-            return False         # int8 projections (MXVL_W_INT8): K % 64 == 0 on the one kernel they have
+        if (model.is_int8() or model.is_mxfp4()) and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
+            return False         # int8 / mxfp4 projections (MXVL_W_INT8, MXVL_W_MXFP4): K % 64 == 0 on the one kernel each has
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
@@ -597,14 +598,16 @@ class _KernelStepper(_Stepper):
         self.batched = rows > 8 or (self.hidden % 64 == 0 and self.inter % 64 == 0 and (self.H * self.D) % 64 == 0)
         # int8 layer projections (ReportDecoder.quantize_int8_): the matrix-core kernel at every row count, explicit norm launches
         # ("split" mode) -- there is no int8 form of the fused RMSNorm; lm_head and the embedding stay 16-bit
-        self.int8 = model.is_int8()
+        # mxfp4 layer projections (ReportDecoder.quantize_mxfp4_) take the same route with MXVL_W_MXFP4
+        self.int8, self.mxfp4 = model.is_int8(), model.is_mxfp4()
+        self.quantised = self.int8 or self.mxfp4
         # rows <= 8: RMSNorm fused into the MFMA projection that consumes the rows (csrc/decode_gemm.h NORM, K % 64 == 0): no
         # mxvl_decode_rmsnorm launches (65 of a token's 229), o_proj / down_proj add their residual in their own epilogue instead of
         # splitting K.  Measured in one call (profiles/r05_decode_norm_ab.txt): batch 1 x beam 3 332.7 -> 361.1 tok/s, Qwen-1.8B 1 x 5
         # 755.7 -> 809.6; at 18 / 48 / 80 rows the unsplit o_proj / down_proj (256 workgroups of ONE 16-column tile: activation
         # re-reads = rows / 16 x the weight bytes) cost more than the launches save (1638 -> 1575, 2894 -> 2656, 2212 -> 1852
         # tok/s): those keep the K-split sums folded by an explicit norm launch ("split"; norm_mode is the A/B switch of bench.py)
-        self.fused_norm = self.batched and not self.int8 and self.norm_mode == "fused" and rows <= 8 and self.hidden % 64 == 0 and self.hidden >= 256 \
+        self.fused_norm = self.batched and not self.quantised and self.norm_mode == "fused" and rows <= 8 and self.hidden % 64 == 0 and self.hidden >= 256 \
             and self.inter % 64 == 0 and self.inter >= 256 and (self.H * self.D) % 64 == 0 and self.H * self.D >= 256
         # fp16 only (bf16 has fp32's exponent range): a power-of-two scale per RMSNorm gain, 2^-ceil(log2 max|g|), so that the fused
         # projection's dtype(g * s * x) can neither overflow nor sink into subnormals where the modules' dtype(dtype(x * rstd) * g) --
@@ -717,8 +720,8 @@ class _KernelStepper(_Stepper):
     def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0, scale=None, scale2=None):
         d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
-        if scale is not None:                   # W / W2 are int8 codes, scale / scale2 their row-wise absmax (SCB)
-            d.dtype |= _abi.MXVL_W_INT8
+        if scale is not None:                   # W / W2 are int8 codes + row-wise absmax (SCB), or packed E2M1 codes + E8M0 block scales
+            d.dtype |= _abi.MXVL_W_MXFP4 if self.mxfp4 else _abi.MXVL_W_INT8
             d.w_scale, d.w2_scale = scale.data_ptr(), _abi.ptr(scale2)
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
         d.x, d.norm_weight, d.W = x.data_ptr(), _abi.ptr(norm), W.data_ptr()
@@ -795,12 +798,13 @@ class _KernelStepper(_Stepper):
                 self._cross_attn(i)
                 att = self.att2
             if batched:
-                sc = (lambda lin: lin.SCB) if self.int8 else (lambda lin: None)
-                self._gemv(att, at.o_proj.weight, None, self.H * self.D, self.hidden, split=so, scale=sc(at.o_proj))
+                sc = (lambda lin: lin.weight_scale) if self.mxfp4 else (lambda lin: lin.SCB) if self.int8 else (lambda lin: None)
+                wt = (lambda lin: lin.weight_packed) if self.mxfp4 else (lambda lin: lin.weight)
+                self._gemv(att, wt(at.o_proj), None, self.H * self.D, self.hidden, split=so, scale=sc(at.o_proj))
                 xin = self._rmsnorm(None, ln2.weight, ln2.variance_epsilon, self.hidden, fold_res=self.x, x_out=self.x2, splits=so)
-                self._gemv(xin, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter, W2=layer.mlp.up_proj.weight,
+                self._gemv(xin, wt(layer.mlp.gate_proj), self.act, self.hidden, self.inter, W2=wt(layer.mlp.up_proj),
                            scale=sc(layer.mlp.gate_proj), scale2=sc(layer.mlp.up_proj))
-                self._gemv(self.act, layer.mlp.down_proj.weight, None, self.inter, self.hidden, split=sd, scale=sc(layer.mlp.down_proj))
+                self._gemv(self.act, wt(layer.mlp.down_proj), None, self.inter, self.hidden, split=sd, scale=sc(layer.mlp.down_proj))
             else:
                 self._gemv(att, at.o_proj.weight, self.x2, self.H * self.D, self.hidden, res=self.x)
                 self._gemv(self.x2, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter,
@@ -873,18 +877,22 @@ class ReportDecoder(nn.Module):
         for layer in self.model.layers:
             at = layer.self_attn
             W = getattr(at, "qkv_weight", None)
-            if W is not None and W.data_ptr() == at.q_proj.weight.data_ptr() and W.dtype == at.q_proj.weight.dtype:
+            qkv = (at.q_proj, at.k_proj, at.v_proj)
+            # where a projection keeps its weight bytes and their scales: nn.Linear / Int8Linear `weight` (+ `SCB`), MxFp4Linear its two buffers
+            wkey, skey = ("weight_packed", "weight_scale") if isinstance(at.q_proj, MxFp4Linear) else ("weight", "SCB")
+            w0 = getattr(at.q_proj, wkey)
+            if W is not None and W.data_ptr() == w0.data_ptr() and W.dtype == w0.dtype:
                 continue        # still fused (a later .to(device/dtype) re-creates the parameters and un-fuses them)
             with torch.no_grad():
-                W = torch.cat([at.q_proj.weight, at.k_proj.weight, at.v_proj.weight], dim=0).contiguous()
+                W = torch.cat([getattr(lin, wkey) for lin in qkv], dim=0).contiguous()
                 b = torch.cat([at.q_proj.bias, at.k_proj.bias, at.v_proj.bias], dim=0).contiguous()
-                nq, nk = at.q_proj.weight.shape[0], at.k_proj.weight.shape[0]
-                if isinstance(at.q_proj, Int8Linear):
-                    # int8: the codes' rows and the per-row scales concatenate exactly; the buffers become views of the fused ones
-                    # (assigned, not .data: the unfused storage is released, no second copy of the bytes)
-                    S = torch.cat([at.q_proj.SCB, at.k_proj.SCB, at.v_proj.SCB], dim=0).contiguous()
+                nq, nk = w0.shape[0], getattr(at.k_proj, wkey).shape[0]
+                if isinstance(at.q_proj, (Int8Linear, MxFp4Linear)):
+                    # int8 / mxfp4: the codes' rows and the per-row (per-block) scales concatenate exactly; the buffers become views of
+                    # the fused ones (assigned, not .data: the unfused storage is released, no second copy of the bytes)
+                    S = torch.cat([getattr(lin, skey) for lin in qkv], dim=0).contiguous()
                     for lin, lo, hi in ((at.q_proj, 0, nq), (at.k_proj, nq, nq + nk), (at.v_proj, nq + nk, W.shape[0])):
-                        lin.weight, lin.SCB, lin.bias = W[lo:hi], S[lo:hi], b[lo:hi]
+                        setattr(lin, wkey, W[lo:hi]); setattr(lin, skey, S[lo:hi]); lin.bias = b[lo:hi]
                     at.qkv_scale = S
                 else:
                     at.q_proj.weight.data, at.k_proj.weight.data, at.v_proj.weight.data = W[:nq], W[nq:nq + nk], W[nq + nk:]
@@ -897,11 +905,20 @@ class ReportDecoder(nn.Module):
     def is_int8(self):
         return isinstance(self.model.layers[0].mlp.down_proj, Int8Linear)
 
-    def quantize_int8_(self):
-        """The reference's `low_resource` (load_in_8bit=True): q/k/v/o_proj and gate/up/down_proj of every layer become Int8Linear
-        (row-wise absmax int8, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head (HF's 8-bit loader
-        skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The layers share
-        one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly."""
+    def is_mxfp4(self):
+        return isinstance(self.model.layers[0].mlp.down_proj, MxFp4Linear)
+
+    def quantize_mxfp4_(self):
+        """`low_resource="mxfp4"`: the projections quantize_int8_ covers become MxFp4Linear (OCP MXFP4: E2M1 codes, one E8M0 scale
+        per 32 along K; mxfp4_linear.py) and their 16-bit storage is released; the same modules stay 16-bit.  Every in_features
+        must be a multiple of 32; an fp16 weight outside fp16's exact range raises (quantize_mxfp4).  An int8 decoder is refused:
+        its 16-bit weights are gone."""
+        if self.is_int8():
+            raise RuntimeError("quantize_mxfp4_() on an int8 decoder: quantise the 16-bit weights, not their int8 codes")
+        self._quantize_layers(MxFp4Linear)
+        return self
+
+    def _quantize_layers(self, cls):
         scratch = DequantScratch()
         for layer in self.model.layers:
             at = layer.self_attn
@@ -910,11 +927,20 @@ class ReportDecoder(nn.Module):
                 mod = getattr(layer, owner)
                 for name in names:
                     lin = getattr(mod, name)
-                    if not isinstance(lin, Int8Linear):
-                        setattr(mod, name, Int8Linear.from_linear(lin, scratch))
+                    if not isinstance(lin, cls):
+                        setattr(mod, name, cls.from_linear(lin, scratch))
                     scratch.reserve(lin.in_features * lin.out_features)        # the buffer is sized once, for the largest weight
         self.__dict__.pop("_steppers", None)                            # captured steps name the old weights
         self.__dict__.pop("_autocast_shadows", None)
+
+    def quantize_int8_(self):
+        """The reference's `low_resource` (load_in_8bit=True): q/k/v/o_proj and gate/up/down_proj of every layer become Int8Linear
+        (row-wise absmax int8, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head (HF's 8-bit loader
+        skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The layers share
+        one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly."""
+        if self.is_mxfp4():
+            raise RuntimeError("quantize_int8_() on an mxfp4 decoder: quantise the 16-bit weights, not their 4-bit codes")
+        self._quantize_layers(Int8Linear)
         return self
 
     def get_input_embeddings(self):
@@ -1153,8 +1179,9 @@ class ReportDecoder(nn.Module):
             # (new parameter storage) or condition_vis_x() must not replay it.  The weight identity is part of the cache
             # (stale steppers are dropped), the conditioning state is part of the key.
             conditioned = any(self.model.layers[i].vis_x is not None for i in self.hybrid_layers)
+            last = self.model.layers[-1].mlp.down_proj
             ident = tuple((w.data_ptr(), w.dtype) for w in (self.lm_head.weight, self.model.embed_tokens.weight,
-                                                            self.model.layers[-1].mlp.down_proj.weight))
+                                                            last.weight_packed if self.is_mxfp4() else last.weight))
             if self.__dict__.get("_stepper_weights") != ident:
                 self.__dict__["_steppers"] = {}
                 self.__dict__["_stepper_weights"] = ident
