@@ -722,19 +722,53 @@ int mxvl_dwconv2d_bwd(const void *x, const void *weight, const void *bias, const
  *     22-bit fixed point, zero past the tap count.  in_size == out_size gives the identity (ksize 1), i.e. a skipped pass.
  *   mxvl_image_preprocess: src (in_h, in_w, 3) uint8 -> out (3, out_h, out_w) in out_dtype; tmp is a caller-provided
  *     (in_h, out_w, 3) uint8 workspace (Pillow's intermediate image); lut (3, 256) fp32 = value of byte v in channel c after
- *     rescale + normalise.  All pointers are device pointers; in_w <= 20000. */
+ *     rescale + normalise.  All pointers are device pointers; in_w <= 20000.
+ * The fields after `out_dtype` and after `out` serve the pre-training recipe RandomResizedCrop -> [Grayscale] ->
+ * RandomHorizontalFlip -> ToTensor -> Normalize (CXPMRG_Bench_MambaXray_VL/pretrain/main_pretrain.py:116-120,
+ * HD_Xray_Pretrain_MAE/pretrain/main.py:136-141); all zero = the whole-image call above, byte for byte.
+ *   flags: MXVL_IMG_FLIP_H -- output column x holds resized column out_w-1-x (PIL transpose(FLIP_LEFT_RIGHT) after the resize).
+ *          MXVL_IMG_GRAY   -- after the vertical pass L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 on the resized BYTES
+ *                             (Pillow convert("L")); out is (1, out_h, out_w) and only lut row 0 (256 floats) is read.
+ *          Any other bit: MXVL_ERR_UNSUPPORTED.
+ *   src_pitch: bytes between source rows; 0 = in_w*3; 0 < src_pitch < in_w*3: MXVL_ERR_STRIDE.  A crop (i, j, h, w) of a
+ *          (H, W, 3) image is src + (i*W + j)*3, in_h = h, in_w = w, src_pitch = W*3: CROP, THEN RESIZE -- taps clamp at the
+ *          crop's own border and the coefficients are those of in_size = crop size (Image.crop(box).resize(size), not
+ *          Image.resize(size, box=box), which reads pixels outside the box).  The in_w limit is the crop's; rows may start
+ *          at any byte alignment.
+ *   batch: 0 = the one image the descriptor describes.  batch >= 1 (<= 65535; < 0: MXVL_ERR_SHAPE): `items` is a DEVICE array
+ *          of `batch` mxvl_image_item records (NULL: MXVL_ERR_NULL) and out is (batch, C, out_h, out_w).  out_h, out_w,
+ *          out_dtype, lut and the MXVL_IMG_GRAY bit of `flags` are shared; the descriptor's in_h / in_w are the MAXIMA of the
+ *          items' (they size the grid and the LDS row; an item whose in_h or in_w exceeds them is skipped by both passes: its
+ *          part of out is left unwritten); its src, src_pitch, ksize, bounds, kk and tmp are ignored.  A record's flags carry that image's MXVL_IMG_FLIP_H.  The whole batch is
+ *          two launches (horizontal, vertical + normalise) with the image index as a grid dimension. */
 typedef enum mxvl_resample { MXVL_RESAMPLE_BILINEAR = 2, MXVL_RESAMPLE_BICUBIC = 3 } mxvl_resample; /* PIL.Image.Resampling values */
+typedef enum mxvl_image_flags { MXVL_IMG_FLIP_H = 1, MXVL_IMG_GRAY = 2 } mxvl_image_flags;
+typedef struct mxvl_image_item {   /* one image of a batched call: 80 bytes, device memory */
+  const void *src;              /* first byte of the (crop's) first row */
+  int64_t src_pitch;            /* bytes between source rows, >= in_w*3 (0 is NOT read as dense here) */
+  int32_t in_h, in_w;           /* the crop's size */
+  int32_t ksize_h, ksize_v;
+  int32_t flags;                /* MXVL_IMG_FLIP_H */
+  int32_t reserved0;
+  const void *bounds_h, *kk_h;  /* in_w -> out_w */
+  const void *bounds_v, *kk_v;  /* in_h -> out_h */
+  void *tmp;                    /* this image's (in_h, out_w, 3) uint8 slab */
+} mxvl_image_item;
 typedef struct mxvl_image_desc {
   int32_t in_h, in_w, out_h, out_w;
   int32_t ksize_h, ksize_v;
   int32_t out_dtype; /* mxvl_dtype */
-  int32_t reserved0;
+  int32_t flags;     /* mxvl_image_flags */
   const void *src;
   const void *bounds_h, *kk_h; /* horizontal pass: in_w -> out_w */
   const void *bounds_v, *kk_v; /* vertical pass:   in_h -> out_h */
   const void *lut;
   void *tmp;
   void *out;
+  int64_t src_pitch;
+  int32_t batch;
+  int32_t reserved1;
+  const void *items; /* device array of mxvl_image_item[batch] */
 } mxvl_image_desc;
 int mxvl_resample_ksize(int in_size, int out_size, int filter);
 int mxvl_resample_coeffs(int in_size, int out_size, int filter, int32_t *bounds, int32_t *kk);

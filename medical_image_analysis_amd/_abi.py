@@ -270,9 +270,22 @@ class SampleDesc(ctypes.Structure):
 class ImageDesc(ctypes.Structure):
     _fields_ = [
         ("in_h", c_int32), ("in_w", c_int32), ("out_h", c_int32), ("out_w", c_int32),
-        ("ksize_h", c_int32), ("ksize_v", c_int32), ("out_dtype", c_int32), ("reserved0", c_int32),
+        ("ksize_h", c_int32), ("ksize_v", c_int32), ("out_dtype", c_int32), ("flags", c_int32),
         ("src", c_void_p), ("bounds_h", c_void_p), ("kk_h", c_void_p), ("bounds_v", c_void_p), ("kk_v", c_void_p),
         ("lut", c_void_p), ("tmp", c_void_p), ("out", c_void_p),
+        ("src_pitch", c_int64), ("batch", c_int32), ("reserved1", c_int32), ("items", c_void_p),
+    ]
+
+
+MXVL_IMG_FLIP_H, MXVL_IMG_GRAY = 1, 2
+
+
+class ImageItem(ctypes.Structure):
+    """mxvl_image_item: one image of a batched mxvl_image_preprocess call (a record of the device array ImageDesc.items names)."""
+    _fields_ = [
+        ("src", c_void_p), ("src_pitch", c_int64), ("in_h", c_int32), ("in_w", c_int32), ("ksize_h", c_int32), ("ksize_v", c_int32),
+        ("flags", c_int32), ("reserved0", c_int32),
+        ("bounds_h", c_void_p), ("kk_h", c_void_p), ("bounds_v", c_void_p), ("kk_v", c_void_p), ("tmp", c_void_p),
     ]
 
 
@@ -392,6 +405,16 @@ def dtype_code(dt: torch.dtype) -> int:
 
 def ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
+
+
+def sizeof(struct) -> int:
+    return ctypes.sizeof(struct)
+
+
+def array_in(struct, count: int, buffer):
+    """`count` records of `struct` laid over the first bytes of a writable host buffer (a pinned staging array): what the caller
+    fills is what the device reads after the upload.  The records hold the buffer; drop them before it goes away."""
+    return (struct * count).from_buffer(buffer)
 
 
 def stream_ptr(device) -> int:

@@ -12,6 +12,10 @@
 //   * vertical pass + normalisation: one thread per output pixel, taps broadcast through scalar loads, the byte ->
 //     float map (rescale + normalise of all 256 byte values per channel, computed by the caller exactly as
 //     transformers does) is a 3x256 LDS table, so the float result carries no rounding of its own.
+//   * pre-training augmentation (RandomResizedCrop -> [Grayscale] -> RandomHorizontalFlip -> ToTensor -> Normalize) rides the
+//     same two kernels: a crop is a source pointer + row pitch (crop, then resize: the taps never leave the crop), the mirror
+//     is the horizontal pass's write address, the luma is Pillow's convert("L") integer formula on the resized bytes before
+//     the table lookup, and a batch is one more grid dimension over an array of per-image records (two launches per batch).
 // HBM traffic = 3*in_h*in_w read + 2*3*in_h*out_w (intermediate, L2-resident) + elt*3*out_h*out_w written.
 #include <cmath>
 
@@ -35,12 +39,23 @@ static double filter_weight(int kind, double x) {
 }
 static double filter_support(int kind) { return kind == MXVL_RESAMPLE_BILINEAR ? 1.0 : 2.0; }
 
-struct ImgArgs {
-  int in_h, in_w, out_h, out_w, ksize_h, ksize_v;
+// One image of a call: the layout of mxvl_image_item (a batched call reads these records from device memory; the single-image
+// call carries one in the kernel arguments).
+struct ImgItem {
   const uint8_t* src;
+  int64_t pitch;
+  int in_h, in_w, ksize_h, ksize_v, flags, reserved0;
   const int32_t *bounds_h, *kk_h, *bounds_v, *kk_v;
-  const float* lut;
   uint8_t* tmp;
+};
+static_assert(sizeof(ImgItem) == sizeof(mxvl_image_item) && sizeof(ImgItem) == 80, "ImgItem mirrors mxvl_image_item");
+
+struct ImgArgs {
+  ImgItem one;             // batch == 0
+  const ImgItem* items;    // batch >= 1: image blockIdx.{y (horizontal), z (vertical)}
+  int max_in_h, max_in_w;  // the grid's row extent and what the LDS row buffer was sized for
+  int out_h, out_w, gray;
+  const float* lut;
   void* out;
 };
 
@@ -51,9 +66,13 @@ __device__ inline int clip8(int v) {
 
 __global__ __launch_bounds__(kImgThreads) void resample_h_kernel(const ImgArgs p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t row[];
+  const ImgItem it = p.items ? p.items[blockIdx.y] : p.one;
   const int y = blockIdx.x, tid = threadIdx.x;
-  const int nbytes = p.in_w * 3;
-  const uint8_t* rowp = p.src + (size_t)y * nbytes;
+  // the grid spans the tallest image of a batch: rows past this one's leave here, the whole workgroup, before the barrier
+  // (an image larger than the descriptor's maxima is skipped by both passes: nothing of it is written)
+  if (y >= it.in_h || it.in_h > p.max_in_h || it.in_w > p.max_in_w || it.in_w <= 0) return;
+  const int nbytes = it.in_w * 3;
+  const uint8_t* rowp = it.src + (size_t)y * (size_t)it.pitch;
   const int mis = (int)((uintptr_t)rowp & 3);            // LDS byte i mirrors address rowp - mis + i (word aligned)
   const int nw = (mis + nbytes + 3) >> 2;
   for (int w = tid; w < nw; w += kImgThreads) {
@@ -69,48 +88,59 @@ __global__ __launch_bounds__(kImgThreads) void resample_h_kernel(const ImgArgs p
     }
   }
   __syncthreads();
-  uint8_t* dst = p.tmp + (size_t)y * p.out_w * 3;
+  uint8_t* dst = it.tmp + (size_t)y * p.out_w * 3;
+  const bool flip = (it.flags & MXVL_IMG_FLIP_H) != 0;
   for (int ox = tid; ox < p.out_w; ox += kImgThreads) {
-    const int xmin = p.bounds_h[2 * ox], n = p.bounds_h[2 * ox + 1];
+    const int xmin = it.bounds_h[2 * ox], n = it.bounds_h[2 * ox + 1];
     int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
     const uint8_t* px = row + mis + xmin * 3;
     for (int x = 0; x < n; ++x) {
-      const int k = p.kk_h[(size_t)x * p.out_w + ox];
+      const int k = it.kk_h[(size_t)x * p.out_w + ox];
       s0 += (int)px[0] * k;
       s1 += (int)px[1] * k;
       s2 += (int)px[2] * k;
       px += 3;
     }
-    dst[ox * 3 + 0] = (uint8_t)clip8(s0);
-    dst[ox * 3 + 1] = (uint8_t)clip8(s1);
-    dst[ox * 3 + 2] = (uint8_t)clip8(s2);
+    uint8_t* d = dst + (flip ? p.out_w - 1 - ox : ox) * 3;   // the mirror is a write address: the vertical pass never sees it
+    d[0] = (uint8_t)clip8(s0);
+    d[1] = (uint8_t)clip8(s1);
+    d[2] = (uint8_t)clip8(s2);
   }
 }
 
 template <typename out_t>
 __global__ __launch_bounds__(kImgThreads) void resample_v_norm_kernel(const ImgArgs p) {
   __shared__ float lut[3 * 256];
+  const ImgItem it = p.items ? p.items[blockIdx.z] : p.one;
+  if (it.in_h > p.max_in_h || it.in_w > p.max_in_w || it.in_w <= 0 || it.in_h <= 0) return;   // what the horizontal pass skipped (workgroup-uniform)
   const int tid = threadIdx.x, oy = blockIdx.y;
-  for (int i = tid; i < 3 * 256; i += kImgThreads) lut[i] = p.lut[i];
+  const int nlut = p.gray ? 256 : 3 * 256;                 // a grey call owns one table row
+  for (int i = tid; i < nlut; i += kImgThreads) lut[i] = p.lut[i];
   __syncthreads();
   const int ox = blockIdx.x * kImgThreads + tid;
   if (ox >= p.out_w) return;
-  const int ymin = p.bounds_v[2 * oy], n = p.bounds_v[2 * oy + 1];
+  const int ymin = it.bounds_v[2 * oy], n = it.bounds_v[2 * oy + 1];
   const size_t pitch = (size_t)p.out_w * 3;
-  const uint8_t* px = p.tmp + (size_t)ymin * pitch + (size_t)ox * 3;
+  const uint8_t* px = it.tmp + (size_t)ymin * pitch + (size_t)ox * 3;
   int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
   for (int yy = 0; yy < n; ++yy) {
-    const int k = p.kk_v[(size_t)yy * p.out_h + oy];       // uniform over the workgroup
+    const int k = it.kk_v[(size_t)yy * p.out_h + oy];      // uniform over the workgroup
     s0 += (int)px[0] * k;
     s1 += (int)px[1] * k;
     s2 += (int)px[2] * k;
     px += pitch;
   }
   const size_t plane = (size_t)p.out_h * p.out_w;
-  out_t* o = (out_t*)p.out + (size_t)oy * p.out_w + ox;
-  Io<out_t>::st(o, lut[clip8(s0)]);
-  Io<out_t>::st(o + plane, lut[256 + clip8(s1)]);
-  Io<out_t>::st(o + 2 * plane, lut[512 + clip8(s2)]);
+  const int r = clip8(s0), g = clip8(s1), b = clip8(s2);
+  if (p.gray) {                                            // Pillow convert("L"): ITU-R 601-2 luma in 16-bit fixed point, on the bytes
+    out_t* o = (out_t*)p.out + (size_t)blockIdx.z * plane + (size_t)oy * p.out_w + ox;
+    Io<out_t>::st(o, lut[(19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16]);
+    return;
+  }
+  out_t* o = (out_t*)p.out + (size_t)blockIdx.z * 3 * plane + (size_t)oy * p.out_w + ox;
+  Io<out_t>::st(o, lut[r]);
+  Io<out_t>::st(o + plane, lut[256 + g]);
+  Io<out_t>::st(o + 2 * plane, lut[512 + b]);
 }
 
 }  // namespace mxvl
@@ -171,19 +201,29 @@ int mxvl_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds,
 
 int mxvl_image_preprocess(const mxvl_image_desc* d, void* hip_stream) {
   if (!d) return MXVL_ERR_NULL;
-  if (!d->src || !d->bounds_h || !d->kk_h || !d->bounds_v || !d->kk_v || !d->lut || !d->tmp || !d->out) return MXVL_ERR_NULL;
-  if (d->in_h <= 0 || d->in_w <= 0 || d->out_h <= 0 || d->out_w <= 0 || d->ksize_h <= 0 || d->ksize_v <= 0) return MXVL_ERR_SHAPE;
+  if (d->flags & ~(MXVL_IMG_FLIP_H | MXVL_IMG_GRAY)) return MXVL_ERR_UNSUPPORTED;
+  if (d->batch < 0 || d->batch > 65535) return MXVL_ERR_SHAPE;
+  if (!d->lut || !d->out) return MXVL_ERR_NULL;
+  if (d->batch ? !d->items : (!d->src || !d->bounds_h || !d->kk_h || !d->bounds_v || !d->kk_v || !d->tmp)) return MXVL_ERR_NULL;
+  if (d->in_h <= 0 || d->in_w <= 0 || d->out_h <= 0 || d->out_w <= 0) return MXVL_ERR_SHAPE;
+  if (!d->batch && (d->ksize_h <= 0 || d->ksize_v <= 0)) return MXVL_ERR_SHAPE;
   if (d->out_dtype != MXVL_F32 && d->out_dtype != MXVL_BF16 && d->out_dtype != MXVL_F16) return MXVL_ERR_DTYPE;
   if ((long)d->in_w * 3 + 8 > kMaxRowBytes) return MXVL_ERR_UNSUPPORTED;
+  if (!d->batch && d->src_pitch != 0 && d->src_pitch < (int64_t)d->in_w * 3) return MXVL_ERR_STRIDE;
   ImgArgs a;
-  a.in_h = d->in_h; a.in_w = d->in_w; a.out_h = d->out_h; a.out_w = d->out_w; a.ksize_h = d->ksize_h; a.ksize_v = d->ksize_v;
-  a.src = (const uint8_t*)d->src; a.bounds_h = (const int32_t*)d->bounds_h; a.kk_h = (const int32_t*)d->kk_h;
-  a.bounds_v = (const int32_t*)d->bounds_v; a.kk_v = (const int32_t*)d->kk_v; a.lut = (const float*)d->lut;
-  a.tmp = (uint8_t*)d->tmp; a.out = d->out;
+  a.one.src = (const uint8_t*)d->src; a.one.pitch = d->src_pitch ? d->src_pitch : (int64_t)d->in_w * 3;
+  a.one.in_h = d->in_h; a.one.in_w = d->in_w; a.one.ksize_h = d->ksize_h; a.one.ksize_v = d->ksize_v;
+  a.one.flags = d->flags; a.one.reserved0 = 0;
+  a.one.bounds_h = (const int32_t*)d->bounds_h; a.one.kk_h = (const int32_t*)d->kk_h;
+  a.one.bounds_v = (const int32_t*)d->bounds_v; a.one.kk_v = (const int32_t*)d->kk_v; a.one.tmp = (uint8_t*)d->tmp;
+  a.items = d->batch ? (const ImgItem*)d->items : nullptr;
+  a.max_in_h = d->in_h; a.max_in_w = d->in_w; a.out_h = d->out_h; a.out_w = d->out_w; a.gray = (d->flags & MXVL_IMG_GRAY) ? 1 : 0;
+  a.lut = (const float*)d->lut; a.out = d->out;
   hipStream_t s = (hipStream_t)hip_stream;
+  const unsigned n_img = d->batch ? d->batch : 1;
   const size_t lds = ((size_t)d->in_w * 3 + 8 + 15) & ~(size_t)15;
-  hipLaunchKernelGGL(resample_h_kernel, dim3(d->in_h), dim3(kImgThreads), lds, s, a);
-  const dim3 grid((d->out_w + kImgThreads - 1) / kImgThreads, d->out_h);
+  hipLaunchKernelGGL(resample_h_kernel, dim3(d->in_h, n_img), dim3(kImgThreads), lds, s, a);
+  const dim3 grid((d->out_w + kImgThreads - 1) / kImgThreads, d->out_h, n_img);
   switch (d->out_dtype) {
     case MXVL_F32: hipLaunchKernelGGL(resample_v_norm_kernel<float>, grid, dim3(kImgThreads), 0, s, a); break;
     case MXVL_BF16: hipLaunchKernelGGL(resample_v_norm_kernel<bf16_t>, grid, dim3(kImgThreads), 0, s, a); break;

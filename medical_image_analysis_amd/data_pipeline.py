@@ -6,6 +6,9 @@ the CPU inside the DataLoader workers (Pillow + numpy, 20-30 ms per radiograph);
 (H, W, 3) uint8 and `DeviceBatcher` runs `mxvl_image_preprocess` on the GPU in the training process (20-80 us per image,
 bit-identical pixel_values).  Same `args` fields (`dataset`, `annotation`, `base_dir`, `input_size`), same sample keys
 (`id`, `input_text`, `image`).
+
+The pre-training side has the same split: `RawImageFolder` + `collate_images` hand the decoded radiographs of a batch to
+`augment.PretrainAugment`, whose device tensor is what `PretrainEngine.step` takes.
 """
 from __future__ import annotations
 
@@ -65,6 +68,34 @@ def load_rgb_uint8(path: str) -> np.ndarray:
         if array.shape[-1] != 3 or len(array.shape) != 3:
             array = np.array(pil.convert("RGB"), dtype=np.uint8)
     return array
+
+
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
+
+
+class RawImageFolder(data.Dataset):
+    """Every image file below `root` (sorted, recursive) as an (H, W, 3) uint8 array: the decode half of the pre-training
+    scripts' `MyDatasets.__getitem__` (CXPMRG_Bench_MambaXray_VL/pretrain/dataset/MyDatasets.py:13-18, `Image.open` + the
+    transform).  The transform half runs on the device: collate with `collate_images`, then
+    `augment.PretrainAugment(batch)` -> `PretrainEngine.step(imgs)`."""
+
+    def __init__(self, root: str, extensions=IMAGE_EXTENSIONS):
+        self.root = root
+        self.paths = sorted(os.path.join(d, f) for d, _, files in os.walk(root) for f in files
+                            if f.lower().endswith(tuple(extensions)))
+        if not self.paths:
+            raise FileNotFoundError(f"no image files ({', '.join(extensions)}) below {root}")
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, index) -> np.ndarray:
+        return load_rgb_uint8(self.paths[index])
+
+
+def collate_images(samples):
+    """DataLoader collate_fn of `RawImageFolder`: radiographs differ in size, so a batch is the list of its arrays."""
+    return list(samples)
 
 
 class FieldParser:

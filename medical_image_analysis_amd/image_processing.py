@@ -63,26 +63,143 @@ def byte_value_table(do_rescale: bool, rescale_factor: float, do_normalize: bool
     return np.ascontiguousarray(t, dtype=np.float32)
 
 
+# a random crop's sizes do not come back: its tables bypass _coeffs_host's cache (same function, same two check sites)
+_coeffs_uncached = _coeffs_host.__wrapped__
+
+
+def _align16(n: int) -> int:
+    return (n + 15) & ~15
+
+
+def _layout(arrays, start: int):
+    """Byte offsets of `arrays` packed 16-byte aligned from `start`, and the end of the last one."""
+    offs = []
+    for a in arrays:
+        offs.append(start)
+        start += _align16(a.nbytes)
+    return offs, start
+
+
+def _fill(host: np.ndarray, arrays, offs) -> None:
+    for a, at in zip(arrays, offs):
+        host[at:at + a.nbytes] = a.reshape(-1).view(np.uint8)
+
+
+def _check_crop(crop, H: int, W: int):
+    i, j, h, w = (int(v) for v in crop)
+    if not (0 <= i and 0 <= j and 0 < h and 0 < w and i + h <= H and j + w <= W):
+        raise ValueError(f"crop (i, j, h, w) = {(i, j, h, w)} does not lie inside the {H} x {W} image")
+    return i, j, h, w
+
+
 def preprocess_image(img: torch.Tensor, out_h: int, out_w: int, resample: int, table: torch.Tensor,
-                     out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """One mxvl_image_preprocess call: img (H, W, 3) uint8 on the GPU -> (3, out_h, out_w)."""
+                     out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32,
+                     crop=None, flip: bool = False, gray: bool = False) -> torch.Tensor:
+    """One mxvl_image_preprocess call: img (H, W, 3) uint8 on the GPU -> (3, out_h, out_w).
+    crop = (i, j, h, w): `Image.crop` of rows [i, i+h) x columns [j, j+w) BEFORE the resize (a pointer and a row pitch: nothing
+    is copied); flip: `transpose(FLIP_LEFT_RIGHT)` after it; gray: `convert("L")` after it -> (1, out_h, out_w) through
+    table row 0."""
     dev = _abi.require_gpu(img, table, out)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise RuntimeError(f"image must be (H, W, 3) uint8, got {tuple(img.shape)} {img.dtype}")
     img = img.contiguous()
     H, W, _ = img.shape
-    ks_h, b_h, k_h = _coeffs_device(W, out_w, resample, dev)
-    ks_v, b_v, k_v = _coeffs_device(H, out_h, resample, dev)
+    C = 1 if gray else 3
+    if table.dtype != torch.float32 or table.numel() < C * 256:
+        raise RuntimeError(f"table must hold ({C}, 256) float32 values")
+    if crop is None:
+        i, j, h, w = 0, 0, H, W
+        ks_h, b_h, k_h = _coeffs_device(W, out_w, resample, dev)
+        ks_v, b_v, k_v = _coeffs_device(H, out_h, resample, dev)
+    else:                                   # crop sizes are random: their tables enter neither cache and travel in one pinned copy
+        i, j, h, w = _check_crop(crop, H, W)
+        (ks_h, bh, kh), (ks_v, bv, kv) = _coeffs_uncached(w, out_w, resample), _coeffs_uncached(h, out_h, resample)
+        offs, n_bytes = _layout((bh, kh, bv, kv), 0)
+        stage = torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True)
+        _fill(stage.numpy(), (bh, kh, bv, kv), offs)
+        tables = stage.to(dev, non_blocking=True)
+        b_h, k_h, b_v, k_v = (tables[o:] for o in offs)
     if out is None:
-        out = torch.empty((3, out_h, out_w), dtype=dtype, device=dev)
-    elif tuple(out.shape) != (3, out_h, out_w) or not out.is_contiguous():
-        raise RuntimeError("out must be a contiguous (3, out_h, out_w) tensor")
-    tmp = torch.empty((H, out_w, 3), dtype=torch.uint8, device=dev)
+        out = torch.empty((C, out_h, out_w), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (C, out_h, out_w) or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous ({C}, out_h, out_w) tensor")
+    tmp = torch.empty((h, out_w, 3), dtype=torch.uint8, device=dev)
     d = _abi.ImageDesc()
-    d.in_h, d.in_w, d.out_h, d.out_w, d.ksize_h, d.ksize_v = H, W, out_h, out_w, ks_h, ks_v
+    d.in_h, d.in_w, d.out_h, d.out_w, d.ksize_h, d.ksize_v = h, w, out_h, out_w, ks_h, ks_v
     d.out_dtype = _abi.dtype_code(out.dtype)
-    d.src, d.bounds_h, d.kk_h, d.bounds_v, d.kk_v = img.data_ptr(), b_h.data_ptr(), k_h.data_ptr(), b_v.data_ptr(), k_v.data_ptr()
+    d.flags = (_abi.MXVL_IMG_FLIP_H if flip else 0) | (_abi.MXVL_IMG_GRAY if gray else 0)
+    d.src, d.src_pitch = img.data_ptr() + (i * W + j) * 3, (W * 3 if crop is not None else 0)
+    d.bounds_h, d.kk_h, d.bounds_v, d.kk_v = b_h.data_ptr(), k_h.data_ptr(), b_v.data_ptr(), k_v.data_ptr()
     d.lut, d.tmp, d.out = table.data_ptr(), tmp.data_ptr(), out.data_ptr()
+    _abi.launch("mxvl_image_preprocess", d, device=dev)
+    return out
+
+
+def preprocess_batch(images, crops, flips, size, resample: int, table: torch.Tensor, gray: bool = False,
+                     dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """B images -> (B, C, S_h, S_w) on table's device with ONE mxvl_image_preprocess call (two kernel launches).
+    images: (H, W, 3) uint8 numpy arrays or tensors, any sizes; a host image uploads only the rows its crop reads, a device
+    tensor is read in place.  crops: (i, j, h, w) per image (None = the whole image); flips: bool per image; size: int or
+    (height, width).  The item records and every coefficient table travel in one pinned staging buffer, one copy."""
+    dev = _abi.require_gpu(table)
+    B = len(images)
+    if B == 0 or len(crops) != B or len(flips) != B:
+        raise ValueError("preprocess_batch needs one crop and one flip per image, and at least one image")
+    out_h, out_w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    C = 1 if gray else 3
+    if table.dtype != torch.float32 or table.numel() < C * 256:
+        raise RuntimeError(f"table must hold ({C}, 256) float32 values")
+    isz = _abi.sizeof(_abi.ImageItem)
+    boxes, coeffs, offs, keep = [], [], [], []
+    n_bytes, n_tmp = _align16(B * isz), 0
+    for im, crop in zip(images, crops):
+        if not isinstance(im, torch.Tensor):
+            a = np.asarray(im)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"expected an (H, W, 3) uint8 image, got {a.shape} {a.dtype}")
+        elif im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f"expected an (H, W, 3) uint8 image, got {tuple(im.shape)} {im.dtype}")
+        H, W = int(im.shape[0]), int(im.shape[1])
+        i, j, h, w = _check_crop(crop, H, W) if crop is not None else (0, 0, H, W)
+        if isinstance(im, torch.Tensor) and im.is_cuda:
+            if im.device != dev:
+                raise RuntimeError("images and table must live on one device")
+            slab = im.contiguous()
+            src = slab.data_ptr() + (i * W + j) * 3
+        else:                               # rows [i, i+h) are one contiguous slab of the host image
+            rows = im[i:i + h] if isinstance(im, torch.Tensor) else np.ascontiguousarray(np.asarray(im)[i:i + h])
+            if not isinstance(rows, torch.Tensor):
+                rows = torch.from_numpy(rows if rows.flags.writeable else rows.copy())
+            slab = rows.contiguous().to(dev)
+            src = slab.data_ptr() + j * 3
+        keep.append(slab)
+        boxes.append((src, W * 3, h, w))
+        coeffs_of = _coeffs_host if crop is None else _coeffs_uncached      # whole-image sizes recur, random boxes do not
+        ch, cv = coeffs_of(w, out_w, resample), coeffs_of(h, out_h, resample)
+        coeffs.append((ch, cv))
+        o, n_bytes = _layout((ch[1], ch[2], cv[1], cv[2]), n_bytes)
+        o.append(n_tmp)
+        n_tmp += _align16(h * out_w * 3)
+        offs.append(o)
+    stage = torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    table_dev = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+    tmp = torch.empty(n_tmp, dtype=torch.uint8, device=dev)
+    base, tbase = table_dev.data_ptr(), tmp.data_ptr()
+    items = _abi.array_in(_abi.ImageItem, B, host)
+    for it, (src, pitch, h, w), (ch, cv), o, flip in zip(items, boxes, coeffs, offs, flips):
+        it.src, it.src_pitch, it.in_h, it.in_w, it.ksize_h, it.ksize_v = src, pitch, h, w, ch[0], cv[0]
+        it.flags, it.reserved0 = (_abi.MXVL_IMG_FLIP_H if flip else 0), 0
+        it.bounds_h, it.kk_h, it.bounds_v, it.kk_v, it.tmp = base + o[0], base + o[1], base + o[2], base + o[3], tbase + o[4]
+        _fill(host, (ch[1], ch[2], cv[1], cv[2]), o)
+    del items
+    table_dev.copy_(stage, non_blocking=True)
+    out = torch.empty((B, C, out_h, out_w), dtype=dtype, device=dev)
+    d = _abi.ImageDesc()
+    d.in_h, d.in_w = max(b[2] for b in boxes), max(b[3] for b in boxes)
+    d.out_h, d.out_w, d.out_dtype = out_h, out_w, _abi.dtype_code(out.dtype)
+    d.flags = _abi.MXVL_IMG_GRAY if gray else 0
+    d.lut, d.out, d.batch, d.items = table.data_ptr(), out.data_ptr(), B, base
     _abi.launch("mxvl_image_preprocess", d, device=dev)
     return out
 
