@@ -103,3 +103,37 @@ def test_kv_cache_decode_equals_full_forward():
             outs.append(lay(x[:, t:t + 1], position_ids=pos[:, t:t + 1], past_key_value=cache, use_cache=True,
                             cache_position=torch.tensor([t]))[0])
     assert_close(torch.cat(outs, 1), full, 1e-5, 1e-4, "incremental decode")
+
+
+@pytest.mark.gpu
+def test_self_attention_padding_mask_gpu_matches_cpu_expression():
+    """Qwen2HybridAttention.forward with a (B, kv_len) padding mask -- one left-padded, one right-padded, one full row -- on the
+    GPU (attention_mask[:, :kv_len].bool() -> key_mask of the causal MFMA kernel) against the same module and weights on the CPU
+    (its reference expression): output and hidden_states.grad at the non-padded positions, and finite values at the padded ones
+    (a left-padded row has queries without a single key).  The upstream gradient is zero at padded positions, as a loss with
+    ignored pads gives."""
+    import copy
+    from medical_image_analysis_amd.hybrid_decoder_layer import Qwen2HybridAttention
+    torch.manual_seed(0)
+    att = Qwen2HybridAttention(False, None, None, config=CFG, layer_idx=0).eval()
+    B, T = 3, 40
+    hs = torch.randn(B, T, CFG.hidden_size)
+    mask = torch.ones(B, T + 6, dtype=torch.long)          # wider than kv_len: the module's column slice is not contiguous
+    mask[0, :13] = 0
+    mask[1, 29:] = 0
+    valid = mask[:, :T].bool()
+    up = torch.randn(B, T, CFG.hidden_size) * valid[:, :, None]
+    pos = torch.arange(T)[None].expand(B, -1)
+
+    def run(dev):
+        m = copy.deepcopy(att).to(dev)
+        x = hs.clone().to(dev).requires_grad_(True)
+        out = m(x, attention_mask=mask.to(dev), position_ids=pos.to(dev))[0]
+        out.backward(up.to(dev))
+        return out.detach().cpu(), x.grad.cpu()
+    out_c, grad_c = run("cpu")
+    out_g, grad_g = run("cuda:0")
+    assert bool(torch.isfinite(out_g).all()) and bool(torch.isfinite(grad_g).all())
+    assert float(grad_c[valid].abs().max()) > 1e-2
+    assert_close(out_g[valid], out_c[valid], 2e-5, 1e-4, "padded causal self-attention, output")
+    assert_close(grad_g[valid], grad_c[valid], 2e-5, 1e-4, "padded causal self-attention, hidden_states.grad")
