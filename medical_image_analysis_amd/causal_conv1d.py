@@ -76,6 +76,8 @@ class CausalConv1dFn(torch.autograd.Function):
         if w2.shape[0] != x.shape[1]:
             raise RuntimeError("causal_conv1d: weight.shape[0] must equal dim")
         w32 = w2.detach().float().contiguous()
+        if bias is not None and tuple(bias.shape) != (x.shape[1],):
+            raise RuntimeError("causal_conv1d: bias must be (dim,)")
         b32 = bias.detach().float().contiguous() if bias is not None else None
         y = conv1d_fwd_raw(x, w32, b32, silu)
         ctx.silu = silu
@@ -106,7 +108,13 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
     x = x.contiguous()
     w32 = _w2(weight).detach().float().contiguous()
     b32 = bias.detach().float().contiguous() if bias is not None else None
+    if x.dim() != 2:
+        raise RuntimeError("causal_conv1d_update: x must be (batch, dim)")
     batch, dim = x.shape
+    if w32.shape[0] != dim or tuple(conv_state.shape) != (batch, dim, w32.shape[1]):
+        raise RuntimeError("causal_conv1d_update: weight must be (dim, width) and conv_state (batch, dim, width)")
+    if b32 is not None and tuple(b32.shape) != (dim,):
+        raise RuntimeError("causal_conv1d_update: bias must be (dim,)")
     y = torch.empty_like(x)
     _abi.launch("mxvl_conv1d_update", x.data_ptr(), conv_state.data_ptr(), w32.data_ptr(), _abi.ptr(b32), y.data_ptr(),
                 batch, dim, w32.shape[1], _abi.dtype_code(x.dtype), silu, device=x.device)

@@ -533,6 +533,7 @@ int mxvl_conv1d_bwd(const mxvl_conv1d_bwd_desc* d, void* hip_stream) {
   const bool svec = a.vec && a.W == 4 && a.L % 4 == 0 && a.L <= 512 && a.dim <= 65535 && rows_aligned(d->dx, d->dx_bs, d->dx_ds, d->fwd.io_dtype);
   const int TPR = (a.L + 7) / 8, RW = svec ? 256 / TPR : 0;          // L <= 512 -> TPR <= 64, RW >= 4
   const dim3 vgrid(RW > 0 ? (a.batch + RW - 1) / RW : 1, a.dim);
+  // tests/test_conv1d_gpu.py restates this choice and the forward's (_bwd_kernel_for / _fwd_kernel_for): change them together
 #define MXVL_CONV_BWD(T) \
   do { \
     if (svec && RW >= 2) hipLaunchKernelGGL((conv1d_bwd_vec_rows_kernel<T, 4>), vgrid, dim3(256), 0, s, a, TPR, RW); \

@@ -21,8 +21,11 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     A32 = A.float().contiguous()
     D32 = D.float().contiguous() if D is not None else None
     b32 = dt_bias.float().contiguous() if dt_bias is not None else None
-    if tuple(x.shape) != (batch, dim) or tuple(A32.shape) != (dim, N) or tuple(B.shape) != (batch, N):
-        raise RuntimeError("selective_state_update: shape mismatch")
+    # the kernel indexes every operand by (batch, dim, dstate) alone: a mis-shaped one would read or write out of bounds
+    for name, t, want in (("x", x, (batch, dim)), ("dt", dt, (batch, dim)), ("A", A32, (dim, N)), ("B", B, (batch, N)),
+                          ("C", C, (batch, N)), ("z", z, (batch, dim)), ("D", D32, (dim,)), ("dt_bias", b32, (dim,))):
+        if t is not None and tuple(t.shape) != want:
+            raise RuntimeError(f"selective_state_update: shape mismatch: {name} is {tuple(t.shape)}, expected {want}")
     out = torch.empty_like(x)
     _abi.launch("mxvl_state_update", state.data_ptr(), x.data_ptr(), dt.data_ptr(), A32.data_ptr(), B.data_ptr(),
                 C.data_ptr(), _abi.ptr(D32), _abi.ptr(z), _abi.ptr(b32), out.data_ptr(),
