@@ -446,7 +446,7 @@ __device__ __forceinline__ void dgw_epilogue(const DecodeGemmArgs& p, const dg_f
 // private LDS ring exactly as above, and the activation tile of a 64-column chunk (MT x 16 rows x 128 bytes, same XOR swizzle) is
 // brought in ONCE per workgroup by LDS-DMA (its 2 MT one-kilobyte pieces dealt round-robin to the waves) and read by every wave as
 // the B operand: MT / (NW R) activation bytes per weight byte, no fragment registers, a ring as deep as LDS holds (5..8 stages,
-// decode_gemm.hip wide_pf).  One s_barrier per chunk: behind it every wave's pieces of stage i have landed, and every wave is done
+// decode_gemm.hip ring_depth).  One s_barrier per chunk: behind it every wave's pieces of stage i have landed, and every wave is done
 // with the slot of stage i - 1, which is refilled right away.  No cross-wave reduction: a wave owns the whole K range of its columns
 // and runs the epilogue from registers (a lane's four columns of a row as ONE 16- / 8-byte store).
 // What bounds a launch (tools/cu_stream_probe.hip + the kernel with pieces switched off, profiles/r05_cu_stream_probe.txt,
@@ -455,130 +455,16 @@ __device__ __forceinline__ void dgw_epilogue(const DecodeGemmArgs& p, const dg_f
 // bytes per row and instruction -- halve it), HBM gives ~6.5-7 TB/s to >= 128 streaming CUs.  So the activation bytes a CU has to
 // pull next to its weight share, and the CUs a grid leaves idle, are what the 80-row projections pay for: NW = 3 where that fills
 // the chip (decode_gemm.hip), and the walk over K staggered per workgroup (below).
-template <typename E, int MT, int R, int NW, int PF>
-__global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(const DecodeGemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char dgw_smem[];
-  constexpr int ACT = MT * 2048, WST = R * 2048, STAGE = ACT + NW * WST;
-  constexpr int AI = (2 * MT + NW - 1) / NW;           // activation DMA instructions per wave and stage (a few waves repeat the last piece)
-  constexpr int OPS = 2 * R + AI;
-  static_assert(PF >= 2 && (PF - 1) * OPS <= 63, "vmcnt is a 6-bit field");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l16 = lane & 15, q = lane >> 4;
-  const int K = p.K, N = p.N;
-  const int cols_per_wave = (p.swiglu ? R / 2 : R) * 16;
-  const int n0 = (blockIdx.x * NW + wave) * cols_per_wave;       // this wave's first output column
-  const int rl = lane >> 3, ul = lane & 7;
-  const char* wsrc[R][2];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
-    const uint16_t* base = (p.swiglu && r >= R / 2) ? p.W2 : p.W;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = h * 8 + rl;
-      int n = n0 + t * 16 + row;
-      n = n < N ? n : N - 1;
-      wsrc[r][h] = (const char*)(base + (size_t)n * K) + ((ul ^ dg_key(row)) << 4);
-    }
-  }
-  const char* asrc[AI];
-  unsigned adst[AI];
-#pragma unroll
-  for (int i = 0; i < AI; ++i) {
-    int a = wave + NW * i;
-    a = a < 2 * MT ? a : 2 * MT - 1;
-    const int row = a * 8 + rl;                                    // row of the padded MT x 16 tile
-    const int m = row < p.rows ? row : p.rows - 1;
-    asrc[i] = (const char*)(p.x + (size_t)m * K) + ((ul ^ dg_key(row & 15)) << 4);
-    adst[i] = (unsigned)a * 1024u;
-  }
-  const int chunks = K >> 6;
-  const int cpw = (chunks + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int c_begin = blockIdx.y * cpw;
-  const int c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
-  const int n_it = c_end - c_begin;
-
-  dg_f32x4 acc[R][MT];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[r][mt] = dg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dgw_smem;
-
-  // Workgroup b starts its walk at chunk (5 b) % n_it of its range and wraps: with everybody at chunk 0 every request in flight on the
-  // chip shares address bits 7..12 (rows are K * 2 bytes apart) and the HBM channels take turns instead of working side by side --
-  // tools/cu_stream_probe.hip, profiles/r05_cu_stream_probe.txt: 192 workgroups streaming 100 MB reach 5.5 TB/s in lock-step, 6.2 staggered.
-  const int stag = n_it > 0 ? (int)((blockIdx.x * 5u) % (unsigned)n_it) : 0;
-  auto issue = [&](int slot, int c) {
-    int j = c - c_begin + stag;
-    j = j >= n_it ? j - n_it : j;
-    int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads (the counts stay uniform)
-    cc = cc < chunks ? cc : chunks - 1;
-    const unsigned sbase = lds0 + (unsigned)slot * STAGE;
-#pragma unroll
-    for (int i = 0; i < AI; ++i) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(sbase + adst[i]), "v"(asrc[i] + (size_t)cc * 128) : "memory", "scc");
-    }
-    const unsigned wdst = sbase + ACT + (unsigned)wave * WST;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
-                   "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(wdst + r * 2048), "v"(wsrc[r][0] + (size_t)cc * 128), "v"(wsrc[r][1] + (size_t)cc * 128) : "memory", "scc");
-    }
-  };
-  auto consume = [&](int slot) {
-    const char* act = dgw_smem + slot * STAGE;
-    const char* wt = act + ACT + wave * WST;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int unit = ((ks * 4 + q) ^ dg_key(l16)) << 4;
-      dg_u32x4 bf[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(act + (mt * 16 + l16) * 128 + unit);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + unit);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(av, bf[mt], acc[r][mt]);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-#pragma unroll
-  for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
-  int slot = 0, fill = PF - 1;
-  const int n_main = n_it - (PF - 1);                  // iterations that still have a stage to ask for
-  for (int i = 0; i < n_main; ++i) {
-    dg_wait_vm<(PF - 2) * OPS>();                      // stage i has landed (this wave's pieces); PF - 2 younger stages stay in flight
-    __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with the slot of stage i - 1
-    asm volatile("" ::: "memory");
-    issue(fill, c_begin + i + PF - 1);
-    consume(slot);
-    slot = slot + 1 == PF ? 0 : slot + 1;
-    fill = fill + 1 == PF ? 0 : fill + 1;
-  }
-  // the last PF - 1 stages: nothing left to ask for (the deep rings used to re-request a chunk per iteration here, a tenth of the
-  // launch's LDS-DMA instructions at 64 chunks, a third at 16), the wait counts shrink with the ring
-  const int i_tail = n_main > 0 ? n_main : 0;
-  dg_static_for<PF - 1>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    if (i_tail + t < n_it) {                            // (uniform)
-      dg_wait_vm<(PF - 2 - t) * OPS>();
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      consume(slot);
-      slot = slot + 1 == PF ? 0 : slot + 1;
-    }
-  });
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
-
-  dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
-}
+//
+// ONE body for the three weight formats of this decomposition (decode_gemm_wide_kernel: 16-bit; decode_gemm_w8_kernel: MXVL_W_INT8;
+// decode_gemm_w4_kernel: MXVL_W_MXFP4; the latter two at every row count).  A weight row always arrives as whole 128-byte lines, so a
+// chunk is 64 x IMGS columns (IMGS = 1 / 2 / 4), the weight image of a stage is byte for byte the same in all three (16 rows x 128
+// bytes per tile, two DMA instructions, same XOR swizzle) and the activation image is IMGS of the 16-bit kernel's (columns 64 a ..
+// 64 a + 63 of the chunk, 2 IMGS MT one-kilobyte pieces).  Set-up, chunk arithmetic, the two LDS-DMA statements and the ring driver
+// are written once; a format trait (DgW16 / DgW8 / DgW4, below) supplies the constants and the tail rule, and the three steps that
+// really differ -- LDS image -> MFMAs of a stage, mxfp4's scale staging, int8's row scales -- are `if constexpr` branches of the
+// body, not calls into the trait: hipcc forms the LDS addresses of a called step differently (v_add3 becomes two v_add, the mxfp4
+// kernels gain 4..14 VGPRs and lose a wave or two of occupancy), whatever the inlining attribute.
 
 // ---- MXVL_W_INT8: row-wise absmax int8 weights (bitsandbytes' Int8Params storage), 16-bit activations, rows 1..80 ------------------
 //   y[m][n] = epi( s[n] * fp32( sum_k float(CB[n][k]) * float(x[m][k]) ) ),   s[n] = ws[n] / 127
@@ -618,168 +504,6 @@ template <> struct W8Cvt<EltF16> {
   }
 };
 
-template <typename E, int MT, int R, int NW, int PF>
-__global__ __launch_bounds__(NW * 64) void decode_gemm_w8_kernel(const DecodeGemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char dg8_smem[];
-  constexpr int AHALF = MT * 2048, ACT = 2 * AHALF, WST = R * 2048, STAGE = ACT + NW * WST;
-  constexpr int AI = (4 * MT + NW - 1) / NW;           // activation DMA instructions per wave and stage
-  constexpr int OPS = 2 * R + AI;
-  static_assert(PF >= 2 && (PF - 1) * OPS <= 63, "vmcnt is a 6-bit field");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l16 = lane & 15, q = lane >> 4;
-  const int K = p.K, N = p.N;
-  const int cols_per_wave = (p.swiglu ? R / 2 : R) * 16;
-  const int n0 = (blockIdx.x * NW + wave) * cols_per_wave;       // this wave's first output column
-  const int rl = lane >> 3, ul = lane & 7;
-  const char* wsrc[R][2];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
-    const char* base = (const char*)((p.swiglu && r >= R / 2) ? p.W2 : p.W);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = h * 8 + rl;
-      int n = n0 + t * 16 + row;
-      n = n < N ? n : N - 1;
-      wsrc[r][h] = base + (size_t)n * K + ((ul ^ dg_key(row)) << 4);
-    }
-  }
-  // bit 2 of a lane's source unit (ul ^ dg_key(row)) depends on bit 1 of the row only: the same for both DMA calls of a tile
-  const int wback = ((ul ^ dg_key(rl)) & 4) ? 64 : 0;
-  const char* asrc[AI];
-  unsigned adst[AI];
-  int aback[AI];
-#pragma unroll
-  for (int i = 0; i < AI; ++i) {
-    int a = wave + NW * i;
-    a = a < 4 * MT ? a : 4 * MT - 1;
-    const int half = a / (2 * MT), ap = a - half * 2 * MT;
-    const int row = ap * 8 + rl;                                   // row of the padded MT x 16 tile
-    const int m = row < p.rows ? row : p.rows - 1;
-    asrc[i] = (const char*)(p.x + (size_t)m * K) + half * 128 + ((ul ^ dg_key(row & 15)) << 4);
-    adst[i] = (unsigned)(half * AHALF + ap * 1024);
-    aback[i] = half * 128;
-  }
-  const int chunks = (K + 127) >> 7;
-  const bool half_tail = (K & 64) != 0;                            // the last chunk holds 64 columns
-  const int cpw = (chunks + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int c_begin = blockIdx.y * cpw;
-  const int c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
-  const int n_it = c_end - c_begin;
-
-  dg_f32x4 acc[R][MT];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[r][mt] = dg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dg8_smem;
-
-  // the walk over K staggered per workgroup, as in decode_gemm_wide_kernel
-  const int stag = n_it > 0 ? (int)((blockIdx.x * 5u) % (unsigned)n_it) : 0;
-  auto chunk_at = [&](int c) {
-    int j = c - c_begin + stag;
-    j = j >= n_it ? j - n_it : j;
-    const int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads
-    return cc < chunks ? cc : chunks - 1;
-  };
-  auto issue = [&](int slot, int c) {
-    const int cc = chunk_at(c);
-    const bool tail = half_tail && cc == chunks - 1;               // (uniform)
-    const unsigned sbase = lds0 + (unsigned)slot * STAGE;
-#pragma unroll
-    for (int i = 0; i < AI; ++i) {
-      unsigned keep;
-      const char* g = asrc[i] + ((long)cc * 256 - (tail ? aback[i] : 0));
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(sbase + adst[i])), "v"(g) : "memory", "scc");
-    }
-    const unsigned wdst = sbase + ACT + (unsigned)wave * WST;
-    const long woff = (long)cc * 128 - (tail ? wback : 0);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
-                   "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(wdst + r * 2048)), "v"(wsrc[r][0] + woff), "v"(wsrc[r][1] + woff) : "memory", "scc");
-    }
-  };
-  auto consume = [&](int slot, int c) {
-    const bool tail = half_tail && chunk_at(c) == chunks - 1;      // (uniform)
-    const char* act = dg8_smem + slot * STAGE;
-    const char* wt = act + ACT + wave * WST;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (j == 1 && tail) break;
-      const int wunit = ((j * 4 + q) ^ dg_key(l16)) << 4;
-      dg_u32x4 cv[R][2];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
-        uint32_t o[8];
-        W8Cvt<E>::cvt4(av.x, o[0], o[1]);
-        W8Cvt<E>::cvt4(av.y, o[2], o[3]);
-        W8Cvt<E>::cvt4(av.z, o[4], o[5]);
-        W8Cvt<E>::cvt4(av.w, o[6], o[7]);
-        cv[r][0] = dg_u32x4{o[0], o[1], o[2], o[3]};
-        cv[r][1] = dg_u32x4{o[4], o[5], o[6], o[7]};
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int aunit = ((q * 2 + h) ^ dg_key(l16)) << 4;
-        dg_u32x4 bf[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(act + j * AHALF + (mt * 16 + l16) * 128 + aunit);
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][h], bf[mt], acc[r][mt]);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-#pragma unroll
-  for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
-  int slot = 0, fill = PF - 1;
-  const int n_main = n_it - (PF - 1);                  // iterations that still have a stage to ask for
-  for (int i = 0; i < n_main; ++i) {
-    dg_wait_vm<(PF - 2) * OPS>();                      // stage i has landed (this wave's pieces); PF - 2 younger stages stay in flight
-    __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with the slot of stage i - 1
-    asm volatile("" ::: "memory");
-    issue(fill, c_begin + i + PF - 1);
-    consume(slot, c_begin + i);
-    slot = slot + 1 == PF ? 0 : slot + 1;
-    fill = fill + 1 == PF ? 0 : fill + 1;
-  }
-  const int i_tail = n_main > 0 ? n_main : 0;
-  dg_static_for<PF - 1>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    if (i_tail + t < n_it) {                            // (uniform)
-      dg_wait_vm<(PF - 2 - t) * OPS>();
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      consume(slot, c_begin + i_tail + t);
-      slot = slot + 1 == PF ? 0 : slot + 1;
-    }
-  });
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
-
-  // the row scales on the fp32 sums, then the epilogue of the wide kernel
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
-    const float* sp = (p.swiglu && r >= R / 2) ? p.ws2 : p.ws;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int n = n0 + t * 16 + 4 * q + v;
-      const float sc = n < N ? sp[n] / 127.0f : 0.0f;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[r][mt][v] *= sc;
-    }
-  }
-  dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
-}
-
 // ---- MXVL_W_MXFP4: OCP microscaling FP4 weights (E2M1 codes, one E8M0 scale per 32 along K), 16-bit activations, rows 1..80 ---------
 //   y[m][n] = epi( fp32( sum_k v[n][k] * 2^(e[n][k / 32] - 127) * x[m][k] ) )
 // W / W2 are (N, K / 2) bytes, the element of even k in the low nibble; wx / wx2 the (N, K / 32) E8M0 bytes.
@@ -813,88 +537,115 @@ template <> struct W4Cvt<EltF16> {
 // bytes of LDS per scale row for a K range of `cpw` chunks (host and kernel agree through this one function)
 __host__ __device__ constexpr int w4_scale_pitch(int cpw) { return cpw * 8 + 4; }
 
-template <typename E, int MT, int R, int NW, int PF>
-__global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char dg4_smem[];
-  constexpr int AQ = MT * 2048, ACT = 4 * AQ, WST = R * 2048, STAGE = ACT + NW * WST;
-  constexpr int AI = (8 * MT + NW - 1) / NW;           // activation DMA instructions per wave and stage
+// Format traits of dg_nsplit_body.  K % 64 == 0 always, so the last chunk of a row holds vq = (K / 64) % IMGS 64-column images (0: it
+// is whole); its DMA sources past the row are pulled back inside it by wback (weights: source unit ul ^ dg_key(row) of a lane) and
+// aback (the activation pieces of image img) bytes.
+struct DgW16 {                                           // a chunk is one image: every chunk is whole
+  static constexpr int IMGS = 1;
+  static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)(W + (size_t)n * K); }
+  static __device__ __forceinline__ int vq(int) { return 0; }
+  static __device__ __forceinline__ int wback(int, int, int) { return 0; }
+  static __device__ __forceinline__ int aback(int, int) { return 0; }
+  __host__ __device__ static constexpr int scale_lds(int, int, int) { return 0; }
+};
+struct DgW8 {                                            // weight units 4..7 re-read units 0..3, the second image's pieces re-read the first
+  static constexpr int IMGS = 2;
+  static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * K; }
+  static __device__ __forceinline__ bool vq(int K) { return (K & 64) != 0; }
+  // bit 2 of a lane's source unit depends on bit 1 of the row only: the same for both DMA calls of a tile
+  static __device__ __forceinline__ int wback(bool, int ul, int row) { return ((ul ^ dg_key(row & 7)) & 4) ? 64 : 0; }
+  static __device__ __forceinline__ int aback(bool, int img) { return img * 128; }
+  __host__ __device__ static constexpr int scale_lds(int, int, int) { return 0; }
+};
+struct DgW4 {                                            // weight units >= 2 vq re-read unit 0, images >= vq re-read image 0
+  static constexpr int IMGS = 4;
+  static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * (K >> 1); }
+  static __device__ __forceinline__ int vq(int K) { return (K >> 6) & 3; }
+  static __device__ __forceinline__ int wback(int vq, int ul, int row) { const int su = ul ^ dg_key(row); return su >= 2 * vq ? su << 4 : 0; }
+  static __device__ __forceinline__ int aback(int vq, int img) { return img >= vq ? img * 128 : 0; }
+  // LDS behind the ring: the waves' scale rows over a K range of `cpw` chunks (host and kernel agree through this one function)
+  __host__ __device__ static constexpr int scale_lds(int NW, int R, int cpw) { return NW * R * 16 * w4_scale_pitch(cpw); }
+};
+
+template <typename Fmt, typename E, int MT, int R, int NW, int PF>
+__device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
+  extern __shared__ __attribute__((aligned(16))) char dgn_smem[];
+  constexpr int IMGS = Fmt::IMGS, SH = 6 + (IMGS == 4 ? 2 : IMGS - 1);     // a chunk: 1 << SH columns
+  constexpr int AIMG = MT * 2048, ACT = IMGS * AIMG, WST = R * 2048, STAGE = ACT + NW * WST;
+  constexpr int AI = (2 * IMGS * MT + NW - 1) / NW;    // activation DMA instructions per wave and stage (a few waves repeat the last piece)
   constexpr int OPS = 2 * R + AI;
   static_assert(PF >= 2 && (PF - 1) * OPS <= 63, "vmcnt is a 6-bit field");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, q = lane >> 4;
   const int K = p.K, N = p.N;
-  const int KB = K >> 1, KS = K >> 5;                  // bytes of a weight row, of a scale row
   const int cols_per_wave = (p.swiglu ? R / 2 : R) * 16;
   const int n0 = (blockIdx.x * NW + wave) * cols_per_wave;       // this wave's first output column
   const int rl = lane >> 3, ul = lane & 7;
-  const int vq = (K >> 6) & 3;                         // quarters of the last chunk; 0: it is whole
+  const auto vq = Fmt::vq(K);                          // 64-column images of the last chunk; 0: it is whole
   const char* wsrc[R][2];
-  int wback[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int su = ul ^ dg_key(h * 8 + rl);
-    wback[h] = su >= 2 * vq ? su << 4 : 0;
-  }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
-    const char* base = (const char*)((p.swiglu && r >= R / 2) ? p.W2 : p.W);
+    const uint16_t* base = (p.swiglu && r >= R / 2) ? p.W2 : p.W;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int row = h * 8 + rl;
       int n = n0 + t * 16 + row;
       n = n < N ? n : N - 1;
-      wsrc[r][h] = base + (size_t)n * KB + ((ul ^ dg_key(row)) << 4);
+      wsrc[r][h] = Fmt::row(base, n, K) + ((ul ^ dg_key(row)) << 4);
     }
   }
+  int wback[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) wback[h] = Fmt::wback(vq, ul, h * 8 + rl);
   const char* asrc[AI];
   unsigned adst[AI];
   int aback[AI];
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     int a = wave + NW * i;
-    a = a < 8 * MT ? a : 8 * MT - 1;
-    const int quarter = a / (2 * MT), ap = a - quarter * 2 * MT;
+    a = a < 2 * IMGS * MT ? a : 2 * IMGS * MT - 1;
+    const int img = IMGS == 1 ? 0 : a / (2 * MT), ap = a - img * 2 * MT;
     const int row = ap * 8 + rl;                                   // row of the padded MT x 16 tile
     const int m = row < p.rows ? row : p.rows - 1;
-    asrc[i] = (const char*)(p.x + (size_t)m * K) + quarter * 128 + ((ul ^ dg_key(row & 15)) << 4);
-    adst[i] = (unsigned)(quarter * AQ + ap * 1024);
-    aback[i] = quarter >= vq ? quarter * 128 : 0;
+    asrc[i] = (const char*)(p.x + (size_t)m * K) + img * 128 + ((ul ^ dg_key(row & 15)) << 4);
+    adst[i] = (unsigned)(img * AIMG + ap * 1024);
+    aback[i] = Fmt::aback(vq, img);
   }
-  const int chunks = (K + 255) >> 8;
+  const int chunks = (K + (IMGS > 1 ? (1 << SH) - 1 : 0)) >> SH;
   const int cpw = (chunks + (int)gridDim.y - 1) / (int)gridDim.y;
   const int c_begin = blockIdx.y * cpw;
   const int c_end = c_begin + cpw < chunks ? c_begin + cpw : chunks;
   const int n_it = c_end - c_begin;
-  const int pitch = w4_scale_pitch(cpw);
-  char* const sc_l = dg4_smem + PF * STAGE + wave * (R * 16 * pitch);
 
   dg_f32x4 acc[R][MT];
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[r][mt] = dg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dg4_smem;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dgn_smem;
 
-  // the walk over K staggered per workgroup, as in decode_gemm_wide_kernel
+  // Workgroup b starts its walk at chunk (5 b) % n_it of its range and wraps: with everybody at chunk 0 every request in flight on the
+  // chip shares address bits 7..12 (rows are K * 2 bytes apart) and the HBM channels take turns instead of working side by side --
+  // tools/cu_stream_probe.hip, profiles/r05_cu_stream_probe.txt: 192 workgroups streaming 100 MB reach 5.5 TB/s in lock-step, 6.2 staggered.
   const int stag = n_it > 0 ? (int)((blockIdx.x * 5u) % (unsigned)n_it) : 0;
   auto chunk_at = [&](int c) {
     int j = c - c_begin + stag;
     j = j >= n_it ? j - n_it : j;
-    const int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads
+    const int cc = c < c_end ? c_begin + j : c_begin;       // past the range: a harmless repeat into a slot nobody reads (the counts stay uniform)
     return cc < chunks ? cc : chunks - 1;
   };
   auto issue = [&](int slot, int c) {
     const int cc = chunk_at(c);
-    const bool tail = vq != 0 && cc == chunks - 1;                 // (uniform)
+    const bool tail = vq && cc == chunks - 1;                 // (uniform)
     const unsigned sbase = lds0 + (unsigned)slot * STAGE;
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
       unsigned keep;
-      const char* g = asrc[i] + ((long)cc * 512 - (tail ? aback[i] : 0));
+      const char* g = asrc[i] + ((long)cc * (128 * IMGS) - (tail ? aback[i] : 0));
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(sbase + adst[i])), "v"(g) : "memory", "scc");
+                   : "=&s"(keep) : "s"(sbase + adst[i]), "v"(g) : "memory", "scc");
     }
     const unsigned wdst = sbase + ACT + (unsigned)wave * WST;
     const long woff0 = (long)cc * 128 - (tail ? wback[0] : 0), woff1 = (long)cc * 128 - (tail ? wback[1] : 0);
@@ -903,56 +654,20 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGem
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
                    "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(__builtin_amdgcn_readfirstlane(wdst + r * 2048)), "v"(wsrc[r][0] + woff0), "v"(wsrc[r][1] + woff1) : "memory", "scc");
+                   : "=&s"(keep) : "s"(wdst + r * 2048), "v"(wsrc[r][0] + woff0), "v"(wsrc[r][1] + woff1) : "memory", "scc");
     }
-  };
-  auto consume = [&](int slot, int c) {
-    const int cc = chunk_at(c);
-    const bool tail = vq != 0 && cc == chunks - 1;                 // (uniform)
-    const char* act = dg4_smem + slot * STAGE;
-    const char* wt = act + ACT + wave * WST;
-    const char* sc = sc_l + (cc - c_begin) * 8 + l16 * pitch;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (tail && 2 * j >= vq) break;                              // blocks 4 j .. 4 j + 3 all lie past the row
-      const int u = 4 * j + q;
-      const bool dead = tail && u >= 2 * vq;                       // this lane's block lies past the row
-      const int wunit = (u ^ dg_key(l16)) << 4;
-      dg_u32x4 cv[R][4];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
-        const uint32_t e = *(const uint8_t*)(sc + r * 16 * pitch + u);
-        const float s = __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);      // 2^(e - 127); e = 0 is fp32's subnormal 2^-127
-        if (dead) av = dg_u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          cv[r][i] = dg_u32x4{W4Cvt<E>::template cvt2<0>(av[i], s), W4Cvt<E>::template cvt2<1>(av[i], s),
-                              W4Cvt<E>::template cvt2<2>(av[i], s), W4Cvt<E>::template cvt2<3>(av[i], s)};
-      }
-      const char* aq = act + (2 * j + (q >> 1)) * AQ + l16 * 128;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int aunit = ((4 * (q & 1) + i) ^ dg_key(l16)) << 4;
-        dg_u32x4 bf[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(aq + mt * 2048 + aunit);
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][i], bf[mt], acc[r][mt]);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
 #pragma unroll
   for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
-
-  // this wave's scale bytes over the workgroup's K range: 4 rows x 16 lanes per pass.  (The loads' results are waited for with
-  // vmcnt(0), i.e. together with the ring's prologue, which the first iteration needs anyway.)
-  {
+  // mxfp4: this wave's scale bytes over the workgroup's K range into LDS behind the ring, 4 rows x 16 lanes per pass.  (The loads'
+  // results are waited for with vmcnt(0), i.e. together with the ring's prologue, which the first iteration needs anyway.)
+  struct { const char* rows; int pitch; } sc{};
+  if constexpr (IMGS == 4) {
+    const int KS = K >> 5;                  // bytes of a scale row
+    const int pitch = w4_scale_pitch(cpw);
+    char* const sc_l = dgn_smem + PF * STAGE + wave * (R * 16 * pitch);
     const int sbeg = c_begin * 8, sbytes = n_it * 8;
-    auto stage_scales = [&](auto unit) {
+    auto copy = [&](auto unit) {
       typedef decltype(unit) U;
       constexpr int PASSES = R * 4, CB = 4, US = (int)sizeof(U);
       const int upr = sbytes / US;                       // units per row; <= 0: this workgroup has no chunk
@@ -986,8 +701,93 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGem
           }
       }
     };
-    if ((KS & 3) == 0) stage_scales(uint32_t{0}); else stage_scales(uint16_t{0});
+    if ((KS & 3) == 0) copy(uint32_t{0}); else copy(uint16_t{0});
+    sc = {sc_l, pitch};
   }
+  auto consume = [&](int slot, int c) {
+    const int cc = chunk_at(c);
+    const char* act = dgn_smem + slot * STAGE;
+    const char* wt = act + ACT + wave * WST;
+    const bool tail = vq && cc == chunks - 1;                      // (uniform)
+    if constexpr (IMGS == 1) {                                     // 16-bit: the plain operand
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int unit = ((ks * 4 + q) ^ dg_key(l16)) << 4;
+        dg_u32x4 bf[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(act + (mt * 16 + l16) * 128 + unit);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + unit);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(av, bf[mt], acc[r][mt]);
+        }
+      }
+    } else if constexpr (IMGS == 2) {                              // int8: 16 codes of row l16 widened to two A operands
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (j == 1 && tail) break;
+        const int wunit = ((j * 4 + q) ^ dg_key(l16)) << 4;
+        dg_u32x4 cv[R][2];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
+          uint32_t o[8];
+          W8Cvt<E>::cvt4(av.x, o[0], o[1]);
+          W8Cvt<E>::cvt4(av.y, o[2], o[3]);
+          W8Cvt<E>::cvt4(av.z, o[4], o[5]);
+          W8Cvt<E>::cvt4(av.w, o[6], o[7]);
+          cv[r][0] = dg_u32x4{o[0], o[1], o[2], o[3]};
+          cv[r][1] = dg_u32x4{o[4], o[5], o[6], o[7]};
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int aunit = ((q * 2 + h) ^ dg_key(l16)) << 4;
+          dg_u32x4 bf[MT];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(act + j * (MT * 2048) + (mt * 16 + l16) * 128 + aunit);
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][h], bf[mt], acc[r][mt]);
+        }
+      }
+    } else {                                                       // mxfp4: 32 codes = one scale block, four A operands
+      const char* scp = sc.rows + (cc - c_begin) * 8 + l16 * sc.pitch;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (tail && 2 * j >= vq) break;                              // blocks 4 j .. 4 j + 3 all lie past the row
+        const int u = 4 * j + q;
+        const bool dead = tail && u >= 2 * vq;                       // this lane's block lies past the row
+        const int wunit = (u ^ dg_key(l16)) << 4;
+        dg_u32x4 cv[R][4];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
+          const uint32_t e = *(const uint8_t*)(scp + r * 16 * sc.pitch + u);
+          const float s = __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);      // 2^(e - 127); e = 0 is fp32's subnormal 2^-127
+          if (dead) av = dg_u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            cv[r][i] = dg_u32x4{W4Cvt<E>::template cvt2<0>(av[i], s), W4Cvt<E>::template cvt2<1>(av[i], s),
+                                W4Cvt<E>::template cvt2<2>(av[i], s), W4Cvt<E>::template cvt2<3>(av[i], s)};
+        }
+        const char* aq = act + (2 * j + (q >> 1)) * (MT * 2048) + l16 * 128;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int aunit = ((4 * (q & 1) + i) ^ dg_key(l16)) << 4;
+          dg_u32x4 bf[MT];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) bf[mt] = *(const dg_u32x4*)(aq + mt * 2048 + aunit);
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][i], bf[mt], acc[r][mt]);
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
 
   int slot = 0, fill = PF - 1;
   const int n_main = n_it - (PF - 1);                  // iterations that still have a stage to ask for
@@ -1000,6 +800,8 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGem
     slot = slot + 1 == PF ? 0 : slot + 1;
     fill = fill + 1 == PF ? 0 : fill + 1;
   }
+  // the last PF - 1 stages: nothing left to ask for (the deep rings used to re-request a chunk per iteration here, a tenth of the
+  // launch's LDS-DMA instructions at 64 chunks, a third at 16), the wait counts shrink with the ring
   const int i_tail = n_main > 0 ? n_main : 0;
   dg_static_for<PF - 1>([&](auto tc) {
     constexpr int t = decltype(tc)::value;
@@ -1013,8 +815,29 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGem
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
 
+  if constexpr (IMGS == 2) {                           // int8: the row scales on the fp32 sums
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
+      const float* sp = (p.swiglu && r >= R / 2) ? p.ws2 : p.ws;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int n = n0 + t * 16 + 4 * q + v;
+        const float sc = n < N ? sp[n] / 127.0f : 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[r][mt][v] *= sc;
+      }
+    }
+  }
   dgw_epilogue<E, MT, R>(p, acc, n0, l16, q);
 }
+
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW16, E, MT, R, NW, PF>(p); }
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w8_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW8, E, MT, R, NW, PF>(p); }
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW4, E, MT, R, NW, PF>(p); }
 
 // RMSNorm of the activation rows ahead of a projection (Qwen2RMSNorm / LlamaRMSNorm, EMRRG/models/hybrid_decoder_layer.py:185-199):
 // y = bf16( bf16(x * rsqrt(mean(x^2) + eps)) * g ), statistics in fp32.  One workgroup per row.  (At <= 8 rows the GEMV kernel

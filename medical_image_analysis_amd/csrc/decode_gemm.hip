@@ -1,6 +1,7 @@
 // decode_gemm.hip -- host side of the 9..80-row decoder projections (kernels: decode_gemm.h) and of mxvl_decode_rmsnorm.
 // mxvl_decode_gemv (decode.hip) forwards here for rows > 8, so the stepper has ONE projection entry for every row count the
 // reference's launch scripts decode at (MambaXrayVL_DownStream.py:292-301; 3 .. 80 rows).
+#include <initializer_list>
 #include "decode_gemm.h"
 
 namespace mxvl {
@@ -40,176 +41,121 @@ static int launch_direct(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   return launch_status();
 }
 
-// MT >= 2 (17..80 rows), K % 64 == 0, >= 64 workgroups: the waves split N, activations shared through LDS (decode_gemm_wide_kernel)
-// ring depth of the wide kernel: as many stages as 150 KB of LDS hold (one workgroup per CU is all these grids ask for), capped by the
-// 6-bit vmcnt field and at 8 -- against the first version's 3 stages: 48-row token +5 %, 80-row +0.7 % (profiles/r05_decode_gemm_ring_ab.txt)
-constexpr int wide_pf(int MT, int R, int NW) {
-  const int stage = MT * 2048 + NW * R * 2048, ops = 2 * R + (2 * MT + NW - 1) / NW;
-  int pf = (150 * 1024) / stage;
+// ---- the N-split ring kernels (decode_gemm.h dg_nsplit_body): 16-bit weights at 17..80 rows (decode_gemm_wide_kernel), MXVL_W_INT8
+// (decode_gemm_w8_kernel) and MXVL_W_MXFP4 (decode_gemm_w4_kernel) at every row count ------------------------------------------------
+// ring depth: as many stages of `stage` bytes as `budget` bytes of LDS hold (one workgroup per CU is all these grids ask for), capped
+// by the 6-bit vmcnt field (`ops` requests per stage) and at 8 -- against the first version's 3 stages: 48-row token +5 %, 80-row
+// +0.7 % (profiles/r05_decode_gemm_ring_ab.txt)
+constexpr int ring_depth(int stage, int ops, int budget) {
+  int pf = budget / stage;
   while (pf > 2 && (pf - 1) * ops > 63) --pf;
   return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
+}
+// LDS budgets: the ring gets 150 KB; with mxfp4 112 KB, and the waves' scale rows up to 48 KB (Llama-7B's K = 11008 unsplit at two
+// tiles per wave needs 43.5)
+constexpr int kRingBytes = 150 * 1024, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
+// a stage: IMGS activation images of MT tiles + NW x R weight tiles, 2 R + ceil(2 IMGS MT / NW) requests per wave
+template <typename Fmt> constexpr int nsplit_stage(int MT, int R, int NW) { return Fmt::IMGS * MT * 2048 + NW * R * 2048; }
+template <typename Fmt> constexpr int nsplit_pf(int MT, int R, int NW) {
+  return ring_depth(nsplit_stage<Fmt>(MT, R, NW), 2 * R + (2 * Fmt::IMGS * MT + NW - 1) / NW, std::is_same_v<Fmt, DgW4> ? kW4RingBytes : kRingBytes);
+}
+template <typename Fmt> static int nsplit_cpw(const DecodeGemmArgs& a, int splits) {      // chunks of a workgroup's K range
+  return ((a.K + 64 * Fmt::IMGS - 1) / (64 * Fmt::IMGS) + splits - 1) / splits;
 }
 static int g_wide_pf3 = 0;     // (A/B: mxvl_set_decode_gemm_wide(3) = the 3-stage ring of the first version)
 static int g_wide_nw4 = 0;     // (A/B: mxvl_set_decode_gemm_wide(4) = four waves per workgroup everywhere)
 static int g_wide_min_mt = 2;  // wide from 17 rows on (A/B: mode 5 = from 33 rows on, as first shipped; mode 6 = from 1 row on)
 static int g_wide_min_g = 64;  // ... for grids of at least 64 workgroups (A/B: mode 5 = 160)
+static int g_decode_gemm_wide = 1;        // mxvl_set_decode_gemm_wide: the A/B switch of tools / bench (default on; 2: also at 17..32 rows)
 
-template <typename E, int MT, int R, int NW, int PF>
-static int launch_wide_pf(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+template <typename Fmt, typename E, int MT, int R, int NW, int PF>
+static int launch_nsplit(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
   const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
-  const size_t lds = (size_t)PF * (MT * 2048 + NW * R * 2048);
-  auto kern = decode_gemm_wide_kernel<E, MT, R, NW, PF>;
+  const size_t lds = (size_t)PF * nsplit_stage<Fmt>(MT, R, NW) + (size_t)Fmt::scale_lds(NW, R, nsplit_cpw<Fmt>(a, splits));
+  void (*kern)(const DecodeGemmArgs);
+  if constexpr (std::is_same_v<Fmt, DgW8>) kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
+  else if constexpr (std::is_same_v<Fmt, DgW4>) kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
+  else kern = decode_gemm_wide_kernel<E, MT, R, NW, PF>;
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
   return launch_status();
 }
 
-template <typename E, int MT, int R, int NW = 4>
-static int launch_wide(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  if constexpr (NW == 4) { if (g_wide_pf3) return launch_wide_pf<E, MT, R, 4, 3>(a, splits, s); }
-  return launch_wide_pf<E, MT, R, NW, wide_pf(MT, R, NW)>(a, splits, s);
-}
-
-static int g_decode_gemm_wide = 1;        // mxvl_set_decode_gemm_wide: the A/B switch of tools / bench (default on; 2: also at 17..32 rows)
-
-// The wide kernel's plan for a launch, or false: the K-split kernels keep it.  Shared by the launch below and by mxvl_decode_gemm_plan
-// (the dispatch as a pure function of the descriptor: tests/test_abi.py pins it for the reference's decoder shapes without a GPU).
+// The N-split kernels' plan for a launch, shared by the launch below and by mxvl_decode_gemm_plan (the dispatch as a pure function
+// of the descriptor: tests/test_abi.py pins it for the reference's decoder shapes without a GPU).
 // What bounds these launches is what ONE CU can pull through its load path, weights and activations together (~50 GB/s of
 // full-line LDS-DMA, tools/cu_stream_probe.hip -- HBM needs 27 GB/s from each of 256 CUs): a workgroup of NW waves x R tiles
-// moves 1 + MT / (NW R) bytes per weight byte, and the launch is as long as its busiest CU.  So: the (NW, R) with the least
-//   (1 + MT / (NW R)) x rounds / workgroups,      rounds = ceil(workgroups / 256)   (the LDS ring leaves one workgroup per CU)
+// moves 1 + f MT / (NW R) bytes per weight byte (f = 1 / 2 / 4 for 16-bit / int8 / mxfp4 weights: the weight bytes halve, the
+// activations do not), and the launch is as long as its busiest CU.  So: of the candidates, the (NW, R) with the least
+//   (1 + f MT / (NW R)) x rounds / workgroups,      rounds = ceil(workgroups / 256)   (the LDS ring leaves one workgroup per CU)
 // -- three waves per workgroup when that fills the chip: 230 workgroups for Llama's gate / up (172 with four waves), 256 for qkv (192).
-// From 17 rows and 64 workgroups on (profiles/r05_decode_gemm_wide_rows_ab.txt: against the K-split kernels the 18-row token
-// +7 %, the 24-row token +11 %, Qwen1.5-1.8B's 96..128-workgroup projections +4 % at 80 rows; the first version -- 3-stage
-// ring, aligned walks -- had lost to them below 160 workgroups and at 17..32 rows).  At 1..16 rows the K-split kernel keeps the
-// launches: it carries the fused RMSNorm, and without it the wide kernel is +2 % (Llama) / 0 % (Qwen) there.
+// (For f = 2, 4 a starting point: the 16-bit kernels' model, not a measurement of half- and quarter-size tiles.)
 struct WidePlan { int nw, r; long g; };
-static bool wide_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
-  if (!(g_decode_gemm_wide && MT >= g_wide_min_mt && a.K % 64 == 0 && a.K >= 256 && !a.g)) return false;
-  pl = WidePlan{0, 0, 0};
+template <typename Fits>
+static WidePlan nsplit_plan(int f, int MT, const DecodeGemmArgs& a, int splits, std::initializer_list<WidePlan> cands, Fits fits) {
+  WidePlan pl{0, 0, 0};
   double best = 1e30;
-  for (int nw : {4, 3}) {
-    if (nw == 3 && g_wide_nw4) continue;
-    for (int r : {1, 2, 4}) {
-      if (a.swiglu && (r & 1)) continue;
-      if (nw == 3 && r == 4) continue;
-      const int cols = nw * (a.swiglu ? r / 2 : r) * 16;
-      const long g = (long)((a.N + cols - 1) / cols) * splits;
-      const double est = (1.0 + (double)MT / (nw * r)) * (double)((g + 255) / 256) / (double)g;
-      if (est < best - 1e-12) { best = est; pl = WidePlan{nw, r, g}; }
-    }
-  }
-  return pl.g >= g_wide_min_g;
-}
-
-// ---- MXVL_W_INT8 (decode_gemm_w8_kernel): one kernel at every row count -------------------------------------------------------------
-// ring depth: as many stages of (two activation half-tiles + NW x R weight tiles) as 150 KB of LDS hold, capped by vmcnt and at 8
-constexpr int w8_pf(int MT, int R, int NW) {
-  const int stage = MT * 4096 + NW * R * 2048, ops = 2 * R + (4 * MT + NW - 1) / NW;
-  int pf = (150 * 1024) / stage;
-  while (pf > 2 && (pf - 1) * ops > 63) --pf;
-  return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
-}
-constexpr int kW8Waves = 4;
-// The wide kernel's estimate with the weight bytes halved: a workgroup pulls 1 + 2 MT / (NW R) bytes per weight byte, the launch is
-// as long as its busiest CU.  (A starting point: the 16-bit kernels' model, not a measurement of half-size tiles.)
-static WidePlan w8_plan(int MT, const DecodeGemmArgs& a, int splits) {
-  WidePlan pl{kW8Waves, a.swiglu ? 2 : 1, 0};
-  double best = 1e30;
-  for (int r : {1, 2}) {            // (four tiles per wave leave the ring two or three stages at 33..80 rows and no registers for the widened operands)
-    if (a.swiglu && (r & 1)) continue;
-    const int cols = kW8Waves * (a.swiglu ? r / 2 : r) * 16;
+  for (const WidePlan& c : cands) {
+    if ((a.swiglu && (c.r & 1)) || !fits(c)) continue;
+    const int cols = c.nw * (a.swiglu ? c.r / 2 : c.r) * 16;
     const long g = (long)((a.N + cols - 1) / cols) * splits;
-    const double est = (1.0 + 2.0 * MT / (kW8Waves * r)) * (double)((g + 255) / 256) / (double)g;
-    if (est < best - 1e-12) { best = est; pl = WidePlan{kW8Waves, r, g}; }
+    const double est = (1.0 + (double)(f * MT) / (c.nw * c.r)) * (double)((g + 255) / 256) / (double)g;
+    if (est < best - 1e-12) { best = est; pl = WidePlan{c.nw, c.r, g}; }
   }
   return pl;
 }
-
-template <typename E, int MT, int R>
-static int launch_w8_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  constexpr int NW = kW8Waves, PF = w8_pf(MT, R, NW);
-  const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
-  const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
-  const size_t lds = (size_t)PF * (MT * 4096 + NW * R * 2048);
-  auto kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
-  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
-    return MXVL_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return launch_status();
-}
-
-template <typename E, int MT>
-static int launch_w8(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  switch (w8_plan(MT, a, splits).r) {
-    case 2: return launch_w8_r<E, MT, 2>(a, splits, s);
-    default: return launch_w8_r<E, MT, 1>(a, splits, s);
+// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 = the 16-bit / int8 / mxfp4 N-split kernel with `pl`, 0 = the
+// K-split kernels keep it, < 0 = an error
+static int decode_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
+  // quantised: four waves, one or two tiles per wave (four leave the ring two or three stages at 33..80 rows and no registers for
+  // the widened operands)
+  if (a.ws) {
+    pl = nsplit_plan(DgW8::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [](const WidePlan&) { return true; });
+    return 3;
   }
-}
-
-// ---- MXVL_W_MXFP4 (decode_gemm_w4_kernel): one kernel at every row count ------------------------------------------------------------
-// LDS: the ring gets 112 KB (stages of four activation quarter-tiles + NW x R weight tiles), the waves' scale rows up to 48 KB
-// (Llama-7B's K = 11008 unsplit at two tiles per wave needs 43.5).
-constexpr int kW4Waves = 4, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
-constexpr int w4_pf(int MT, int R, int NW) {
-  const int stage = MT * 8192 + NW * R * 2048, ops = 2 * R + (8 * MT + NW - 1) / NW;
-  int pf = kW4RingBytes / stage;
-  while (pf > 2 && (pf - 1) * ops > 63) --pf;
-  return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
-}
-static int w4_cpw(const DecodeGemmArgs& a, int splits) { return ((a.K + 255) / 256 + splits - 1) / splits; }
-static bool w4_fits(const DecodeGemmArgs& a, int splits, int r) { return kW4Waves * r * 16 * w4_scale_pitch(w4_cpw(a, splits)) <= kW4ScaleBytes; }
-// w8_plan's estimate with the weight bytes halved again: a workgroup pulls 1 + 4 MT / (NW R) bytes per weight byte.  Two tiles per
-// wave need the K range of a workgroup to be at most 12032 columns (the scale rows' share of LDS), one tile 24320.
-static bool w4_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
-  pl = WidePlan{kW4Waves, 0, 0};
-  double best = 1e30;
-  for (int r : {1, 2}) {
-    if ((a.swiglu && (r & 1)) || !w4_fits(a, splits, r)) continue;
-    const int cols = kW4Waves * (a.swiglu ? r / 2 : r) * 16;
-    const long g = (long)((a.N + cols - 1) / cols) * splits;
-    const double est = (1.0 + 4.0 * MT / (kW4Waves * r)) * (double)((g + 255) / 256) / (double)g;
-    if (est < best - 1e-12) { best = est; pl = WidePlan{kW4Waves, r, g}; }
+  if (a.wx) {     // the scale rows' share of LDS: two tiles per wave up to a K range of 12032 columns per workgroup, one tile up to 24320
+    const int cpw = nsplit_cpw<DgW4>(a, splits);
+    pl = nsplit_plan(DgW4::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [&](const WidePlan& c) { return DgW4::scale_lds(c.nw, c.r, cpw) <= kW4ScaleBytes; });
+    return pl.r ? 4 : MXVL_ERR_UNSUPPORTED;
   }
-  return pl.r != 0;
+  // 16-bit: from 17 rows and 64 workgroups on (profiles/r05_decode_gemm_wide_rows_ab.txt: against the K-split kernels the 18-row token
+  // +7 %, the 24-row token +11 %, Qwen1.5-1.8B's 96..128-workgroup projections +4 % at 80 rows; the first version -- 3-stage
+  // ring, aligned walks -- had lost to them below 160 workgroups and at 17..32 rows).  At 1..16 rows the K-split kernel keeps the
+  // launches: it carries the fused RMSNorm, and without it the wide kernel is +2 % (Llama) / 0 % (Qwen) there.
+  if (!(g_decode_gemm_wide && MT >= g_wide_min_mt && a.K % 64 == 0 && a.K >= 256 && !a.g)) return 0;
+  pl = nsplit_plan(DgW16::IMGS, MT, a, splits, {{4, 1}, {4, 2}, {4, 4}, {3, 1}, {3, 2}}, [](const WidePlan& c) { return c.nw == 4 || !g_wide_nw4; });
+  return pl.g >= g_wide_min_g ? 1 : 0;
+}
+// ring depth of a planned launch
+template <typename Fmt> static int plan_pf(int MT, const WidePlan& pl) {
+  return std::is_same_v<Fmt, DgW16> && pl.nw == 4 && g_wide_pf3 ? 3 : nsplit_pf<Fmt>(MT, pl.r, pl.nw);
 }
 
-template <typename E, int MT, int R>
-static int launch_w4_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  constexpr int NW = kW4Waves, PF = w4_pf(MT, R, NW);
-  const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
-  const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
-  const size_t lds = (size_t)PF * (MT * 8192 + NW * R * 2048) + (size_t)NW * R * 16 * w4_scale_pitch(w4_cpw(a, splits));
-  auto kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
-  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
-    return MXVL_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
-  return launch_status();
+template <typename Fmt, typename E, int MT, int R, int NW>
+static int launch_nsplit_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  if constexpr (std::is_same_v<Fmt, DgW16> && NW == 4) { if (g_wide_pf3) return launch_nsplit<Fmt, E, MT, R, 4, 3>(a, splits, s); }
+  return launch_nsplit<Fmt, E, MT, R, NW, nsplit_pf<Fmt>(MT, R, NW)>(a, splits, s);
 }
-
-template <typename E, int MT>
-static int launch_w4(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  WidePlan pl;
-  if (!w4_plan(MT, a, splits, pl)) return MXVL_ERR_UNSUPPORTED;
-  return pl.r == 2 ? launch_w4_r<E, MT, 2>(a, splits, s) : launch_w4_r<E, MT, 1>(a, splits, s);
+template <typename Fmt, typename E, int MT>
+static int launch_planned(const WidePlan& pl, const DecodeGemmArgs& a, int splits, hipStream_t s) {
+  if constexpr (std::is_same_v<Fmt, DgW16>) {
+    if (pl.nw == 3) return pl.r == 2 ? launch_nsplit_r<Fmt, E, MT, 2, 3>(a, splits, s) : launch_nsplit_r<Fmt, E, MT, 1, 3>(a, splits, s);
+    if (pl.r == 4) return launch_nsplit_r<Fmt, E, MT, 4, 4>(a, splits, s);
+  }
+  return pl.r == 2 ? launch_nsplit_r<Fmt, E, MT, 2, 4>(a, splits, s) : launch_nsplit_r<Fmt, E, MT, 1, 4>(a, splits, s);
 }
 
 template <typename E, int MT>
 static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  if (a.ws) return launch_w8<E, MT>(a, splits, s);
-  if (a.wx) return launch_w4<E, MT>(a, splits, s);
-  {
-    WidePlan pl;
-    if (wide_plan(MT, a, splits, pl)) {
-      if (pl.nw == 3) return pl.r == 2 ? launch_wide<E, MT, 2, 3>(a, splits, s) : launch_wide<E, MT, 1, 3>(a, splits, s);
-      switch (pl.r) {
-        case 4: return launch_wide<E, MT, 4>(a, splits, s);
-        case 2: return launch_wide<E, MT, 2>(a, splits, s);
-        default: return launch_wide<E, MT, 1>(a, splits, s);
-      }
-    }
+  WidePlan pl;
+  switch (const int kind = decode_plan(MT, a, splits, pl)) {
+    case 0: break;
+    case 1: return launch_planned<DgW16, E, MT>(pl, a, splits, s);
+    case 3: return launch_planned<DgW8, E, MT>(pl, a, splits, s);
+    case 4: return launch_planned<DgW4, E, MT>(pl, a, splits, s);
+    default: return kind;
   }
   // R = weight tiles per workgroup.  Two effects, both measured (tools/decode_gemm_bench.py A/B at 18 rows, profiles/r04_decode_gemm_r_sweep.txt):
   // (1) a CU streams ~28 GB/s whatever it holds, so the workgroups must fill whole rounds of the 256 CUs -- 344 workgroups (gate / up
@@ -263,38 +209,19 @@ int decode_gemm_dispatch(const mxvl_gemv_desc* d, hipStream_t s) {
   return decode_dtype(d->dtype & ~kWeightFlags) == MXVL_F16 ? launch_decode_gemm_rows<EltF16>(a, splits, s) : launch_decode_gemm_rows<EltBf16>(a, splits, s);
 }
 
-// the wide kernel's ring depth for a plan, as launch_wide picks it
-static int wide_plan_pf(int MT, const WidePlan& pl) {
-  if (pl.nw == 4 && g_wide_pf3) return 3;
-  int pf = 2;
-  for (int mt = 1; mt <= 5; ++mt) for (int r : {1, 2, 4}) for (int nw : {3, 4}) if (mt == MT && r == pl.r && nw == pl.nw) pf = wide_pf(mt, r, nw);
-  return pf;
-}
-
+// out: kind (decode_plan), then waves, tiles per wave, ring stages, workgroups of the N-split kernel; kind 0: zeros
 int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   DecodeGemmArgs a;
   int splits = 1;
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
   const int MT = (a.rows + 15) / 16 > 5 ? 5 : (a.rows + 15) / 16;
-  if (a.ws) {                       // MXVL_W_INT8: out[0] = 3, then waves, tiles per wave, ring stages, workgroups of decode_gemm_w8_kernel
-    const WidePlan w = w8_plan(MT, a, splits);
-    out[0] = 3; out[1] = w.nw; out[2] = w.r; out[3] = w8_pf(MT, w.r, kW8Waves); out[4] = (int32_t)w.g;
-    return MXVL_OK;
-  }
-  if (a.wx) {                       // MXVL_W_MXFP4: out[0] = 4, then the same four figures of decode_gemm_w4_kernel
-    WidePlan w;
-    if (!w4_plan(MT, a, splits, w)) return MXVL_ERR_UNSUPPORTED;
-    out[0] = 4; out[1] = w.nw; out[2] = w.r; out[3] = w4_pf(MT, w.r, kW4Waves); out[4] = (int32_t)w.g;
-    return MXVL_OK;
-  }
   WidePlan pl;
-  const bool wide = wide_plan(MT, a, splits, pl);
-  out[0] = wide ? 1 : 0;
-  out[1] = wide ? pl.nw : 0;
-  out[2] = wide ? pl.r : 0;
-  out[3] = wide ? wide_plan_pf(MT, pl) : 0;
-  out[4] = wide ? (int32_t)pl.g : 0;
+  const int kind = decode_plan(MT, a, splits, pl);
+  if (kind < 0) return kind;
+  if (kind == 0) pl = WidePlan{0, 0, 0};
+  out[0] = kind; out[1] = pl.nw; out[2] = pl.r; out[4] = (int32_t)pl.g;
+  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : plan_pf<DgW4>(MT, pl);
   return MXVL_OK;
 }
 

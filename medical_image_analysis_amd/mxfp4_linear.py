@@ -10,15 +10,14 @@ even k in the low nibble: 4.25 bits per weight.
 The represented weight value(code) * 2^X is exact in bf16, and in fp16 for X in [-15, 13] (the quantiser refuses an fp16 weight
 outside that range).  The decode step reads codes and scales directly (mxvl_decode_gemv with MXVL_W_MXFP4, csrc/decode_gemm.h
 decode_gemm_w4_kernel); prompt prefill and stage-3 training through the frozen LLM dequantise one weight at a time into the scratch
-buffer the int8 path uses (int8_linear.DequantScratch) and run F.linear on it, in eager torch.  What 4-bit weights cost in report
+buffer the int8 path uses (quant_linear.DequantScratch) and run F.linear on it, in eager torch.  What 4-bit weights cost in report
 quality is not measured here."""
 from __future__ import annotations
 
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
-from .int8_linear import DequantScratch
+from ._abi import MXVL_W_MXFP4
+from .quant_linear import QuantLinear
 
 BLOCK = 32
 FP16_X_RANGE = (-15, 13)                                        # 0.5 * 2^-15 = fp16's 2^-16 (subnormal, exact) .. 6 * 2^13 = 49152
@@ -65,63 +64,14 @@ def dequantize_mxfp4(packed, scale, dtype, out=None):
     return view
 
 
-class _MxFp4LinearFn(torch.autograd.Function):
-    """F.linear on the dequantised weight; saves codes and scales only (never the 16-bit weight), backward re-creates it:
-    dx = dy @ Wdq.  The weight gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, x, packed, scale, bias, scratch, dtype):
-        w = dequantize_mxfp4(packed, scale, dtype, scratch.get(packed.numel() * 2, dtype, packed.device))
-        ctx.save_for_backward(packed, scale)
-        ctx.scratch, ctx.wdtype, ctx.xdtype = scratch, dtype, x.dtype
-        return F.linear(x, w, bias)
-
-    @staticmethod
-    def backward(ctx, dy):
-        packed, scale = ctx.saved_tensors
-        w = dequantize_mxfp4(packed, scale, ctx.wdtype, ctx.scratch.get(packed.numel() * 2, ctx.wdtype, packed.device))
-        dx = (dy.to(ctx.wdtype) @ w).to(ctx.xdtype)
-        return dx, None, None, None, None, None
-
-
-class MxFp4Linear(nn.Module):
+class MxFp4Linear(QuantLinear):
     """nn.Linear with a frozen MXFP4 weight.  Buffers `weight_packed` (uint8, (N, K / 2)), `weight_scale` (uint8 E8M0, (N, K / 32)),
     optional `bias` (activation dtype): the state-dict keys.  A 16-bit `weight` in a state dict is quantised on load."""
+    CODES, SCALES, KIND, W_FLAG = "weight_packed", "weight_scale", "mxfp4", MXVL_W_MXFP4
+    quantize, dequantize_into = staticmethod(quantize_mxfp4), staticmethod(dequantize_mxfp4)
 
-    def __init__(self, in_features, out_features, bias=False, dtype=torch.float16, device=None, scratch=None):
-        super().__init__()
-        if in_features % BLOCK:
-            raise ValueError(f"MXFP4 needs in_features % {BLOCK} == 0, got {in_features}")
-        self.in_features, self.out_features, self.wdtype = in_features, out_features, dtype
-        self.register_buffer("weight_packed", torch.zeros(out_features, in_features // 2, dtype=torch.uint8, device=device))
-        self.register_buffer("weight_scale", torch.zeros(out_features, in_features // BLOCK, dtype=torch.uint8, device=device))
-        self.register_buffer("bias", torch.zeros(out_features, dtype=dtype, device=device) if bias else None)
-        self.scratch = scratch if scratch is not None else DequantScratch()
-
-    @classmethod
-    def from_linear(cls, lin: nn.Linear, scratch=None):
-        packed, scale = quantize_mxfp4(lin.weight)                       # (before anything is built: an fp16 weight out of range raises here)
-        m = cls(lin.in_features, lin.out_features, bias=lin.bias is not None, dtype=lin.weight.dtype, device=lin.weight.device, scratch=scratch)
-        m.weight_packed, m.weight_scale = packed, scale
-        if lin.bias is not None:
-            m.bias = lin.bias.detach().clone()
-        return m
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        w = state_dict.get(prefix + "weight")
-        if w is not None and w.is_floating_point():
-            state_dict = {k: v for k, v in state_dict.items() if k != prefix + "weight"}
-            state_dict[prefix + "weight_packed"], state_dict[prefix + "weight_scale"] = quantize_mxfp4(w)
-        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
-
-    def dequantize(self, dtype=None):
-        """A fresh (N, K) tensor of the represented weights Wdq, exact in `dtype` (default: the 16-bit type the module was built for)."""
-        return dequantize_mxfp4(self.weight_packed, self.weight_scale, self.wdtype if dtype is None else dtype)
-
-    def forward(self, x):
-        dev = x.device.type
-        dt = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else x.dtype
-        return _MxFp4LinearFn.apply(x, self.weight_packed, self.weight_scale, self.bias, self.scratch, dt)
-
-    def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, mxfp4"
+    @staticmethod
+    def buffers(N, K):
+        if K % BLOCK:
+            raise ValueError(f"MXFP4 needs in_features % {BLOCK} == 0, got {K}")
+        return ((N, K // 2), torch.uint8), ((N, K // BLOCK), torch.uint8)

@@ -31,8 +31,9 @@ import torch.nn as nn
 
 from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
-from .int8_linear import DequantScratch, Int8Linear
+from .int8_linear import Int8Linear
 from .mxfp4_linear import MxFp4Linear
+from .quant_linear import DequantScratch, QuantLinear
 
 
 class KVCache:
@@ -568,7 +569,7 @@ class _KernelStepper(_Stepper):
         mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and cfg.hidden_size <= 16384
         fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
             (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
-        if (model.is_int8() or model.is_mxfp4()) and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
+        if model.weight_format() is not None and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
             return False         # int8 / mxfp4 projections (MXVL_W_INT8, MXVL_W_MXFP4): K % 64 == 0 on the one kernel each has
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
@@ -599,8 +600,8 @@ class _KernelStepper(_Stepper):
         # int8 layer projections (ReportDecoder.quantize_int8_): the matrix-core kernel at every row count, explicit norm launches
         # ("split" mode) -- there is no int8 form of the fused RMSNorm; lm_head and the embedding stay 16-bit
         # mxfp4 layer projections (ReportDecoder.quantize_mxfp4_) take the same route with MXVL_W_MXFP4
-        self.int8, self.mxfp4 = model.is_int8(), model.is_mxfp4()
-        self.quantised = self.int8 or self.mxfp4
+        self.wfmt = model.weight_format()                # None, Int8Linear or MxFp4Linear
+        self.quantised = self.wfmt is not None
         # rows <= 8: RMSNorm fused into the MFMA projection that consumes the rows (csrc/decode_gemm.h NORM, K % 64 == 0): no
         # mxvl_decode_rmsnorm launches (65 of a token's 229), o_proj / down_proj add their residual in their own epilogue instead of
         # splitting K.  Measured in one call (profiles/r05_decode_norm_ab.txt): batch 1 x beam 3 332.7 -> 361.1 tok/s, Qwen-1.8B 1 x 5
@@ -706,6 +707,9 @@ class _KernelStepper(_Stepper):
         d.gate_weight, d.gate_bias, d.warm_up_gate = c["gate_w"].data_ptr(), c["gate_b"].data_ptr(), _abi.ptr(c["warm"])
         _abi.launch("mxvl_decode_cross_attn", d, device=self.x.device)
 
+    int8 = property(lambda self: self.wfmt is Int8Linear)
+    mxfp4 = property(lambda self: self.wfmt is MxFp4Linear)
+
     def _rmsnorm(self, x, norm, eps, K, fold_res=None, x_out=None, splits=1):
         """rows > 8: RMSNorm ahead of an MFMA projection (the GEMV kernel, rows <= 8, normalises in its own prologue).  With
         fold_res the row is first completed from the split projection's fp32 sums: x_out = bf16(acc) + fold_res; acc is cleared."""
@@ -721,7 +725,7 @@ class _KernelStepper(_Stepper):
         d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
         if scale is not None:                   # W / W2 are int8 codes + row-wise absmax (SCB), or packed E2M1 codes + E8M0 block scales
-            d.dtype |= _abi.MXVL_W_MXFP4 if self.mxfp4 else _abi.MXVL_W_INT8
+            d.dtype |= self.wfmt.W_FLAG
             d.w_scale, d.w2_scale = scale.data_ptr(), _abi.ptr(scale2)
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
         d.x, d.norm_weight, d.W = x.data_ptr(), _abi.ptr(norm), W.data_ptr()
@@ -798,13 +802,11 @@ class _KernelStepper(_Stepper):
                 self._cross_attn(i)
                 att = self.att2
             if batched:
-                sc = (lambda lin: lin.weight_scale) if self.mxfp4 else (lambda lin: lin.SCB) if self.int8 else (lambda lin: None)
-                wt = (lambda lin: lin.weight_packed) if self.mxfp4 else (lambda lin: lin.weight)
-                self._gemv(att, wt(at.o_proj), None, self.H * self.D, self.hidden, split=so, scale=sc(at.o_proj))
+                self._gemv(att, _codes(at.o_proj), None, self.H * self.D, self.hidden, split=so, scale=_scales(at.o_proj))
                 xin = self._rmsnorm(None, ln2.weight, ln2.variance_epsilon, self.hidden, fold_res=self.x, x_out=self.x2, splits=so)
-                self._gemv(xin, wt(layer.mlp.gate_proj), self.act, self.hidden, self.inter, W2=wt(layer.mlp.up_proj),
-                           scale=sc(layer.mlp.gate_proj), scale2=sc(layer.mlp.up_proj))
-                self._gemv(self.act, wt(layer.mlp.down_proj), None, self.inter, self.hidden, split=sd, scale=sc(layer.mlp.down_proj))
+                self._gemv(xin, _codes(layer.mlp.gate_proj), self.act, self.hidden, self.inter, W2=_codes(layer.mlp.up_proj),
+                           scale=_scales(layer.mlp.gate_proj), scale2=_scales(layer.mlp.up_proj))
+                self._gemv(self.act, _codes(layer.mlp.down_proj), None, self.inter, self.hidden, split=sd, scale=_scales(layer.mlp.down_proj))
             else:
                 self._gemv(att, at.o_proj.weight, self.x2, self.H * self.D, self.hidden, res=self.x)
                 self._gemv(self.x2, layer.mlp.gate_proj.weight, self.act, self.hidden, self.inter,
@@ -827,6 +829,15 @@ class _KernelStepper(_Stepper):
         self.cur.fill_(k + 1)               # the prologue kernel derives the position and the RoPE step from it
         out = self._replay("graph", self._body, self.tok, self.beam, self.cur)
         return self.logits if out is None else out
+
+
+def _codes(lin):
+    """the weight bytes a decode projection reads: an nn.Linear's `weight`, a QuantLinear's codes"""
+    return lin.codes if isinstance(lin, QuantLinear) else lin.weight
+
+
+def _scales(lin):
+    return lin.scales if isinstance(lin, QuantLinear) else None
 
 
 class _Stack(nn.Module):
@@ -878,21 +889,19 @@ class ReportDecoder(nn.Module):
             at = layer.self_attn
             W = getattr(at, "qkv_weight", None)
             qkv = (at.q_proj, at.k_proj, at.v_proj)
-            # where a projection keeps its weight bytes and their scales: nn.Linear / Int8Linear `weight` (+ `SCB`), MxFp4Linear its two buffers
-            wkey, skey = ("weight_packed", "weight_scale") if isinstance(at.q_proj, MxFp4Linear) else ("weight", "SCB")
-            w0 = getattr(at.q_proj, wkey)
+            w0 = _codes(at.q_proj)
             if W is not None and W.data_ptr() == w0.data_ptr() and W.dtype == w0.dtype:
                 continue        # still fused (a later .to(device/dtype) re-creates the parameters and un-fuses them)
             with torch.no_grad():
-                W = torch.cat([getattr(lin, wkey) for lin in qkv], dim=0).contiguous()
+                W = torch.cat([_codes(lin) for lin in qkv], dim=0).contiguous()
                 b = torch.cat([at.q_proj.bias, at.k_proj.bias, at.v_proj.bias], dim=0).contiguous()
-                nq, nk = w0.shape[0], getattr(at.k_proj, wkey).shape[0]
-                if isinstance(at.q_proj, (Int8Linear, MxFp4Linear)):
+                nq, nk = w0.shape[0], _codes(at.k_proj).shape[0]
+                if isinstance(at.q_proj, QuantLinear):
                     # int8 / mxfp4: the codes' rows and the per-row (per-block) scales concatenate exactly; the buffers become views of
                     # the fused ones (assigned, not .data: the unfused storage is released, no second copy of the bytes)
-                    S = torch.cat([getattr(lin, skey) for lin in qkv], dim=0).contiguous()
+                    S = torch.cat([lin.scales for lin in qkv], dim=0).contiguous()
                     for lin, lo, hi in ((at.q_proj, 0, nq), (at.k_proj, nq, nq + nk), (at.v_proj, nq + nk, W.shape[0])):
-                        setattr(lin, wkey, W[lo:hi]); setattr(lin, skey, S[lo:hi]); lin.bias = b[lo:hi]
+                        lin.set_quantized(W[lo:hi], S[lo:hi]); lin.bias = b[lo:hi]
                     at.qkv_scale = S
                 else:
                     at.q_proj.weight.data, at.k_proj.weight.data, at.v_proj.weight.data = W[:nq], W[nq:nq + nk], W[nq + nk:]
@@ -902,11 +911,16 @@ class ReportDecoder(nn.Module):
 
     _INT8_TARGETS = (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj")))
 
+    def weight_format(self):
+        """None (16-bit), Int8Linear or MxFp4Linear: the class of the layer projections"""
+        cls = type(self.model.layers[0].mlp.down_proj)
+        return cls if issubclass(cls, QuantLinear) else None
+
     def is_int8(self):
-        return isinstance(self.model.layers[0].mlp.down_proj, Int8Linear)
+        return self.weight_format() is Int8Linear
 
     def is_mxfp4(self):
-        return isinstance(self.model.layers[0].mlp.down_proj, MxFp4Linear)
+        return self.weight_format() is MxFp4Linear
 
     def quantize_mxfp4_(self):
         """`low_resource="mxfp4"`: the projections quantize_int8_ covers become MxFp4Linear (OCP MXFP4: E2M1 codes, one E8M0 scale
@@ -1181,7 +1195,7 @@ class ReportDecoder(nn.Module):
             conditioned = any(self.model.layers[i].vis_x is not None for i in self.hybrid_layers)
             last = self.model.layers[-1].mlp.down_proj
             ident = tuple((w.data_ptr(), w.dtype) for w in (self.lm_head.weight, self.model.embed_tokens.weight,
-                                                            last.weight_packed if self.is_mxfp4() else last.weight))
+                                                            _codes(last)))
             if self.__dict__.get("_stepper_weights") != ident:
                 self.__dict__["_steppers"] = {}
                 self.__dict__["_stepper_weights"] = ident

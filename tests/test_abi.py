@@ -357,7 +357,7 @@ def _plan(rows, K, N, swiglu=False, splits=0, norm=False):
 
 
 def test_decode_projection_dispatch_for_the_reference_decoder_shapes():
-    """mxvl_decode_gemm_plan = the dispatch of mxvl_decode_gemv as a pure function (csrc/decode_gemm.hip wide_plan), at the shapes the
+    """mxvl_decode_gemm_plan = the dispatch of mxvl_decode_gemv as a pure function (csrc/decode_gemm.hip decode_plan), at the shapes the
     reference decodes with: Llama-2-7B (hidden 4096, intermediate 11008, vocabulary 32000) and Qwen1.5-1.8B (2048 / 5504 / 151936) at
     val 6 x beam 3 = 18, config default 16 x 3 = 48 and IU test 16 x beam 5 = 80 rows.  (kind, waves, tiles per wave, ring stages, workgroups)"""
     # 80 rows: three waves per workgroup where that fills the 256 CUs

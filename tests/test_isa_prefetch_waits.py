@@ -5,6 +5,8 @@ this repo that had one (docs/DESIGN_HISTORY.md "Round 3" table; tools/isa_wait_a
 without failing any numerical test -- the results do not change, only the overlap does -- so the compiled ISA is checked here:
 between the requests of the next tile inside the main loop and the first `vmcnt` wait after them there must be the loop's
 arithmetic (MFMAs, or the scan's state loop)."""
+import ctypes
+import functools
 import os
 import re
 import shutil
@@ -17,10 +19,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 
 
-def _body(src, name_part):
+@functools.lru_cache(maxsize=None)
+def _kernels(src):
     import isa_wait_audit as audit
-    path = audit.compile_s(os.path.join(audit.CSRC, src))
-    found = [(n, b) for n, b in audit.kernels(path) if name_part in n]
+    return list(audit.kernels(audit.compile_s(os.path.join(audit.CSRC, src))))
+
+
+def _body(src, name_part):
+    found = [(n, b) for n, b in _kernels(src) if name_part in n]
     assert len(found) == 1, (name_part, [n for n, _ in found])
     return [x for x in found[0][1] if not x.endswith(":")]
 
@@ -136,6 +142,17 @@ def test_attention_dq64_kernel_has_no_scratch():
         assert not _scratch_ops(_body("attn.hip", name)), name
 
 
+def _ring_is_asked_for_each_chunk_once(fmt, factor, elt, mt, r, nw, pf):
+    """the assertions of the N-split ring kernels; factor = 64-column activation images per chunk (1 / 2 / 4 for 16-bit / int8 / mxfp4)"""
+    ins = _body("decode_gemm.hip", f"decode_gemm_{fmt}_kernelINS_{len(elt)}{elt}ELi{mt}ELi{r}ELi{nw}ELi{pf}E")
+    ops = 2 * r + (2 * factor * mt + nw - 1) // nw
+    assert sum(1 for x in ins if x.startswith("global_load_lds_dwordx4")) == pf * ops
+    waits = {int(re.search(r"vmcnt\((\d+)\)", x).group(1)) for x in ins if "vmcnt" in x}
+    assert {(pf - 2 - t) * ops for t in range(pf - 1)} <= waits, sorted(waits)
+    assert sum(1 for x in ins if x.startswith("v_mfma_f32_16x16x32")) == pf * 2 * factor * r * mt
+    assert not _scratch_ops(ins)
+
+
 @pytest.mark.parametrize("elt", ["EltBf16", "EltF16"])
 @pytest.mark.parametrize("mt,r,nw,pf", [(5, 1, 3, 8), (5, 2, 3, 6), (2, 2, 3, 8)])
 def test_wide_decode_projection_ring_is_asked_for_each_chunk_once(elt, mt, r, nw, pf):
@@ -144,10 +161,36 @@ def test_wide_decode_projection_ring_is_asked_for_each_chunk_once(elt, mt, r, nw
     loop body for one -- PF x OPS request instructions in the whole kernel, none in the unrolled tail (the first deep-ring version
     re-requested a chunk per tail iteration: a tenth of a launch's requests at 64 chunks); the tail's waits shrink with the ring,
     (PF - 2 - t) x OPS for t = 0 .. PF - 2; the loop body plus the PF - 1 tail copies hold PF x 2 R MT MFMAs; no scratch."""
-    ins = _body("decode_gemm.hip", f"decode_gemm_wide_kernelINS_{len(elt)}{elt}ELi{mt}ELi{r}ELi{nw}ELi{pf}E")
-    ops = 2 * r + (2 * mt + nw - 1) // nw
-    assert sum(1 for x in ins if x.startswith("global_load_lds_dwordx4")) == pf * ops
-    waits = {int(re.search(r"vmcnt\((\d+)\)", x).group(1)) for x in ins if "vmcnt" in x}
-    assert {(pf - 2 - t) * ops for t in range(pf - 1)} <= waits, sorted(waits)
-    assert sum(1 for x in ins if x.startswith("v_mfma_f32_16x16x32")) == pf * 2 * r * mt
-    assert not _scratch_ops(ins)
+    _ring_is_asked_for_each_chunk_once("wide", 1, elt, mt, r, nw, pf)
+
+
+def _quantised_llama7b_plans(flag):
+    """(MT, R, NW, PF) of the quantised kernel for Llama-2-7B's qkv, gate + up and down projections (the latter on the stepper's four
+    K planes) at 3, 18 and 80 rows, as mxvl_decode_gemm_plan reports them"""
+    from medical_image_analysis_amd import _abi
+    lib, out, plans = _abi.load(), (ctypes.c_int32 * 5)(), set()
+    for rows in (3, 18, 80):
+        for K, N, swiglu, splits in ((4096, 12288, 0, 1), (4096, 11008, 1, 1), (11008, 4096, 0, 4)):
+            d = _abi.GemvDesc()
+            d.rows, d.K, d.N, d.dtype, d.swiglu, d.k_splits = rows, K, N, _abi.MXVL_BF16 | flag, swiglu, splits
+            d.x, d.W, d.y, d.w_scale = 0x1000, 0x2000, 0x3000, 0x4000     # fake pointers: nothing is launched
+            if swiglu:
+                d.W2, d.w2_scale = 0x5000, 0x6000
+            if splits > 1:
+                d.split_acc, d.y = 0x7000, None
+            assert lib.mxvl_decode_gemm_plan(ctypes.byref(d), out) == 0
+            plans.add(((rows + 15) // 16, out[2], out[1], out[3]))
+    return sorted(plans)
+
+
+@pytest.mark.parametrize("elt", ["EltBf16", "EltF16"])
+@pytest.mark.parametrize("fmt,factor", [("w8", 2), ("w4", 4)])
+def test_quantised_decode_projection_ring_is_asked_for_each_chunk_once(elt, fmt, factor):
+    """decode_gemm_w8_kernel / decode_gemm_w4_kernel: the wide kernel's ring on chunks of 128 / 256 columns -- OPS = 2 R + ceil(4 MT / NW)
+    or 2 R + ceil(8 MT / NW) requests and 4 R MT or 8 R MT MFMAs per stage -- in the instantiations Llama-2-7B's layer projections take
+    at 3, 18 and 80 rows (tiles per wave and ring depth read from mxvl_decode_gemm_plan, not restated here)."""
+    from medical_image_analysis_amd import _abi
+    plans = _quantised_llama7b_plans(_abi.MXVL_W_INT8 if fmt == "w8" else _abi.MXVL_W_MXFP4)
+    assert {mt for mt, _, _, _ in plans} == {1, 2, 5}
+    for mt, r, nw, pf in plans:
+        _ring_is_asked_for_each_chunk_once(fmt, factor, elt, mt, r, nw, pf)
