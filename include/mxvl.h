@@ -706,7 +706,9 @@ int mxvl_cross_merge(const void *ys, void *y, int batch, int channels, int heigh
 /* Depthwise 3x3 convolution (padding 1) + optional SiLU of VMamba's SS2D block: `self.act(self.conv2d(x))`,
  * nn.Conv2d(d_inner, d_inner, 3, padding=1, groups=d_inner) (R2GenCSR/VMamba/classification/models/vmamba.py:746-755, 1121-1123).
  * x, y, dy, dx: (batch, channels, height, width) contiguous in the io dtype; weight (channels, 9) fp32, bias (channels) fp32 or
- * NULL; dweight / dbias fp32, ACCUMULATED into (caller zero-fills).  ksize must be 3, height*width <= 4096. */
+ * NULL; dweight / dbias fp32, ACCUMULATED into (caller zero-fills).  ksize must be 3, height*width <= 4096 and
+ * (height+2)*(width+2) <= 8172 (the backward's two padded fp32 tiles, 8 bytes per padded pixel + 160, fit 64 KB of LDS; only planes
+ * with a side of 1 or 2 are affected); anything else is MXVL_ERR_UNSUPPORTED from both entries. */
 int mxvl_dwconv2d_fwd(const void *x, const void *weight, const void *bias, void *y, int batch, int channels, int height,
                       int width, int ksize, int io_dtype, int silu, void *hip_stream);
 int mxvl_dwconv2d_bwd(const void *x, const void *weight, const void *bias, const void *dy, void *dx, void *dweight,

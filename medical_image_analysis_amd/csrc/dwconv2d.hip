@@ -15,6 +15,11 @@
 namespace mxvl {
 
 constexpr int kDwMaxPlane = 64 * 64;   // largest H*W handled in one LDS tile (SS2D stages are 56x56 .. 7x7 at 224x224)
+// ... and the largest (H+2) * (W+2): the backward holds two padded fp32 tiles of one plane plus 160 bytes of reduction scratch,
+// 2 * 4 * (H+2) * (W+2) + 160 bytes, and stays within the 64 KB of LDS a launch gets without raising
+// hipFuncAttributeMaxDynamicSharedMemorySize.  Only thin planes (H or W of 1 or 2) with H * W <= 4096 exceed it; forward and
+// backward refuse them alike, so a forward that was served never meets a backward that is not.
+constexpr int kDwMaxPadded = (64 * 1024 - 160) / 8;   // 8172
 
 // A workgroup owns ONE channel and `nb` batch elements of it (grid = channels x batch parts): the nine taps and the bias sit in
 // registers, dweight / dbias add up in registers over all its planes (ten atomics per WORKGROUP; the round-1 kernels spent a
@@ -205,7 +210,7 @@ static bool dw_vec4(int HW, std::initializer_list<const void*> ptrs) {
 
 static int dw_check(int B, int C, int H, int W, int K, int dtype) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return MXVL_ERR_SHAPE;
-  if (K != 3 || (long)H * W > kDwMaxPlane) return MXVL_ERR_UNSUPPORTED;
+  if (K != 3 || (long)H * W > kDwMaxPlane || ((long)H + 2) * ((long)W + 2) > kDwMaxPadded) return MXVL_ERR_UNSUPPORTED;
   if (dtype != MXVL_F32 && dtype != MXVL_BF16 && dtype != MXVL_F16) return MXVL_ERR_DTYPE;
   return MXVL_OK;
 }

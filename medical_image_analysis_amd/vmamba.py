@@ -102,10 +102,11 @@ class _DwConv2dAct(torch.autograd.Function):
 
 
 def dwconv3x3_act(x, conv: nn.Conv2d, act: nn.Module):
-    """act(conv(x)); the HIP kernel when conv is the SS2D depthwise 3x3 / padding 1 and the plane fits its LDS tile."""
-    C = x.shape[1]
+    """act(conv(x)); the HIP kernel when conv is the SS2D depthwise 3x3 / padding 1 and the plane fits its LDS tile: H * W <= 4096 and
+    (H + 2) * (W + 2) <= 8172, the backward's two padded fp32 tiles within 64 KB (dw_check of csrc/dwconv2d.hip)."""
+    C, H, W = x.shape[1:]
     fits = (x.is_cuda and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.stride == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == C and conv.in_channels == C and conv.out_channels == C and x.shape[2] * x.shape[3] <= 4096
+            and conv.groups == C and conv.in_channels == C and conv.out_channels == C and H * W <= 4096 and (H + 2) * (W + 2) <= 8172
             and x.dtype in (torch.float32, torch.bfloat16, torch.float16))
     if not fits:
         return act(conv(x))

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import assert_close, load_golden
+from fp64_bounds import FLOOR, GUARD, U, _Buf as _FlatBuf, _ratio, _report, _rho, _ulp
 from medical_image_analysis_amd import _abi
 
 DEV = "cuda:0"
@@ -22,25 +23,7 @@ DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 _DT = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
 gpu = pytest.mark.gpu
 
-# ---- 1. reference and bound ------------------------------------------------------------------------------------------------------------
-U = 2.0 ** -24                     # unit roundoff of fp32
-FLOOR = 2.0 ** -100                # the fast exponential flushes denormals: no tolerance below this
-_PREC = {torch.float32: (24, -126), torch.bfloat16: (8, -126), torch.float16: (11, -14)}
-
-
-def _ulp(v, dtype):
-    """one unit in the last place of `dtype` at |v| (float64 tensor)"""
-    p, emin = _PREC[dtype]
-    _, ex = torch.frexp(v.abs().clamp_min(2.0 ** emin))          # |v| in [2^(ex-1), 2^ex)
-    return torch.ldexp(torch.ones_like(v), ex - p)
-
-
-def _rho(v):
-    """relative error allowed to sigmoid(v) / exp(v) as the kernels form them: v * log2e rounded once (|v| u in the exponent),
-    v_exp_f32 and v_rcp_f32 at one ulp each, one add, one multiply"""
-    return (v.abs() + 8.0) * 2.0 ** -23
-
-
+# ---- 1. reference and bound (U, FLOOR, _ulp, _rho, _ratio: fp64_bounds.py) ------------------------------------------------------------
 def _windows(x64, W):
     """xw[..., t, k] = x[..., t - (W-1) + k], zero before the row starts"""
     return F.pad(x64, (W - 1, 0)).unfold(-1, W, 1)
@@ -139,17 +122,7 @@ def _state_ref(h, x, dt, A, Bm, Cm, D, z, dt_bias, softplus, io_dtype, skip_col=
     return hn, thn, y, (ty + _ulp(y, io_dtype)).clamp_min(FLOOR)
 
 
-def _ratio(got, ref, tol):
-    """max err / tol over ALL elements; a non-finite result counts as infinitely wrong"""
-    r = (got.detach().double().cpu() - ref).abs() / tol
-    return float(torch.nan_to_num(r, nan=float("inf")).max())
-
-
-# ---- 2. strided buffers with guard bands -----------------------------------------------------------------------------------------------
-GUARD = 64                                                        # elements before and after: keeps 256 / 128-byte alignment
-_NAN_BITS = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FC1, torch.float16: 0x7E01}
-
-
+# ---- 2. strided buffers with guard bands (GUARD, the NaN patterns and the buffer itself: fp64_bounds.py) --------------------------------
 def _padded_len(L):
     return L + 4 - L % 4                                          # > L and a multiple of 4
 
@@ -177,39 +150,11 @@ def _rows_aligned(lay, dtype):
     return (off * es) % al == 0 and st[0] % 4 == 0 and st[1] % 4 == 0
 
 
-class _Buf:
-    """a view of `shape` / `strides` at `off` into `n` elements holding the NaN pattern"""
-
-    def __init__(self, n, off, strides, shape, dtype, device, data=None):
-        self.pat, self.geom = _NAN_BITS[dtype], (tuple(shape), tuple(strides), off)
-        self.raw = torch.full((n,), self.pat, dtype=torch.int32 if dtype == torch.float32 else torch.int16, device=device)
-        self.view = self.raw.view(dtype).as_strided(*self.geom)
-        assert self.raw.data_ptr() % 256 == 0
-        self.before = None
-        if data is not None:
-            self.view.copy_(data)
-            self.before = self.raw.clone()
-
+class _Buf(_FlatBuf):
     @classmethod
     def rows(cls, kind, B, D, L, dtype, device, data=None):
         n, off, st = _layout(kind, B, D, L)
         return cls(n, off, st, (B, D, L), dtype, device, data)
-
-    @classmethod
-    def flat(cls, shape, dtype, device, data=None):
-        t = torch.empty(shape)
-        return cls(t.numel() + 2 * GUARD, GUARD, t.stride(), shape, dtype, device, data)
-
-    def guard_intact(self):
-        snap = self.raw.clone()
-        snap.as_strided(*self.geom).fill_(self.pat)
-        return bool((snap == self.pat).all())
-
-    def unchanged(self):
-        return torch.equal(self.raw, self.before)
-
-    def written(self):
-        return not bool(torch.isnan(self.view).any())
 
 
 def _fwd_desc(x, w, b, y, silu):
@@ -371,14 +316,6 @@ def _honest_fp32(x, w, b, silu, dy, io, dw0=None, db0=None):
     dw = wf.grad if dw0 is None else dw0 + wf.grad
     db = None if b is None else (bf.grad if db0 is None else db0 + bf.grad)
     return y.detach().to(io), xf.grad.to(io), dw, db
-
-
-def _report(what, **ratios):
-    """prints max err / tol per output, asserts each <= 1"""
-    ratios = {k: v for k, v in ratios.items() if v is not None}
-    print(f"{what}: max err / tol " + " ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
-    bad = {k: v for k, v in ratios.items() if not v <= 1.0}
-    assert not bad, f"{what}: outside the bound: {bad}"
 
 
 def _ratios(ref, y, dx=None, dw=None, db=None):
