@@ -33,6 +33,9 @@ def _autocast_dtype(x):
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, branch, weight, bias, eps, out_dtype):
+        # an output the loss never reached arrives in backward as None, not as a zeros tensor for the kernel to read: the blocks that take
+        # only n (add_layer_norm(x, None, ...)[1]) run the backward's dh == NULL arm
+        ctx.set_materialize_grads(False)
         C = x.shape[-1]
         x2 = x.reshape(-1, C)
         if not x2.is_contiguous():
@@ -73,7 +76,10 @@ class _AddLayerNorm(torch.autograd.Function):
         shape, has_br, br_dtype, br_orig, out_dtype, w_dtype, has_bias, b_dtype = ctx.meta
         lib = _abi.load()
         rows, C = h.shape
-        dn2 = dn.reshape(rows, C).to(out_dtype).contiguous()
+        if dn is None:                                             # the rare case, a loss on h alone: dn is not optional in the C-ABI
+            dn2 = torch.zeros((rows, C), dtype=out_dtype, device=h.device)
+        else:
+            dn2 = dn.reshape(rows, C).to(out_dtype).contiguous()
         dh2 = dh.reshape(rows, C).to(h.dtype).contiguous() if dh is not None else None
         dx = torch.empty_like(h)
         dbr = torch.empty((rows, C), dtype=br_dtype, device=h.device) if has_br and br_dtype != h.dtype else None

@@ -1,5 +1,5 @@
-"""What the kernel-against-float64 test files share (test_conv1d_gpu.py, test_dwconv2d_gpu.py): the rounding model of the fp32 kernels,
-the err / tol ratio, and the NaN-patterned buffers with guard bands that every tensor a kernel touches is a view into."""
+"""What the kernel-against-float64 test files share (test_conv1d_gpu.py, test_dwconv2d_gpu.py, test_norm_act_gpu.py): the rounding model
+of the fp32 kernels, the err / tol ratio, and the NaN-patterned buffers with guard bands that every tensor a kernel touches is a view into."""
 import torch
 
 U = 2.0 ** -24                     # unit roundoff of fp32
@@ -18,6 +18,22 @@ def _rho(v):
     """relative error allowed to sigmoid(v) / exp(v) as the kernels form them: v * log2e rounded once (|v| u in the exponent),
     v_exp_f32 and v_rcp_f32 at one ulp each, one add, one multiply"""
     return (v.abs() + 8.0) * 2.0 ** -23
+
+
+def _rnd(v, dtype):
+    """float64 `v` rounded to `dtype` (nearest even), back in float64"""
+    return v.to(dtype).double()
+
+
+def _near_tie(v, err, dtype):
+    """where a value within `err` of `v` can round to another `dtype` number than `v` does: the midpoint between two neighbours of
+    v's binade lies ulp / 2 - |v - rnd(v)| away"""
+    return (0.5 * _ulp(v, dtype) - (v - _rnd(v, dtype)).abs()) <= err
+
+
+def _fma32(a, b, c):
+    """fmaf on fp32 tensors: the product is exact in float64, one rounding to 53 bits and one to 24 follow"""
+    return (a.double() * b.double() + c.double()).float()
 
 
 def _ratio(got, ref, tol):
@@ -67,3 +83,22 @@ class _Buf:
 
     def written(self):
         return not bool(torch.isnan(self.view).any())
+
+    def untouched(self):
+        """nothing stored anywhere, the view included: a buffer the kernel was told to leave alone"""
+        return bool((self.raw == self.pat).all())
+
+
+def _ptr(buf):
+    return None if buf is None else buf.view.data_ptr()
+
+
+def _assert_buffers(what, inputs=(), outputs=(), untouched=()):
+    """after a launch: guards intact, inputs unchanged, outputs fully written, buffers the kernel must leave alone still all pattern"""
+    for name, buf in inputs:
+        assert buf is None or buf.unchanged(), f"{what}: input {name} was modified"
+    for name, buf in outputs:
+        assert buf is None or buf.guard_intact(), f"{what}: store outside {name}"
+        assert buf is None or buf.written(), f"{what}: {name} not fully written (or a read outside an input reached it)"
+    for name, buf in untouched:
+        assert buf is None or buf.untouched(), f"{what}: {name} was written"
