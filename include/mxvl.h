@@ -73,6 +73,8 @@
 extern "C" {
 #endif
 
+/* Still 13 with deterministic mode: its additions are additive (mxvl_set_deterministic, mxvl_conv1d_bwd_workspace_bytes) or trailing
+ * (mxvl_conv1d_bwd_desc.workspace / workspace_bytes, read in deterministic mode only); no field moved, no default behaviour changed. */
 #define MXVL_ABI_VERSION 13
 
 typedef enum mxvl_status {
@@ -162,10 +164,13 @@ typedef struct mxvl_scan_bwd_desc {
   void *du, *ddelta, *dz;   /* dz required iff fwd.z */
   void *dA, *dB, *dC;       /* fp32 accumulate */
   void *dD, *ddelta_bias;   /* fp32 accumulate; optional like their forward twins */
-  /* Reserved (ABI v3 layout kept): ignored.  dB / dC are sums over all channels of a group; every workgroup pre-sums its
+  /* Default mode: ignored.  dB / dC are sums over all channels of a group; every workgroup pre-sums its
    * 16 / 32 rows in registers + LDS and adds ONE fp32 global atomic per (n, t), as the reference's kernel does per row
    * (selective_scan_bwd_kernel.cuh:215-221).  The per-tile scratch + reduce kernel of round 2 measured slower at every
-   * shape (profiles/r02_bwd_workspace_ab.txt) and was removed: mxvl_scan_bwd_workspace_bytes() returns 0. */
+   * shape (profiles/r02_bwd_workspace_ab.txt) and was removed: mxvl_scan_bwd_workspace_bytes() returns 0.
+   * Deterministic mode (mxvl_set_deterministic): required, >= mxvl_scan_bwd_workspace_bytes(&fwd) bytes of device memory, 4-byte
+   * aligned, contents irrelevant (the entry zero-fills what it uses on the stream); NULL -> MXVL_ERR_NULL, not 4-byte aligned ->
+   * MXVL_ERR_STRIDE, too small -> MXVL_ERR_SHAPE, all before anything is enqueued. */
   void *workspace;
   int64_t workspace_bytes;
 } mxvl_scan_bwd_desc;
@@ -191,6 +196,11 @@ typedef struct mxvl_conv1d_bwd_desc {
   void *dx;      /* io dtype, fully written */
   void *dweight; /* (dim,width) fp32, accumulated into */
   void *dbias;   /* (dim) fp32, accumulated into, optional */
+  /* trailing, read in deterministic mode only (mxvl_set_deterministic): >= mxvl_conv1d_bwd_workspace_bytes(desc) bytes of device
+   * memory, 4-byte aligned, contents irrelevant; NULL -> MXVL_ERR_NULL, not 4-byte aligned -> MXVL_ERR_STRIDE, too small ->
+   * MXVL_ERR_SHAPE, before anything is enqueued */
+  void *workspace;
+  int64_t workspace_bytes;
 } mxvl_conv1d_bwd_desc;
 
 /*
@@ -373,6 +383,41 @@ typedef struct mxvl_rmsnorm_desc {
  * rows and >= 160 workgroups only, 6 = wide from one row on.  Returns the previous setting.  Same results in every mode up to the order
  * of the fp32 sums. */
 int mxvl_set_decode_gemm_wide(int on);
+/*
+ * Deterministic mode.  on != 0: every fp32-accumulated result libmxvl produces is a pure function of the call's inputs, shapes,
+ * strides, this build of the library and the device model -- bit-identical from run to run whatever order the workgroups arrive in.
+ * 0 (the default): the kernels, their dispatch and their speed are what they were before the switch existed, and the low bits of
+ * the sums named below depend on the arrival order.  Returns the previous value.  The value is process-wide and is read by the
+ * launchers when an entry is called: a captured graph keeps the mode it was captured in.
+ *   The guarantee does NOT cover a different batch size or launch geometry (another shape, alignment or mxvl_set_scan_variant), and
+ * the deterministic bits of an accumulated output are not the default mode's bits.  Outputs that never pass through a sum across
+ * workgroups (du, ddelta, dz, dx, ...) are bit-identical in both modes.  Vendor GEMMs (rocBLAS / hipBLASLt), RCCL and the
+ * framework's own operators are outside the guarantee.
+ *   Mechanism: no workgroup waits for another (no ticket locks, no spin loops).  Either ONE workgroup owns a destination and sums
+ * in a fixed order, or every contributor adds into a private slot of a caller workspace and a small fold kernel adds the slots in
+ * index order INTO the destination (the accumulate contracts stay).  Per entry, with the switch on:
+ *   mxvl_scan_bwd         private slots: dB / dC per channel tile of a group, dA / dD / ddelta_bias per batch element (folded: per
+ *                         part; dstate-1 kernel: per pass).  Needs mxvl_scan_bwd_desc.workspace of
+ *                         mxvl_scan_bwd_workspace_bytes(&fwd) bytes:
+ *                             dpg = dim / n_groups, tile_rows = 16, passes = 1
+ *                             if not MXVL_SCAN_FOLD_BATCH and dpg % 32 == 0 and batch * n_groups * (dpg / 32) >= 256: tile_rows = 32
+ *                                 (the 8-wave walk; mxvl_set_scan_variant's forced walks count: 1 << 8 -> 32, 2 << 8 -> 16)
+ *                             if dstate == 1 and z == NULL and not MXVL_SCAN_FOLD_BATCH:
+ *                                 rw = min(max(batch * dim / 8192, 8), 64); while rw > 1 and dpg % (4 rw) != 0: rw -= 1
+ *                                 if dpg % (4 rw) == 0: tile_rows = min(tile_rows, 4 rw), passes = ceil(seqlen / 256)
+ *                             tiles = ceil(dpg / tile_rows)
+ *                             bytes = 4 * (2 * tiles * batch * n_groups * dstate * seqlen + batch * passes * dim * (dstate + 2))
+ *                         (an upper bound over the kernels the dispatch may pick; the entry zero-fills and folds what it uses).
+ *                         -1 for a descriptor mxvl_scan_fwd would refuse.
+ *   mxvl_conv1d_bwd       private slots: one per workgroup of a channel.  Needs mxvl_conv1d_bwd_desc.workspace of
+ *                         mxvl_conv1d_bwd_workspace_bytes(desc) = 4 * slots * dim * (width + 1) bytes, slots = batch * ceil(seqlen /
+ *                         1024) for the tile kernels and ceil(batch / rows per workgroup) for the two short-row kernels.
+ *   mxvl_dwconv2d_bwd     single ownership: one workgroup per channel walks the whole batch.  No scratch.
+ *   mxvl_gemm_tn          MXVL_ERR_UNSUPPORTED (its K slices meet in fp32 atomics); callers take the split-K planes + sum form.
+ *   mxvl_mamba_inner_bwd  MXVL_ERR_UNSUPPORTED; compose mxvl_conv1d_bwd / mxvl_scan_bwd and the GEMMs instead.
+ * Every other entry has no order-dependent sum and is unchanged.  With the switch off both workspace queries return 0.
+ */
+int mxvl_set_deterministic(int on);
 /* Diagnostic (ABI v8): which kernel mxvl_decode_gemv would launch for a descriptor -- the dispatch as a pure function, nothing is launched
  * and no GPU is needed.  out[0] = 2 the per-row GEMV kernel (<= 8 rows, k_splits == 0), 1 = decode_gemm_wide_kernel, 0 = the K-split
  * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count), 4 = decode_gemm_w4_kernel (MXVL_W_MXFP4,
@@ -395,11 +440,15 @@ int mxvl_scan_n_chunks(int seqlen, int dstate);
 
 int mxvl_scan_fwd(const mxvl_scan_desc *desc, void *hip_stream);
 int mxvl_scan_bwd(const mxvl_scan_bwd_desc *desc, void *hip_stream);
-/* always 0 since round 3 (kept so ABI-v3 callers link): no scratch is useful, see mxvl_scan_bwd_desc.workspace */
+/* 0 in the default mode (no scratch is useful, see mxvl_scan_bwd_desc.workspace); in deterministic mode the slot workspace of
+ * mxvl_set_deterministic's formula */
 int64_t mxvl_scan_bwd_workspace_bytes(const mxvl_scan_desc *fwd);
 
 int mxvl_conv1d_fwd(const mxvl_conv1d_desc *desc, void *hip_stream);
 int mxvl_conv1d_bwd(const mxvl_conv1d_bwd_desc *desc, void *hip_stream);
+/* 0 in the default mode; in deterministic mode the slot workspace of this call (see mxvl_set_deterministic), -1 for a descriptor
+ * mxvl_conv1d_bwd would refuse.  The kernel choice depends on the alignment of x / dy / dx: ask with the pointers of the call. */
+int64_t mxvl_conv1d_bwd_workspace_bytes(const mxvl_conv1d_bwd_desc *desc);
 /* single-token decode step: conv_state (batch,dim,width) io dtype is rolled in place; x,y: (batch,dim) */
 int mxvl_conv1d_update(const void *x, void *conv_state, const void *weight, const void *bias, void *y,
                        int batch, int dim, int width, int io_dtype, int silu, void *hip_stream);
@@ -618,7 +667,8 @@ int mxvl_gemm_nt(const mxvl_gemm_nt_desc *desc, void *hip_stream);
  * `grad_weight = dy^T x` of every nn.Linear of the blocks (CXPMRG_Bench_MambaXray_VL/arm/Finetuning/mamba_simple.py:76,91 in_proj /
  * out_proj, models_mamba.py:59-83 w1 | w2 | w3; K = the step's tokens).  One MFMA kernel (csrc/gemm_tn.hip): operands through
  * LDS-DMA and the gfx950 transpose read, the token axis split over the XCDs, partial tiles added into c by fp32 atomics (so the
- * low bits of c depend on the arrival order, like the dB / dC of mxvl_scan_bwd).  accumulate == 0: c is zeroed on the stream first.
+ * low bits of c depend on the arrival order, like the dB / dC of mxvl_scan_bwd; in deterministic mode, mxvl_set_deterministic, the entry
+ * returns MXVL_ERR_UNSUPPORTED).  accumulate == 0: c is zeroed on the stream first.
  * K % 64 == 0, K >= 512, M % 8 == 0, N % 8 == 0, 16-byte aligned a / b rows, bf16 / fp16 operands, fp32 accumulation and output.
  * slices_per_xcd: 0 = chosen from the shape (1..4 token slices per XCD), q / -q = forced with / without the split of the last round
  * (measurement). */
@@ -853,7 +903,8 @@ int mxvl_clip_loss(const float *image_features, const float *text_features, cons
  * the scan checkpoints there and the backward reads them back, so the workspace of a forward call must reach the backward call
  * untouched.  The one allocation this entry ever causes is rocBLAS's own handle (once per process).
  * Backward: dxz (io dtype) fully written; every parameter gradient is fp32 and ACCUMULATED into (caller zero-fills: the contract of
- * mxvl_scan_bwd / mxvl_conv1d_bwd); needs its own scratch of mxvl_mamba_inner_bwd_workspace_bytes.
+ * mxvl_scan_bwd / mxvl_conv1d_bwd); needs its own scratch of mxvl_mamba_inner_bwd_workspace_bytes.  In deterministic mode
+ * (mxvl_set_deterministic) the backward returns MXVL_ERR_UNSUPPORTED.
  * The Python mirror's autograd node (selective_scan_interface._MambaInnerFn) keeps composing the same kernels with torch's GEMMs
  * (hipBLASLt, tuned per shape, split-K weight gradients); `mamba_inner_fn_native` is this entry behind the same signature.
  */

@@ -113,6 +113,7 @@ class Conv1dBwdDesc(ctypes.Structure):
         ("fwd", Conv1dDesc),
         ("dy_bs", c_int64), ("dy_ds", c_int64), ("dx_bs", c_int64), ("dx_ds", c_int64),
         ("dy", c_void_p), ("dx", c_void_p), ("dweight", c_void_p), ("dbias", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64),
     ]
 
 
@@ -311,6 +312,7 @@ SIGNATURES = {
     # causal conv1d
     "mxvl_conv1d_fwd": _DESC,
     "mxvl_conv1d_bwd": _DESC,
+    "mxvl_conv1d_bwd_workspace_bytes": (_I64, [_P]),
     "mxvl_conv1d_update": (_I, [_P] * 5 + [_I] * 5 + [_P]),
     # fused Mamba inner block
     "mxvl_mamba_inner_fwd": _DESC,
@@ -321,6 +323,7 @@ SIGNATURES = {
     "mxvl_decode_gemv": _DESC,
     "mxvl_decode_gemm_plan": (_I, [ctypes.POINTER(GemvDesc), ctypes.POINTER(c_int32)]),
     "mxvl_set_decode_gemm_wide": (_I, [_I]),
+    "mxvl_set_deterministic": (_I, [_I]),
     "mxvl_decode_attn": _DESC,
     "mxvl_decode_cross_attn": _DESC,
     "mxvl_decode_prologue": _DESC,
@@ -442,12 +445,59 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed: {STATUS.get(rc, rc)}{hip}")
 
 
+# Deterministic mode (include/mxvl.h mxvl_set_deterministic).  _det_mode: what set_deterministic() asked for (None = follow torch);
+# _det_lib: what the library was last told (it starts at 0).  launch() brings the two in step before it calls an entry.
+_det_mode = None
+_det_lib = 0
+
+
+def set_deterministic(mode) -> None:
+    """True / False: libmxvl's deterministic mode on / off; None (the default): follow torch.are_deterministic_algorithms_enabled()
+    at each call.  With the mode on every fp32-accumulated gradient of the hand-written kernels is bit-identical from run to run
+    (same inputs, shapes, strides, build and device model); vendor GEMMs, RCCL and torch's own ops are outside the guarantee.
+    Under the mode mxvl_gemm_tn and the composed mxvl_mamba_inner_bwd refuse (MXVL_ERR_UNSUPPORTED): splitk_wgrad takes the library's
+    plane-sum form by itself, mamba_inner_fn_native's backward raises.  When the mode comes from torch.use_deterministic_algorithms(True),
+    torch also fills every torch.empty (torch.utils.deterministic.fill_uninitialized_memory), the slot workspaces included."""
+    global _det_mode
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError("set_deterministic: mode must be True, False or None")
+    _det_mode = mode
+
+
+def is_deterministic() -> bool:
+    """The mode the next libmxvl call runs in."""
+    return torch.are_deterministic_algorithms_enabled() if _det_mode is None else _det_mode
+
+
+def sync_deterministic() -> bool:
+    """Tell the library the current mode if it changed since the last call (an int compare otherwise); returns the mode.  The
+    callers that size a workspace by the mode (scan / conv1d backward) call it before they ask the library for the size."""
+    global _det_lib
+    want = 1 if is_deterministic() else 0
+    if want != _det_lib:
+        (_lib or load()).mxvl_set_deterministic(want)
+        _det_lib = want
+    return bool(want)
+
+
+def det_workspace_bytes(name: str, desc) -> int:
+    """Bytes of slot workspace the backward entry behind query `name` (mxvl_scan_bwd_workspace_bytes(fwd descriptor) /
+    mxvl_conv1d_bwd_workspace_bytes(descriptor)) needs in the mode the next call runs in: 0 with deterministic mode off."""
+    if not sync_deterministic():
+        return 0
+    nbytes = int(getattr(_lib or load(), name)(ctypes.byref(desc)))
+    if nbytes < 0:
+        raise RuntimeError(f"{name}: invalid descriptor")
+    return nbytes
+
+
 def launch(name: str, first, *rest, device) -> None:
     """The one way the package enqueues a libmxvl kernel: entry `name` (one whose prototype ends in `void *hip_stream`) on
     `device`'s current stream, with `device` current -- libmxvl's hipFuncSetAttribute calls act on the current device -- and a
     non-zero status raised by check().  A descriptor is an entry's first parameter (include/mxvl.h) and goes by reference; the
     other arguments pass as they are.  A name libmxvl does not export raises before anything is called."""
     fn = getattr(_lib or load(), name)
+    sync_deterministic()
     with torch.cuda.device(device):
         rc = fn(ctypes.byref(first) if isinstance(first, ctypes.Structure) else first, *rest, stream_ptr(device))
     check(rc, name)

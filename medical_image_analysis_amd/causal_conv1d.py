@@ -60,6 +60,10 @@ def conv1d_bwd_raw(x, w32, b32, silu, dy, dx=None):
     f.x, f.weight, f.bias = x.data_ptr(), w32.data_ptr(), _abi.ptr(b32)
     d.dy_bs, d.dy_ds, d.dx_bs, d.dx_ds = dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1)
     d.dy, d.dx, d.dweight, d.dbias = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), _abi.ptr(db)
+    nbytes = _abi.det_workspace_bytes("mxvl_conv1d_bwd_workspace_bytes", d)
+    if nbytes:       # deterministic mode: private slots + a fold in slot order (include/mxvl.h mxvl_set_deterministic)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
     _abi.launch("mxvl_conv1d_bwd", d, device=x.device)
     return dx, dw, db
 

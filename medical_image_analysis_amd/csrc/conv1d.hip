@@ -25,7 +25,23 @@ struct ConvArgs {
   const float *w, *bias;
   void *y, *dx;
   float *dw, *dbias;
+  float* slots;    // deterministic mode (mxvl_set_deterministic): (workgroups per channel, dim, W + 1) fp32, else null
 };
+
+// One dweight tap (k < W) or the dbias sum (k == W) of channel d leaves its workgroup: an fp32 atomic on the destination, or, in
+// deterministic mode, a plain store into the private slot of this workgroup (its index among the workgroups of the channel:
+// blockIdx.x + gridDim.x * blockIdx.z), which conv1d_det_fold_kernel adds up in slot order.  Every workgroup of a grid gets here for
+// every k <= W, so the slots need no zero-fill.
+__device__ __forceinline__ void conv_emit(const ConvArgs& p, int d, int W, int k, float v) {
+  if (p.slots) {
+    const int64_t slot = (int64_t)blockIdx.x + (int64_t)gridDim.x * blockIdx.z;
+    p.slots[(slot * p.dim + d) * (W + 1) + k] = v;
+  } else if (k < W) {
+    unsafeAtomicAdd(p.dw + (int64_t)d * W + k, v);
+  } else if (p.dbias) {
+    unsafeAtomicAdd(p.dbias + d, v);
+  }
+}
 
 // runtime-indexed register arrays would go to scratch: select chain instead (generic-width path only)
 __device__ inline float pick(const float (&w)[kMaxW], int idx) {
@@ -193,8 +209,7 @@ __global__ __launch_bounds__(128) void conv1d_bwd_vec_kernel(const ConvArgs p) {
   if (threadIdx.x <= WT) {
     const int k = threadIdx.x;
     const float v = red[0][k] + red[1][k];
-    if (k < WT) unsafeAtomicAdd(p.dw + (int64_t)d * WT + k, v);
-    else if (p.dbias) unsafeAtomicAdd(p.dbias + d, v);
+    conv_emit(p, d, WT, k, v);
   }
 }
 
@@ -233,8 +248,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_vec_rows_kernel(const ConvArgs
   if (threadIdx.x <= WT) {
     const int k = threadIdx.x;
     const float v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-    if (k < WT) unsafeAtomicAdd(p.dw + (int64_t)d * WT + k, v);
-    else if (p.dbias) unsafeAtomicAdd(p.dbias + d, v);
+    conv_emit(p, d, WT, k, v);
   }
 }
 
@@ -336,8 +350,8 @@ __global__ __launch_bounds__(256) void conv1d_bwd_kernel(const ConvArgs p) {
   if (threadIdx.x <= kMaxW) {
     const int k = threadIdx.x;
     const float v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-    if (k < W) unsafeAtomicAdd(p.dw + (int64_t)d * W + k, v);
-    if (k == kMaxW && p.dbias) unsafeAtomicAdd(p.dbias + d, v);
+    if (k < W) conv_emit(p, d, W, k, v);
+    if (k == kMaxW) conv_emit(p, d, W, W, v);
   }
 }
 
@@ -412,8 +426,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_short_kernel(const ConvArgs p,
   if (threadIdx.x <= WT) {
     const int k = threadIdx.x;
     const float v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-    if (k < WT) unsafeAtomicAdd(p.dw + (int64_t)d * WT + k, v);
-    else if (p.dbias) unsafeAtomicAdd(p.dbias + d, v);
+    conv_emit(p, d, WT, k, v);
   }
 }
 
@@ -477,6 +490,52 @@ static int conv_check(const mxvl_conv1d_desc* d) {
   return MXVL_OK;
 }
 
+// dweight[d][k] / dbias[d] += slot 0 + slot 1 + ... in slot order: one thread per (d, k)
+__global__ __launch_bounds__(256) void conv1d_det_fold_kernel(const float* __restrict__ slots, int n_slots, int dim, int W, float* dw,
+                                                              float* dbias) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= dim * (W + 1)) return;
+  const int d = idx / (W + 1), k = idx - d * (W + 1);
+  float s = slots[idx];
+  for (int i = 1; i < n_slots; ++i) s += slots[(int64_t)i * dim * (W + 1) + idx];
+  if (k < W) dw[(int64_t)d * W + k] += s;
+  else if (dbias) dbias[d] += s;
+}
+
+// The backward's kernel choice and launch geometry, one place for the launcher and mxvl_conv1d_bwd_workspace_bytes.
+// tests/test_conv1d_gpu.py restates the choice and the forward's (_bwd_kernel_for / _fwd_kernel_for): change them together
+struct ConvBwdPlan {
+  int kind;        // 0 vec_rows, 1 short, 2 vec, 3 staged (d_conv 4), 4 staged (any width)
+  dim3 grid;
+  int vec, S, TPR, RW;
+  int64_t slots() const { return (int64_t)grid.x * grid.z; }      // workgroups per channel
+};
+static ConvBwdPlan conv_bwd_plan(const mxvl_conv1d_bwd_desc* d) {
+  const int L = d->fwd.seqlen, W = d->fwd.width, dim = d->fwd.dim, batch = d->fwd.batch, dt = d->fwd.io_dtype;
+  ConvBwdPlan p{};
+  p.vec = (rows_aligned(d->fwd.x, d->fwd.x_bs, d->fwd.x_ds, dt) && rows_aligned(d->dy, d->dy_bs, d->dy_ds, dt)) ? 1 : 0;
+  const bool dx_al = rows_aligned(d->dx, d->dx_bs, d->dx_ds, dt);
+  p.S = (W == 4 && L + 3 <= 512 && dim <= 65535) ? 1024 / (L + 3) : 0;   // batch rows per workgroup of the short-row kernel
+  // register-only vector kernel: aligned x / dy / dx rows of a multiple of 4 steps, d_conv 4, long rows
+  const bool bvec = p.vec && W == 4 && L % 4 == 0 && L > 512 && dx_al;
+  // short aligned rows: the register-only body, several batch rows per workgroup
+  const bool svec = p.vec && W == 4 && L % 4 == 0 && L <= 512 && dim <= 65535 && dx_al;
+  p.TPR = (L + 7) / 8;
+  p.RW = svec ? 256 / p.TPR : 0;                                         // L <= 512 -> TPR <= 64, RW >= 4
+  if (svec && p.RW >= 2) { p.kind = 0; p.grid = dim3((batch + p.RW - 1) / p.RW, dim); }
+  else if (p.S >= 2) { p.kind = 1; p.grid = dim3((batch + p.S - 1) / p.S, dim); }
+  else { p.kind = bvec ? 2 : W == 4 ? 3 : 4; p.grid = dim3((L + 1023) / 1024, dim, batch); }
+  return p;
+}
+static int conv_bwd_check(const mxvl_conv1d_bwd_desc* d) {
+  if (!d) return MXVL_ERR_NULL;
+  int rc = conv_check(&d->fwd);
+  if (rc != MXVL_OK) return rc;
+  if (!d->dy || !d->dx || !d->dweight) return MXVL_ERR_NULL;
+  if (d->fwd.bias && !d->dbias) return MXVL_ERR_NULL;
+  return MXVL_OK;
+}
+
 }  // namespace mxvl
 
 using namespace mxvl;
@@ -510,42 +569,47 @@ int mxvl_conv1d_fwd(const mxvl_conv1d_desc* d, void* hip_stream) {
   return launch_status();
 }
 
+int64_t mxvl_conv1d_bwd_workspace_bytes(const mxvl_conv1d_bwd_desc* d) {
+  if (!g_deterministic) return 0;
+  if (conv_bwd_check(d) != MXVL_OK) return -1;
+  return 4 * conv_bwd_plan(d).slots() * d->fwd.dim * (d->fwd.width + 1);
+}
+
 int mxvl_conv1d_bwd(const mxvl_conv1d_bwd_desc* d, void* hip_stream) {
-  if (!d) return MXVL_ERR_NULL;
-  int rc = conv_check(&d->fwd);
+  int rc = conv_bwd_check(d);
   if (rc != MXVL_OK) return rc;
-  if (!d->dy || !d->dx || !d->dweight) return MXVL_ERR_NULL;
-  if (d->fwd.bias && !d->dbias) return MXVL_ERR_NULL;
   ConvArgs a{};
   a.batch = d->fwd.batch; a.dim = d->fwd.dim; a.L = d->fwd.seqlen; a.W = d->fwd.width; a.silu = d->fwd.silu;
   a.x_bs = d->fwd.x_bs; a.x_ds = d->fwd.x_ds; a.dy_bs = d->dy_bs; a.dy_ds = d->dy_ds; a.dx_bs = d->dx_bs; a.dx_ds = d->dx_ds;
   a.x = d->fwd.x; a.w = (const float*)d->fwd.weight; a.bias = (const float*)d->fwd.bias;
   a.dy = d->dy; a.dx = d->dx; a.dw = (float*)d->dweight; a.dbias = (float*)d->dbias;
-  a.vec = (rows_aligned(d->fwd.x, d->fwd.x_bs, d->fwd.x_ds, d->fwd.io_dtype) &&
-           rows_aligned(d->dy, d->dy_bs, d->dy_ds, d->fwd.io_dtype)) ? 1 : 0;
-  dim3 grid((a.L + 1023) / 1024, a.dim, a.batch);
+  const ConvBwdPlan pl = conv_bwd_plan(d);
+  a.vec = pl.vec;
+  if (g_deterministic) {     // private slots in the caller's workspace + a fold in slot order (checked before anything is enqueued)
+    if (!d->workspace) return MXVL_ERR_NULL;
+    if ((uintptr_t)d->workspace % 4 != 0) return MXVL_ERR_STRIDE;
+    if (d->workspace_bytes < 4 * pl.slots() * a.dim * (a.W + 1)) return MXVL_ERR_SHAPE;
+    a.slots = (float*)d->workspace;
+  }
   hipStream_t s = (hipStream_t)hip_stream;
-  const int S = (a.W == 4 && a.L + 3 <= 512 && a.dim <= 65535) ? 1024 / (a.L + 3) : 0;   // batch rows per workgroup of the short-row kernel
-  const dim3 sgrid(S ? (a.batch + S - 1) / S : 1, a.dim);
-  // register-only vector kernel: aligned x / dy / dx rows of a multiple of 4 steps, d_conv 4, long rows
-  const bool bvec = a.vec && a.W == 4 && a.L % 4 == 0 && a.L > 512 && rows_aligned(d->dx, d->dx_bs, d->dx_ds, d->fwd.io_dtype);
-  // short aligned rows: the register-only body, several batch rows per workgroup
-  const bool svec = a.vec && a.W == 4 && a.L % 4 == 0 && a.L <= 512 && a.dim <= 65535 && rows_aligned(d->dx, d->dx_bs, d->dx_ds, d->fwd.io_dtype);
-  const int TPR = (a.L + 7) / 8, RW = svec ? 256 / TPR : 0;          // L <= 512 -> TPR <= 64, RW >= 4
-  const dim3 vgrid(RW > 0 ? (a.batch + RW - 1) / RW : 1, a.dim);
-  // tests/test_conv1d_gpu.py restates this choice and the forward's (_bwd_kernel_for / _fwd_kernel_for): change them together
 #define MXVL_CONV_BWD(T) \
   do { \
-    if (svec && RW >= 2) hipLaunchKernelGGL((conv1d_bwd_vec_rows_kernel<T, 4>), vgrid, dim3(256), 0, s, a, TPR, RW); \
-    else if (S >= 2) hipLaunchKernelGGL((conv1d_bwd_short_kernel<T, 4>), sgrid, dim3(256), 0, s, a, S); \
-    else if (bvec) hipLaunchKernelGGL((conv1d_bwd_vec_kernel<T, 4>), grid, dim3(128), 0, s, a); \
-    else if (a.W == 4) hipLaunchKernelGGL((conv1d_bwd_kernel<T, 4>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((conv1d_bwd_kernel<T, 0>), grid, dim3(256), 0, s, a); \
+    if (pl.kind == 0) hipLaunchKernelGGL((conv1d_bwd_vec_rows_kernel<T, 4>), pl.grid, dim3(256), 0, s, a, pl.TPR, pl.RW); \
+    else if (pl.kind == 1) hipLaunchKernelGGL((conv1d_bwd_short_kernel<T, 4>), pl.grid, dim3(256), 0, s, a, pl.S); \
+    else if (pl.kind == 2) hipLaunchKernelGGL((conv1d_bwd_vec_kernel<T, 4>), pl.grid, dim3(128), 0, s, a); \
+    else if (pl.kind == 3) hipLaunchKernelGGL((conv1d_bwd_kernel<T, 4>), pl.grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((conv1d_bwd_kernel<T, 0>), pl.grid, dim3(256), 0, s, a); \
   } while (0)
   switch (d->fwd.io_dtype) {
     case MXVL_F32: MXVL_CONV_BWD(float); break;
     case MXVL_BF16: MXVL_CONV_BWD(bf16_t); break;
     default: MXVL_CONV_BWD(f16_t); break;
+  }
+  if (a.slots) {
+    rc = launch_status();
+    if (rc != MXVL_OK) return rc;
+    hipLaunchKernelGGL(conv1d_det_fold_kernel, dim3((a.dim * (a.W + 1) + 255) / 256), dim3(256), 0, s, a.slots, (int)pl.slots(), a.dim, a.W,
+                       a.dw, a.dbias);
   }
   return launch_status();
 }

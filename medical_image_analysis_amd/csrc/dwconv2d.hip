@@ -260,6 +260,9 @@ int mxvl_dwconv2d_bwd(const void* x, const void* weight, const void* bias, const
   a.dw = (float*)dweight; a.dbias = (float*)dbias;
   const bool v4 = dw_vec4(height * width, {x, dy, dx});
   dw_geometry(a, 2, v4);
+  // deterministic mode (mxvl_set_deterministic): ONE workgroup owns a channel and walks the whole batch in order -- its dweight /
+  // dbias atomics are then the only adds their destinations receive from this call
+  if (g_deterministic) a.nb = batch;
   const dim3 grid(channels, (batch + a.nb - 1) / a.nb);
   const size_t lds = sizeof(float) * 2 * (size_t)a.P * (height + 2) * (width + 2);
   hipStream_t s = (hipStream_t)hip_stream;

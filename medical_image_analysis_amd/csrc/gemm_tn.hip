@@ -328,6 +328,7 @@ using namespace mxvl;
 /* see include/mxvl.h: mxvl_gemm_tn */
 extern "C" int mxvl_gemm_tn(const mxvl_gemm_tn_desc* d, void* hip_stream) {
   if (!d || !d->a || !d->b || !d->c) return MXVL_ERR_NULL;
+  if (g_deterministic) return MXVL_ERR_UNSUPPORTED;    /* the K slices of a tile meet in fp32 atomics: refused in deterministic mode */
   if (d->io_dtype != MXVL_BF16 && d->io_dtype != MXVL_F16) return MXVL_ERR_DTYPE;
   if (d->M <= 0 || d->K <= 0 || d->N <= 0) return MXVL_ERR_SHAPE;
   if (d->K % 64 != 0 || d->K / 64 < 8 || d->M % 8 != 0 || d->N % 8 != 0) return MXVL_ERR_UNSUPPORTED;

@@ -246,6 +246,9 @@ int mxvl_mamba_inner_fwd(const mxvl_mamba_inner_desc* d, void* hip_stream) {
 
 int mxvl_mamba_inner_bwd(const mxvl_mamba_inner_bwd_desc* b, void* hip_stream) {
   if (!b) return MXVL_ERR_NULL;
+  // deterministic mode (mxvl_set_deterministic): the composed backward sums out_proj_bias' gradient with atomics and drives
+  // mxvl_scan_bwd / mxvl_conv1d_bwd without their slot workspaces: refused, the caller composes the entries itself
+  if (g_deterministic) return MXVL_ERR_UNSUPPORTED;
   const mxvl_mamba_inner_desc* d = &b->fwd;
   int rc = mi_check(d);
   if (rc != MXVL_OK) return rc;

@@ -37,6 +37,8 @@ inline int hip_status(hipError_t e) {
   return MXVL_ERR_LAUNCH;
 }
 inline int launch_status() { return hip_status(hipGetLastError()); }
+// mxvl_set_deterministic (include/mxvl.h): process-wide, read by the launchers at launch time.  One definition (scan_fwd.hip).
+extern int g_deterministic;
 
 constexpr int kWave = 64;
 typedef float v2f __attribute__((ext_vector_type(2)));   // an aligned VGPR pair: operands of v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32

@@ -35,6 +35,12 @@ struct ScanBwdArgs {
   int64_t du_bs, du_ds, dd_bs, dd_ds, dz_bs, dz_ds;
   int64_t B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, A_ds, A_ns;
   int64_t dB_bs, dB_gs, dB_ns, dC_bs, dC_gs, dC_ns;
+  // Deterministic mode (mxvl_set_deterministic): every contributor adds into a slot of the caller's workspace only it touches --
+  // dB / dC: one slot per channel tile, laid out (batch, group, tile, n, t) so that the tile's index in the grid takes the place
+  // of the group index (det != 0; dB_gs = the slot size); dA / dD / ddelta_bias: one slot per batch element (part, pass), red_ss
+  // (x dstate for dA) elements apart -- and scan_det_fold_kernel adds the slots in index order.  Both 0 otherwise.
+  int64_t red_ss;
+  int det;
   const void *u, *delta, *B, *C, *z, *dout;
   const float *A, *D, *bias, *ckpt;
   void *du, *ddelta, *dz;
@@ -233,8 +239,9 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void scan_bwd_kernel(const ScanBwdA
   io_t* __restrict__ qdz = p.dz ? (io_t*)p.dz + (int64_t)b * p.dz_bs + (int64_t)dc * p.dz_ds + j * T : nullptr;
   const io_t* __restrict__ Bp = (const io_t*)p.B + (int64_t)b * p.B_bs + (int64_t)g * p.B_gs;
   const io_t* __restrict__ Cp = (const io_t*)p.C + (int64_t)b * p.C_bs + (int64_t)g * p.C_gs;
-  float* __restrict__ dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)g * p.dB_gs;
-  float* __restrict__ dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)g * p.dC_gs;
+  const int gu = p.det ? (int)blockIdx.x : g;         // deterministic mode: the workgroup's own (group, tile) slot
+  float* __restrict__ dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)gu * p.dB_gs;
+  float* __restrict__ dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)gu * p.dC_gs;
   const bool has_z = pz != nullptr;
   auto seg_of = [&](int tv) { return (int)__umulhi((unsigned)tv, p.fold_magic); };
   auto fold_off = [&](int tv, int64_t bs) {        // element offset of virtual step tv: (segment tv / SL) * bs + tv % SL
@@ -989,8 +996,9 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void scan_bwd_kernel(const ScanBwdA
   dD_acc = row_sum_to_lane15(dD_acc);
   dbias_acc = row_sum_to_lane15(dbias_acc);
   if (j == LPR - 1 && row_ok) {
-    if (p.dD) unsafeAtomicAdd(p.dD + d, dD_acc);
-    if (p.dbias) unsafeAtomicAdd(p.dbias + d, dbias_acc);
+    const int64_t red_off = (int64_t)blockIdx.y * p.red_ss;                              // 0 but in deterministic mode
+    if (p.dD) unsafeAtomicAdd(p.dD + red_off + d, dD_acc);
+    if (p.dbias) unsafeAtomicAdd(p.dbias + red_off + d, dbias_acc);
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -1000,11 +1008,12 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void scan_bwd_kernel(const ScanBwdA
   int tid_e = threadIdx.x;
   asm volatile("" : "+v"(tid_e));
   const int lane_e = tid_e & 63, wave_e = tid_e >> 6;
+  float* const dAp = p.dA + (int64_t)blockIdx.y * p.red_ss * N;
   for (int i = lane_e; i < RPW * N; i += 64) {
     const int rr = i / N, n = i - rr * N;
     const int dd = d0 + wave_e * RPW + rr;
     // d a / d A = delta * a and A2 = A*log2e only rescales the exponent argument: sdA already holds dA
-    if (dd < d_end) unsafeAtomicAdd(p.dA + (int64_t)dd * N + n, sdA[(wave_e * RPW + rr) * NP + n]);
+    if (dd < d_end) unsafeAtomicAdd(dAp + (int64_t)dd * N + n, sdA[(wave_e * RPW + rr) * NP + n]);
   }
 }
 
@@ -1016,11 +1025,116 @@ extern "C" int mxvl_scan_bwd_variant(void);   // scan_fwd.hip: bits 8..15 of mxv
 #include "scan_n1_short.h"
 namespace mxvl {
 
+// ---- deterministic mode (mxvl_set_deterministic, include/mxvl.h) ---------------------------------------------------------------------
+// The kernels stay as they are: the launcher points their accumulated outputs at zero-filled private slots of the caller's
+// workspace (every slot element then receives exactly ONE add, from the one workgroup that owns the slot: 0 + x is exact), and
+// scan_det_fold_kernel adds the slots in index order INTO the destinations.  No workgroup waits for another.
+struct ScanDet {
+  float* ws;
+  int max_tiles, max_red;     // slots the workspace holds (scan_det_bound)
+  int tiles, red;             // slots the launched kernel uses (det_redirect)
+};
+
+// rows (channels) per wave of scan_n1_bwd_kernel: ~2048 workgroups where the problem allows, at least 8 rows per wave to amortise the
+// dB / dC flush of a pass; 0: 4 rw does not divide dim / n_groups
+static int n1_bwd_rw(int batch, int dim, int G) {
+  constexpr int NW = 4;
+  const int dpg = dim / G;
+  int64_t rw = (int64_t)batch * dim / ((int64_t)NW * 2048);
+  if (rw < 8) rw = 8;
+  if (rw > 64) rw = 64;
+  while (rw > 1 && dpg % (NW * rw) != 0) --rw;
+  return dpg % (NW * rw) != 0 ? 0 : (int)rw;
+}
+
+static bool bwd_wide(int batch, int dim, int G, int L);
+
+// upper bounds of the slot counts over every kernel the dispatch may pick for this problem (the formula of include/mxvl.h)
+static void scan_det_bound(int batch, int dim, int L, int G, int N, bool has_z, bool fold, int& tiles, int& red) {
+  int tile_rows = 16, passes = 1;
+  if (!fold) {                                   // the 8-wave walk of the general kernels owns 32 rows (a folded call: bounded by 16)
+    const int v = mxvl_scan_bwd_variant();
+    if (v == 1 || (v != 2 && bwd_wide(batch, dim, G, L))) tile_rows = 32;
+  }
+  const int rw = (N == 1 && !has_z && !fold) ? n1_bwd_rw(batch, dim, G) : 0;
+  if (rw > 0) {
+    if (4 * rw < tile_rows) tile_rows = 4 * rw;
+    passes = (L + 255) / 256;
+  }
+  tiles = (dim / G + tile_rows - 1) / tile_rows;
+  red = batch * passes;
+}
+static int64_t scan_det_floats(int batch, int dim, int L, int G, int N, int tiles, int red) {
+  return 2 * (int64_t)tiles * batch * G * N * L + (int64_t)red * dim * (N + 2);
+}
+
+// a launcher's copy of the arguments, redirected: dB | dC | dA | dD | ddelta_bias slots, dense, zero-filled on the stream
+static int det_redirect(ScanBwdArgs& a, ScanDet* det, int tiles, int red, hipStream_t stream) {
+  if (tiles > det->max_tiles || red > det->max_red) return MXVL_ERR_SHAPE;     // (scan_det_bound covers every dispatch)
+  const int64_t bc = (int64_t)a.batch * a.G * a.N * a.L, dn = (int64_t)a.dim * a.N;
+  a.dB = det->ws;                            // (batch, G, tiles, N, L)
+  a.dC = a.dB + tiles * bc;
+  a.dA = a.dC + tiles * bc;
+  float* const sD = a.dA + red * dn;
+  float* const sb = sD + (int64_t)red * a.dim;
+  a.dD = a.dD ? sD : nullptr;
+  a.dbias = a.dbias ? sb : nullptr;
+  a.dB_ns = a.dC_ns = a.L;
+  a.dB_gs = a.dC_gs = (int64_t)a.N * a.L;
+  a.dB_bs = a.dC_bs = (int64_t)a.G * tiles * a.N * a.L;
+  if (a.fold_magic && a.dB_bs >= (1ll << 32)) return MXVL_ERR_UNSUPPORTED;   // seg_off: the folded walk's 32-bit batch strides
+  a.det = 1;
+  a.red_ss = a.dim;
+  det->tiles = tiles;
+  det->red = red;
+  return hip_status(hipMemsetAsync(det->ws, 0, sizeof(float) * (size_t)scan_det_floats(a.batch, a.dim, a.L, a.G, a.N, tiles, red), stream));
+}
+
+// dst[(b, g, n, t)] += slot 0 + slot 1 + ..., one thread per element of the (batch, n1, n2, n3) destination (strides (s0, s1, s2, 1)).
+// Slot k of element (r = (b, g), i = (n, t)) sits at r * outer + k * slot_stride + i: dB / dC (batch, G, tiles, N, L) have
+// outer = tiles N L and slot_stride = N L; the (slots, count) arrays of dA / dD / ddelta_bias (n1 = n2 = 1) outer = 0, slot_stride = count
+__global__ __launch_bounds__(256) void scan_det_fold_kernel(const float* __restrict__ slots, int n_slots, int64_t slot_stride, int64_t outer,
+                                                            float* dst, int64_t count, int n1, int n2, int n3, int64_t s0, int64_t s1,
+                                                            int64_t s2) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= count) return;
+  const int64_t inner = (int64_t)n2 * n3, r = idx / inner, i = idx - r * inner;
+  const float* src = slots + r * outer + i;
+  float s = src[0];
+  for (int k = 1; k < n_slots; ++k) s += src[k * slot_stride];
+  const int n = (int)(i / n3), t = (int)(i - (int64_t)n * n3);
+  const int64_t b = r / n1;
+  const int g = (int)(r - b * n1);
+  dst[b * s0 + g * s1 + n * s2 + t] += s;
+}
+static void det_fold1(const float* slots, int n_slots, int64_t slot_stride, int64_t outer, float* dst, int64_t count, int n1, int n2, int n3,
+                      int64_t s0, int64_t s1, int64_t s2, hipStream_t stream) {
+  hipLaunchKernelGGL(scan_det_fold_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, slots, n_slots, slot_stride, outer,
+                     dst, count, n1, n2, n3, s0, s1, s2);
+}
+// `a`: the caller's arguments (the real destinations and their strides)
+static int det_fold(const ScanBwdArgs& a, const ScanDet& det, hipStream_t stream) {
+  const int64_t bc = (int64_t)a.batch * a.G * a.N * a.L, dn = (int64_t)a.dim * a.N;
+  const float* sB = det.ws;
+  const float* sC = sB + det.tiles * bc;
+  const float* sA = sC + det.tiles * bc;
+  const float* sD = sA + det.red * dn;
+  const float* sb = sD + (int64_t)det.red * a.dim;
+  const int64_t nl = (int64_t)a.N * a.L;
+  det_fold1(sB, det.tiles, nl, det.tiles * nl, a.dB, bc, a.G, a.N, a.L, a.dB_bs, a.dB_gs, a.dB_ns, stream);
+  det_fold1(sC, det.tiles, nl, det.tiles * nl, a.dC, bc, a.G, a.N, a.L, a.dC_bs, a.dC_gs, a.dC_ns, stream);
+  det_fold1(sA, det.red, dn, 0, a.dA, dn, 1, 1, (int)dn, 0, 0, 0, stream);
+  if (a.dD) det_fold1(sD, det.red, a.dim, 0, a.dD, a.dim, 1, 1, a.dim, 0, 0, 0, stream);
+  if (a.dbias) det_fold1(sb, det.red, a.dim, 0, a.dbias, a.dim, 1, 1, a.dim, 0, 0, 0, stream);
+  return launch_status();
+}
+
 // dstate 1 without z (VMamba's SS2D): the pass-major kernel of scan_n1_bwd.h.  u / delta / B / C rows need T-element alignment (T = 8
 // for 16-bit rows with L % 8 == 0, else 4), a workgroup's 4 rw channels one B / C group; dout / du / ddelta fall back to element
 // accesses inside the kernel when their rows are not aligned.  Reads the forward's 128-step checkpoints (any forward kernel's).
 template <typename io_t>
-static int try_n1_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
+static int try_n1_bwd(const ScanBwdArgs& a_in, hipStream_t stream, bool& taken, ScanDet* det) {
+  ScanBwdArgs a = a_in;
   taken = false;
   if (a.N != 1 || a.z || a.fold_magic || mxvl_scan_bwd_variant() == 3) return MXVL_OK;     // variant 3: A/B hook, the general kernel
   const int64_t rows = (int64_t)a.batch * a.dim;
@@ -1039,12 +1153,8 @@ static int try_n1_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
   if (T == 0) return MXVL_OK;
   if (a.L > 64 * T && !a.ckpt) return MXVL_OK;             // the state entering a later pass comes from the forward's checkpoints
   constexpr int NW = 4;
-  // ~2048 workgroups where the problem allows, at least 8 rows per wave to amortise the dB / dC flush of a pass
-  int64_t rw = rows / ((int64_t)NW * 2048);
-  if (rw < 8) rw = 8;
-  if (rw > 64) rw = 64;
-  while (rw > 1 && dpg % (NW * rw) != 0) --rw;
-  if (dpg % (NW * rw) != 0) return MXVL_OK;
+  const int rw = n1_bwd_rw(a.batch, a.dim, a.G);
+  if (rw == 0) return MXVL_OK;
   ScanN1BwdGeom gm;
   gm.rw = (int)rw;
   const int gesz = a.out_f32 ? 4 : esz;
@@ -1056,6 +1166,10 @@ static int try_n1_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
   gm.dd_vec = vec(a.ddelta, a.dd_bs, a.dd_ds, esz, 4);
   const dim3 grid((unsigned)(rows / (NW * rw))), block(NW * 64);
   const size_t lds = sizeof(float) * ((size_t)NW * 2 * T * 64 + (size_t)NW * rw);
+  if (det) {
+    const int rc = det_redirect(a, det, dpg / (NW * rw), a.batch * ((a.L + 64 * T - 1) / (64 * T)), stream);
+    if (rc != MXVL_OK) return rc;
+  }
   if constexpr (esz == 2) {
     if (a.out_f32) {
       if (T == 8) hipLaunchKernelGGL((scan_n1_bwd_kernel<io_t, 8, NW, true>), grid, block, lds, stream, a, gm);
@@ -1074,7 +1188,8 @@ static int try_n1_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
 // rows of at most 128 steps that scan_n1_bwd.h cannot take (L % 4 != 0 or unaligned rows): a lane per row (scan_n1_short.h).  Dense
 // (batch, dim, L) u / delta / dout / du / ddelta, 64 | dim / n_groups.
 template <typename io_t>
-static int try_n1_short_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& taken) {
+static int try_n1_short_bwd(const ScanBwdArgs& a_in, hipStream_t stream, bool& taken, ScanDet* det) {
+  ScanBwdArgs a = a_in;
   taken = false;
   if (a.N != 1 || a.z || a.fold_magic || mxvl_scan_bwd_variant() == 3) return MXVL_OK;
   const int dpg = a.dim / a.G;
@@ -1092,6 +1207,10 @@ static int try_n1_short_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& take
   const bool two = 2 * per_wave <= 64 * 1024;
   const dim3 grid((unsigned)(two ? (waves + 1) / 2 : waves)), block(two ? 128 : 64);
   const size_t lds = per_wave * (two ? 2 : 1);
+  if (det) {
+    const int rc = det_redirect(a, det, dpg / 64, a.batch, stream);
+    if (rc != MXVL_OK) return rc;
+  }
   if (a.out_f32 && esz == 2) {
     if (two) hipLaunchKernelGGL((scan_n1_short_bwd_kernel<io_t, 2, true>), grid, block, lds, stream, a);
     else hipLaunchKernelGGL((scan_n1_short_bwd_kernel<io_t, 1, true>), grid, block, lds, stream, a);
@@ -1104,7 +1223,8 @@ static int try_n1_short_bwd(const ScanBwdArgs& a, hipStream_t stream, bool& take
 }
 
 template <typename io_t, int NWAVES, bool VEC, int NS, bool FOLD = false, bool DMAR = false>
-static int launch_bwd1(const ScanBwdArgs& a, hipStream_t stream) {
+static int launch_bwd1(const ScanBwdArgs& a_in, hipStream_t stream, ScanDet* det) {
+  ScanBwdArgs a = a_in;
   constexpr int DT = NWAVES * 4, CH = 128, NT = NWAVES * 64;
   const size_t lds = sizeof(float) * ((size_t)2 * a.N * CH + (size_t)DT * 2 * 2 * CH + (size_t)3 * (DT + 1) * (a.N + 1) + (size_t)DT * (a.N + 1) +
                                       (size_t)NT + a.N) + 16 + (size_t)4 * NT * 8 * sizeof(io_t) +
@@ -1116,18 +1236,22 @@ static int launch_bwd1(const ScanBwdArgs& a, hipStream_t stream) {
     return MXVL_ERR_LAUNCH;
   const int dpg = a.dim / a.G;
   dim3 grid(a.G * ((dpg + DT - 1) / DT), FOLD ? (a.batch + a.fold_bpp - 1) / a.fold_bpp : a.batch), block(NT);
+  if (det) {
+    const int rc = det_redirect(a, det, (dpg + DT - 1) / DT, (int)grid.y, stream);
+    if (rc != MXVL_OK) return rc;
+  }
   hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
   return launch_status();
 }
 // dstate 16 (every Mamba block of the reference) takes the instantiation with the unrolled state loop
 template <typename io_t, int NWAVES, bool VEC>
-static int launch_bwd(const ScanBwdArgs& a, hipStream_t stream) {
+static int launch_bwd(const ScanBwdArgs& a, hipStream_t stream, ScanDet* det) {
   if constexpr (VEC && sizeof(io_t) == 2 && NWAVES == 8) {     // rows by LDS-DMA: whole 8-step lanes only.  (The 4-wave kernel, 4 flush
     // elements per thread, spills row pointers at 256 VGPRs and reloads them between the DMA requests: every reload waits for the
     // requests before it.)
-    if (a.N == 16 && a.L % 8 == 0 && !a.out_f32) return launch_bwd1<io_t, NWAVES, VEC, 16, false, true>(a, stream);
+    if (a.N == 16 && a.L % 8 == 0 && !a.out_f32) return launch_bwd1<io_t, NWAVES, VEC, 16, false, true>(a, stream, det);
   }
-  return a.N == 16 ? launch_bwd1<io_t, NWAVES, VEC, 16>(a, stream) : launch_bwd1<io_t, NWAVES, VEC, 0>(a, stream);
+  return a.N == 16 ? launch_bwd1<io_t, NWAVES, VEC, 16>(a, stream, det) : launch_bwd1<io_t, NWAVES, VEC, 0>(a, stream, det);
 }
 
 // 8-wave workgroups own 32 rows: the dB/dC tile is pre-summed over twice as many rows before it leaves the workgroup
@@ -1142,12 +1266,12 @@ static bool bwd_wide(int batch, int dim, int G, int /*L*/) {
 }
 
 template <typename io_t>
-static int dispatch_bwd(const ScanBwdArgs& a, hipStream_t stream) {
+static int dispatch_bwd(const ScanBwdArgs& a, hipStream_t stream, ScanDet* det) {
   {
     bool taken = false;
-    int rc = try_n1_bwd<io_t>(a, stream, taken);
+    int rc = try_n1_bwd<io_t>(a, stream, taken, det);
     if (rc != MXVL_OK || taken) return rc;
-    rc = try_n1_short_bwd<io_t>(a, stream, taken);
+    rc = try_n1_short_bwd<io_t>(a, stream, taken, det);
     if (rc != MXVL_OK || taken) return rc;
   }
   if (a.fold_magic) {   // batch folded into the sequence (MXVL_SCAN_FOLD_BATCH): aligned rows, dstate 16, io-dtype dout
@@ -1158,15 +1282,15 @@ static int dispatch_bwd(const ScanBwdArgs& a, hipStream_t stream) {
     const long tiles32 = parts * a.G * ((a.dim / a.G + 31) / 32);
     const int fv = mxvl_scan_bwd_variant();       // tests: 1 forces the 8-wave walk at small sizes, 2 the 4-wave walk
     if ((a.dim / a.G) % 32 == 0 && (fv == 1 || (fv != 2 && tiles32 >= 256))) {
-      if constexpr (sizeof(io_t) == 2) return launch_bwd1<io_t, 8, true, 16, true, true>(a, stream);     // rows by LDS-DMA
-      else return launch_bwd1<io_t, 8, true, 16, true>(a, stream);
+      if constexpr (sizeof(io_t) == 2) return launch_bwd1<io_t, 8, true, 16, true, true>(a, stream, det);     // rows by LDS-DMA
+      else return launch_bwd1<io_t, 8, true, 16, true>(a, stream, det);
     }
-    return launch_bwd1<io_t, 4, true, 16, true>(a, stream);
+    return launch_bwd1<io_t, 4, true, 16, true>(a, stream, det);
   }
   const int variant = mxvl_scan_bwd_variant();   // tests / A-B measurements: 0 automatic
   const bool wide = variant == 1 ? true : variant == 2 ? false : bwd_wide(a.batch, a.dim, a.G, a.L);
-  if (wide) return a.vec_ok ? launch_bwd<io_t, 8, true>(a, stream) : launch_bwd<io_t, 8, false>(a, stream);
-  return a.vec_ok ? launch_bwd<io_t, 4, true>(a, stream) : launch_bwd<io_t, 4, false>(a, stream);
+  if (wide) return a.vec_ok ? launch_bwd<io_t, 8, true>(a, stream, det) : launch_bwd<io_t, 8, false>(a, stream, det);
+  return a.vec_ok ? launch_bwd<io_t, 4, true>(a, stream, det) : launch_bwd<io_t, 4, false>(a, stream, det);
 }
 
 }  // namespace mxvl
@@ -1176,11 +1300,15 @@ using namespace mxvl;
 extern "C" int mxvl_scan_check(const mxvl_scan_desc* d);
 
 // The per-tile dB/dC workspace + reduce kernel of ABI v3 measured slower than the fp32 atomics at every shape
-// (profiles/r02_bwd_workspace_ab.txt: 1.47 vs 1.27 ms) and was removed in round 3: no scratch is useful, the descriptor's
-// workspace fields are ignored.
+// (profiles/r02_bwd_workspace_ab.txt: 1.47 vs 1.27 ms) and was removed in round 3: in the default mode no scratch is useful and
+// the descriptor's workspace fields are ignored.  Deterministic mode (mxvl_set_deterministic) is that form again, for every
+// accumulated output: see the formula in include/mxvl.h.
 extern "C" int64_t mxvl_scan_bwd_workspace_bytes(const mxvl_scan_desc* f) {
-  (void)f;
-  return 0;
+  if (!g_deterministic) return 0;
+  if (mxvl_scan_check(f) != MXVL_OK) return -1;
+  int tiles, red;
+  scan_det_bound(f->batch, f->dim, f->seqlen, f->n_groups, f->dstate, f->z != nullptr, (f->flags & MXVL_SCAN_FOLD_BATCH) != 0, tiles, red);
+  return 4 * scan_det_floats(f->batch, f->dim, f->seqlen, f->n_groups, f->dstate, tiles, red);
 }
 
 extern "C" int mxvl_scan_bwd(const mxvl_scan_bwd_desc* d, void* hip_stream) {
@@ -1210,6 +1338,7 @@ extern "C" int mxvl_scan_bwd(const mxvl_scan_bwd_desc* d, void* hip_stream) {
   a.dA = (float*)d->dA; a.dB = (float*)d->dB; a.dC = (float*)d->dC; a.dD = (float*)d->dD; a.dbias = (float*)d->ddelta_bias;
   a.dl_ratio = f->delta_group_ratio > 1 ? f->delta_group_ratio : 1;
   a.dl_magic = delta_magic(a.dl_ratio);
+  a.det = 0; a.red_ss = 0;
   if (f->dstate > 64) return MXVL_ERR_UNSUPPORTED;
   a.ablate = 0;
   a.fold_magic = 0; a.fold_bpp = 0; a.fold_cpp = 0;
@@ -1245,9 +1374,21 @@ extern "C" int mxvl_scan_bwd(const mxvl_scan_bwd_desc* d, void* hip_stream) {
     a.vec_ok = ok ? 1 : 0;
   }
   hipStream_t stream = (hipStream_t)hip_stream;
-  switch (f->io_dtype) {
-    case MXVL_F32: return dispatch_bwd<float>(a, stream);
-    case MXVL_BF16: return dispatch_bwd<bf16_t>(a, stream);
-    default: return dispatch_bwd<f16_t>(a, stream);
+  ScanDet det{};
+  const bool deterministic = g_deterministic != 0;
+  if (deterministic) {     // checked before anything is enqueued
+    scan_det_bound(a.batch, a.dim, a.L, a.G, a.N, a.z != nullptr, a.fold_magic != 0, det.max_tiles, det.max_red);
+    if (!d->workspace) return MXVL_ERR_NULL;
+    if ((uintptr_t)d->workspace % 4 != 0) return MXVL_ERR_STRIDE;
+    if (d->workspace_bytes < 4 * scan_det_floats(a.batch, a.dim, a.L, a.G, a.N, det.max_tiles, det.max_red)) return MXVL_ERR_SHAPE;
+    det.ws = (float*)d->workspace;
   }
+  ScanDet* const dp = deterministic ? &det : nullptr;
+  switch (f->io_dtype) {
+    case MXVL_F32: rc = dispatch_bwd<float>(a, stream, dp); break;
+    case MXVL_BF16: rc = dispatch_bwd<bf16_t>(a, stream, dp); break;
+    default: rc = dispatch_bwd<f16_t>(a, stream, dp); break;
+  }
+  if (rc != MXVL_OK || !deterministic) return rc;
+  return det_fold(a, det, stream);
 }

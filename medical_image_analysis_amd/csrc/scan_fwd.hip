@@ -365,6 +365,7 @@ namespace mxvl {
 
 // ---------------------------------------------------------------------------------------------
 thread_local int g_last_hip_error = 0;   // mxvl_common.h: the library's one last-error slot
+int g_deterministic = 0;                 // mxvl_common.h: mxvl_set_deterministic
 static thread_local const char* g_last_kernel = "none";
 static thread_local int g_variant = 0;   // per calling thread: a test / bench hook, not process-global state
 
@@ -598,6 +599,11 @@ int mxvl_scan_fold_slots(int batch, int seqlen, int dim, int n_groups) {
 int mxvl_last_hip_error(void) { return g_last_hip_error; }
 void mxvl_set_scan_variant(int v) { g_variant = MXVL_ABL(true) ? v : (v & 0xffff); }
 int mxvl_scan_bwd_variant(void) { return (g_variant >> 8) & 0xff; }
+int mxvl_set_deterministic(int on) {
+  const int was = g_deterministic;
+  g_deterministic = on ? 1 : 0;
+  return was;
+}
 const char* mxvl_last_scan_kernel(void) { return g_last_kernel; }
 
 int mxvl_scan_check(const mxvl_scan_desc* d) {

@@ -103,8 +103,10 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_n1_bwd_kernel(const ScanBwdA
   const int npass = (L + 64 * T - 1) / (64 * T);
   const io_t* Bp = (const io_t*)p.B + (int64_t)b * p.B_bs + (int64_t)g * p.B_gs;
   const io_t* Cp = (const io_t*)p.C + (int64_t)b * p.C_bs + (int64_t)g * p.C_gs;
-  float* dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)g * p.dB_gs;
-  float* dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)g * p.dC_gs;
+  // deterministic mode: the workgroup's own slot, (group, tile of NWAVES rw channels) = its index among the batch element's workgroups
+  const int gu = p.det ? (d0 - wave * rw) / (NWAVES * rw) : g;
+  float* dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)gu * p.dB_gs;
+  float* dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)gu * p.dC_gs;
 
   struct Req { raw_t u, dl; raw_t gy; float4 gf[OF32 ? T / 4 : 1]; float A2, Dv, bias, cF; };
   for (int k = npass - 1; k >= 0; --k) {
@@ -250,9 +252,10 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_n1_bwd_kernel(const ScanBwdA
       dD_p = n1b_sum_to_lane63(dD_p);
       db_p = n1b_sum_to_lane63(db_p);
       if (lane == 63) {
-        unsafeAtomicAdd(p.dA + (int64_t)d, dA_p);           // dstate 1: dA is (dim, 1)
-        if (p.dD) unsafeAtomicAdd(p.dD + d, dD_p);
-        if (p.dbias) unsafeAtomicAdd(p.dbias + d, db_p);
+        const int64_t ro = ((int64_t)b * npass + k) * p.red_ss + d;   // deterministic mode: a slot per (batch element, pass)
+        unsafeAtomicAdd(p.dA + ro, dA_p);                   // dstate 1: dA is (dim, 1)
+        if (p.dD) unsafeAtomicAdd(p.dD + ro, dD_p);
+        if (p.dbias) unsafeAtomicAdd(p.dbias + ro, db_p);
       }
       cur = nx1;
       nx1 = nx2;

@@ -146,8 +146,9 @@ __global__ __launch_bounds__(NW * 64) void scan_n1_short_bwd_kernel(const ScanBw
       sh[t * 64 + lane] = h;
     }
   }
-  float* dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)g * p.dB_gs;
-  float* dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)g * p.dC_gs;
+  const int gu = p.det ? d0 / 64 : g;                      // deterministic mode: the wave's own (group, 64-channel tile) slot
+  float* dBp = p.dB + (int64_t)b * p.dB_bs + (int64_t)gu * p.dB_gs;
+  float* dCp = p.dC + (int64_t)b * p.dC_bs + (int64_t)gu * p.dC_gs;
   float gg = 0.0f, dA_p = 0.0f, dD_p = 0.0f, db_p = 0.0f;     // gg = a_{t+1} g_{t+1}
   for (int t = L - 1; t >= 0; --t) {
     const float uu = io::ld(ru + t);
@@ -178,9 +179,10 @@ __global__ __launch_bounds__(NW * 64) void scan_n1_short_bwd_kernel(const ScanBw
     db_p += dd;
     gg = ga;
   }
-  unsafeAtomicAdd(p.dA + (int64_t)d, dA_p);               // dstate 1: dA is (dim, 1)
-  if (p.dD) unsafeAtomicAdd(p.dD + d, dD_p);
-  if (p.dbias) unsafeAtomicAdd(p.dbias + d, db_p);
+  const int64_t ro = (int64_t)b * p.red_ss + d;           // deterministic mode: a slot per batch element (red_ss = 0 otherwise)
+  unsafeAtomicAdd(p.dA + ro, dA_p);                       // dstate 1: dA is (dim, 1)
+  if (p.dD) unsafeAtomicAdd(p.dD + ro, dD_p);
+  if (p.dbias) unsafeAtomicAdd(p.dbias + ro, db_p);
   n1s_wave_sync();
   n1s_copy_out((io_t*)p.du + row0 * L, su, 64 * L * (int)sizeof(io_t), lane);
   n1s_copy_out((io_t*)p.ddelta + row0 * L, sd, 64 * L * (int)sizeof(io_t), lane);

@@ -225,7 +225,13 @@ def scan_bwd_raw(u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout
     desc.dout, desc.du, desc.ddelta, desc.dz = dout.data_ptr(), du.data_ptr(), ddelta.data_ptr(), _abi.ptr(dz)
     desc.dA, desc.dB, desc.dC = dA.data_ptr(), dB.data_ptr(), dC.data_ptr()
     desc.dD, desc.ddelta_bias = _abi.ptr(dD), _abi.ptr(dbias)
-    desc.workspace, desc.workspace_bytes = None, 0     # ABI v3 field, ignored since round 3 (dB / dC leave as fp32 atomics)
+    desc.workspace, desc.workspace_bytes = None, 0     # default mode: ignored (dB / dC leave as fp32 atomics)
+    nbytes = _abi.det_workspace_bytes("mxvl_scan_bwd_workspace_bytes", desc.fwd)
+    if nbytes:       # deterministic mode: private slots + a fold in index order (include/mxvl.h mxvl_set_deterministic)
+        # (with torch.use_deterministic_algorithms(True), torch.utils.deterministic.fill_uninitialized_memory -- on by default --
+        #  makes this torch.empty a fill of the whole workspace, before the entry's own zero-fill of what it uses: DESIGN.md 4.12)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)     # a plain allocation on the current stream: capturable
+        desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
     _timed("scan_bwd", "mxvl_scan_bwd", desc, u.device,
            lambda: scan_algorithmic_bytes(batch, dim, L, A.shape[1], B.shape[1], u.element_size(), z is not None, True, _ckpt_chunks(ckpt, batch, dim)))
     if ratio > 1:
@@ -367,6 +373,8 @@ def gemm_tn_takes(a_km, b_kn):
     """Shapes / layouts mxvl_gemm_tn accepts AND wins on (tools/wgrad_tn_bench.py): 16-bit token-major operands with unit column
     stride, whole 64-token K steps, 16-byte aligned rows."""
     if not (_WGRAD_TN and a_km.is_cuda and a_km.dtype in (torch.bfloat16, torch.float16) and b_kn.dtype == a_km.dtype):
+        return False
+    if _abi.is_deterministic():      # mxvl_gemm_tn refuses in deterministic mode (atomic epilogue): the plane-sum form is order-fixed
         return False
     K, M = a_km.shape
     N = b_kn.shape[1]
@@ -868,7 +876,9 @@ class _MambaInnerNativeFn(torch.autograd.Function):
 def mamba_inner_fn_native(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                           A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
     """mamba_inner_fn's signature (out_proj_weight=None: mamba_inner_fn_no_out_proj's result, (batch, d_inner, seqlen)) served by the
-    single C-ABI entry mxvl_mamba_inner_fwd / _bwd -- what a non-torch host of libmxvl.so calls.  The projections run in xz's dtype."""
+    single C-ABI entry mxvl_mamba_inner_fwd / _bwd -- what a non-torch host of libmxvl.so calls.  The projections run in xz's dtype.
+    In deterministic mode (set_deterministic(True), or torch.use_deterministic_algorithms(True) with the default None) the backward of
+    this function raises MXVL_ERR_UNSUPPORTED: the composed entry refuses the mode; mamba_inner_fn is the covered path."""
     if B is not None or C is not None or B_proj_bias is not None or C_proj_bias is not None:
         raise NotImplementedError("mamba_inner_fn_native: input-dependent B / C without projection biases (what the reference passes)")
     if xz.dim() != 3 or xz.shape[1] % 2 != 0:
