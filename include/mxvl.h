@@ -285,6 +285,22 @@ typedef struct mxvl_gemv_desc {
  * The cache is (rows, n_kv_heads, max_len, head_dim) bf16 indexed by PHYSICAL slot; slot_table[row][t] names the slot
  * holding position t of the hypothesis that `row` continues, so beam re-ordering never moves cache lines.
  */
+/* FP8 KV cache: `dtype | MXVL_KV_FP8`.  k_cache / v_cache are then (rows, n_kv_heads, max_len, head_dim) BYTES of OCP E4M3 codes
+ * (torch.float8_e4m3fn: bias 7, no infinities, 0x7f / 0xff NaN, largest finite 448) and kv_scale two fp32 on the device, the K and
+ * the V scale of this layer, each a power of two s = 2^j; qkv, out and q_rope stay `dtype & ~MXVL_KV_FP8`:
+ *   append   code = rne_e4m3(clamp(x / s, -448, 448))     x: the rotated new key / the new value; the clamp is explicit
+ *   read     x^ = float(code) * s                         exact in `dtype` for j in [-15, 7] (fp16) / [-100, 100] (bf16): every
+ *                                                         finite code times such a scale is a bf16 / fp16 value, no second rounding
+ * A position is seen quantised from the step that writes it: the new key / value of this call enter its attention as x^, not as x.
+ * The caller picks j = ceil(log2(amax / 224)) over the prompt's K (V) of the layer -- 224 = 448 / 2 leaves a factor two for the
+ * generated positions -- clamped to the range above, 0 for amax = 0 or non-finite; the library only requires a power of two.
+ * The arithmetic is that of the 16-bit kernels over x^ (fp32 sums, beams: 16-bit matrix-core products of code values, P rounded to
+ * 16 bits); the K scale multiplies the score, the V scale the output, once each.
+ * head_dim 64 and 128 (256: MXVL_ERR_UNSUPPORTED); kv_scale == NULL is MXVL_ERR_NULL; `dtype & ~MXVL_KV_FP8` is validated as `dtype`
+ * was, so the flag beside MXVL_W_INT8 / MXVL_W_MXFP4 or an unknown dtype is MXVL_ERR_DTYPE -- all before any launch.  Every other decode
+ * entry refuses the flag with MXVL_ERR_DTYPE.  kv_scale is a TRAILING field added without a new ABI version, read only behind the
+ * flag (the argument of w_scale / w2_scale above). */
+#define MXVL_KV_FP8 0x400
 typedef struct mxvl_decode_attn_desc {
   int32_t rows, n_heads, n_kv_heads, head_dim, max_len;
   float scale;
@@ -302,7 +318,8 @@ typedef struct mxvl_decode_attn_desc {
                                (the prompt, the common generated prefix) are read once for all of them; both products run on the
                                matrix cores and the probabilities are rounded to bf16 before the second one (softmax(...).to(bf16) @ V
                                of the modules); needs rows * n_kv_heads * max_len * head_dim < 2^31 (32-bit cache offsets) */
-  int32_t dtype;            /* ABI v8: mxvl_dtype of qkv, the caches, out, q_rope (0 = MXVL_BF16) */
+  int32_t dtype;            /* ABI v8: mxvl_dtype of qkv, the caches, out, q_rope (0 = MXVL_BF16); | MXVL_KV_FP8: the caches are E4M3 bytes */
+  const void *kv_scale;     /* with MXVL_KV_FP8 only (never read otherwise): device, two fp32 -- the K scale and the V scale of this layer */
 } mxvl_decode_attn_desc;
 
 /*

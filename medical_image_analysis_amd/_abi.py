@@ -20,6 +20,7 @@ ABI_VERSION = 13
 MXVL_F32, MXVL_BF16, MXVL_F16 = 0, 1, 2
 MXVL_W_INT8 = 0x100      # mxvl_gemv_desc.dtype flag: W / W2 are int8 codes, w_scale / w2_scale their row-wise absmax
 MXVL_W_MXFP4 = 0x200     # mxvl_gemv_desc.dtype flag: W / W2 are packed E2M1 codes (N, K / 2), w_scale / w2_scale their E8M0 block scales (N, K / 32)
+MXVL_KV_FP8 = 0x400      # mxvl_decode_attn_desc.dtype flag: k_cache / v_cache are OCP E4M3 bytes, kv_scale their two power-of-two scales
 SCAN_DELTA_SOFTPLUS = 1
 SCAN_OUT_F32 = 2          # out / dout fp32 whatever io_dtype is (the oflex i16o32 mode)
 SCAN_FOLD_BATCH = 4       # the batch folded into the sequence (short rows; ask mxvl_scan_fold_ok)
@@ -156,6 +157,7 @@ class DecodeAttnDesc(ctypes.Structure):
         ("qkv", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("k_cache", c_void_p), ("v_cache", c_void_p),
         ("slot_table", c_void_p), ("pos", c_void_p), ("mask", c_void_p), ("out", c_void_p), ("q_rope", c_void_p),
         ("beams", c_int32), ("dtype", c_int32),
+        ("kv_scale", c_void_p),
     ]
 
 

@@ -267,7 +267,7 @@ __device__ __forceinline__ float group_sum(float s) {
   if constexpr (LPR >= 8) s += mv(s, std::integral_constant<int, 0x141>{});   // row_half_mirror
   if constexpr (LPR >= 16) s += mv(s, std::integral_constant<int, 0x140>{});  // row_mirror
   if constexpr (LPR >= 32) s += __shfl_xor(s, 16, 64);                      // the other row (head_dim 256 only)
-  static_assert(LPR == 8 || LPR == 16 || LPR == 32, "8 columns per lane, head_dim 64 / 128 / 256");
+  static_assert(LPR == 4 || LPR == 8 || LPR == 16 || LPR == 32, "8 columns per lane, head_dim 64 / 128 / 256; 16 with the fp8 cache (64 / 128)");
   return s;
 }
 
@@ -712,6 +712,434 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
   }
 }
 
+// ---- MXVL_KV_FP8 (include/mxvl.h): the two kernels above over a cache of OCP E4M3 codes, one power-of-two scale per tensor ---------
+// Same structure as their 16-bit twins -- RoPE of the new q / k, append at *pos, slot-table indirection, mask, one-pass softmax, the
+// fresh position as its own partial -- over cache rows of D BYTES.  The new K / V are encoded first (code = rne_e4m3(clamp(x / s)))
+// and enter this step's attention as code * s, like every cached position: a position is seen quantised from the step that writes
+// it.  The scales never touch an element: the K scale rides on the (already scaled) query, the V scale on the final output -- both
+// exact, they are powers of two -- so what is summed are plain code values.
+struct AttnArgsKv8 {
+  AttnArgs a;          // kc / vc hold bytes (rows, Hkv, max_len, D)
+  const float* kvs;    // device: {K scale, V scale} of this layer
+};
+
+// One workgroup per (head, row).  LDS-DMA moves 16 bytes per lane, so a lane owns 16 elements of a cache row and LPR = D/16 lanes
+// (4 or 8) share it: a wave covers 64/LPR positions per trip, twice decode_attn_kernel's, with the same ring ([K 1 KB | V 1 KB] per
+// trip, each lane reading back the 16 bytes it moved) and the same wait counts.
+template <typename E, int D, int NW, int DEPTH>
+__global__ __launch_bounds__(NW * 64) void decode_attn_kv8_kernel(const AttnArgsKv8 pa) {
+  const AttnArgs& p = pa.a;
+  constexpr int LPR = D / 16, RPW = 64 / LPR, NG = NW * RPW;
+  static_assert((DEPTH & (DEPTH - 1)) == 0, "ring slots are picked with a mask");
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int T = p.max_len;
+  char* ring_all = (char*)sm;     // [NW][DEPTH][K 1 KB | V 1 KB]
+  float* sq = sm + NW * DEPTH * 512;   // [D] rotated query x softmax scale x K scale
+  float* sk = sq + D;             // [D] rotated new key, as the value of its code
+  float* sv = sk + D;             // [D] new value, as the value of its code
+  float* gm = sv + D;             // [NG] group maxima
+  float* gl = gm + NG;            // [NG] group sums
+  float* go = gl + NG;            // [NG][D] group outputs
+  int* ssl = (int*)(go + NG * D); // [T] slot of each position, -1 = masked
+  uint8_t* const kc8 = (uint8_t*)p.kc;
+  uint8_t* const vc8 = (uint8_t*)p.vc;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = blockIdx.x, m = blockIdx.y;
+  const int group = p.H / p.Hkv, hk = h / group;
+  const int pos = (int)*p.pos;
+  const float sK = pa.kvs[0], sV = pa.kvs[1];
+  const size_t row = (size_t)m * (p.H + 2 * p.Hkv) * D;
+  const uint16_t* q = p.qkv + row + (size_t)h * D;
+  const uint16_t* kn = p.qkv + row + (size_t)(p.H + hk) * D;
+  const uint16_t* vn = p.qkv + row + (size_t)(p.H + p.Hkv + hk) * D;
+  // (the prologue's loads all go out before anything is used: see decode_attn_kernel)
+  {
+    const int t = tid < T ? tid : T - 1;
+    const int64_t mk = p.mask[(size_t)m * T + t];
+    const int sl = p.slot[(size_t)m * T + t];
+    __builtin_amdgcn_sched_barrier(0);
+    ssl[t] = mk != 0 ? sl : -1;
+  }
+  for (int t = tid + NW * 64; t <= pos; t += NW * 64) {
+    const int64_t mk = p.mask[(size_t)m * T + t];
+    const int sl = p.slot[(size_t)m * T + t];
+    ssl[t] = mk != 0 ? sl : -1;
+  }
+  if (tid < D) {
+    const int d = tid, half = D / 2;
+    const int dp = d < half ? d + half : d - half;
+    const uint16_t rq = q[d], rqo = q[dp], rk = kn[d], rko = kn[dp], rv = vn[d];
+    const float rc = p.cosv[(size_t)m * D + d], rs = p.sinv[(size_t)m * D + d];
+    const float c = E::rr(rc), s = E::rr(rs);
+    const float qd = E::f(rq), qo = d < half ? -E::f(rqo) : E::f(rqo);
+    const float kd = E::f(rk), ko = d < half ? -E::f(rko) : E::f(rko);
+    const float qr = E::rr(E::rr(qd * c) + E::rr(qo * s));
+    const float kr = E::rr(E::rr(kd * c) + E::rr(ko * s));
+    const uint32_t ck = e4m3_encode(kr * pow2_recip(sK)), cv = e4m3_encode(E::f(rv) * pow2_recip(sV));
+    sq[d] = qr * p.scale * sK;
+    if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
+    sk[d] = e4m3_decode(ck);
+    sv[d] = e4m3_decode(cv);
+    if (h % group == 0) {  // one head of the group appends to the cache (slot m owns position pos of beam m)
+      const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
+      kc8[o] = (uint8_t)ck;
+      vc8[o] = (uint8_t)cv;
+    }
+  }
+  __syncthreads();
+  const int sub = lane % LPR, g = wave * RPW + lane / LPR;
+  float qv[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) qv[j] = sq[sub * 16 + j];
+  float mx = -1e30f, l = 0.0f, o[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) o[j] = 0.0f;
+  auto fold = [&](bool live, const float* kf, const float* vf) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s = fmaf(qv[j], kf[j], s);
+    s = group_sum<LPR>(s);
+    const float mn = live ? fmaxf(mx, s) : mx;
+    const float corr = fast_exp(mx - mn), pr = live ? fast_exp(s - mn) : 0.0f;
+    mx = mn;
+    l = fmaf(l, corr, pr);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) o[j] = fmaf(o[j], corr, pr * vf[j]);
+  };
+  const int ntrips = (pos + NG - 1) / NG;
+  char* ring = ring_all + wave * (DEPTH * 2048);
+  const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
+  const size_t c1 = (size_t)p.Hkv * T * D, lane_off = (size_t)hk * T * D + sub * 16;   // bytes
+  uint32_t livebits = 0;                 // bit (j & 31): trip j of this lane group carries an attended position
+  int iss = 0;
+  auto issue = [&]() {
+    if (iss >= ntrips) return;
+    const int t = g + iss * NG;
+    const int sl = ssl[t < pos ? t : 0];
+    const bool live = t < pos && sl >= 0;    // a masked / out-of-range group re-reads the row's first cache line
+    const size_t off = (live ? (size_t)sl * c1 + (size_t)t * D : (size_t)m * c1) + lane_off;
+    const int bit = iss & 31;
+    livebits = (livebits & ~(1u << bit)) | ((uint32_t)live << bit);
+    const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(iss & (DEPTH - 1)) * 2048u);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(dst), "v"(kc8 + off), "v"(vc8 + off) : "memory", "scc");
+    ++iss;
+  };
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the counts below are counts of ring trips only
+#pragma unroll
+  for (int j = 0; j < DEPTH; ++j) issue();
+  for (int j = 0; j < ntrips; ++j) {                       // cached positions 0 .. pos-1
+    if (j + DEPTH <= ntrips) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (DEPTH - 1)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const char* slot = ring + (j & (DEPTH - 1)) * 2048 + lane * 16;
+    const uint4 kq = *(const uint4*)slot, vq = *(const uint4*)(slot + 1024);
+    const bool live = (livebits >> (j & 31)) & 1u;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // both rows are in registers: the slot may be refilled
+    issue();
+    float kf[16], vf[16];
+    e4m3_unpack4(kq.x, kf); e4m3_unpack4(kq.y, kf + 4); e4m3_unpack4(kq.z, kf + 8); e4m3_unpack4(kq.w, kf + 12);
+    e4m3_unpack4(vq.x, vf); e4m3_unpack4(vq.y, vf + 4); e4m3_unpack4(vq.z, vf + 8); e4m3_unpack4(vq.w, vf + 12);
+    fold(live, kf, vf);
+  }
+  if (g == 0) {  // the fresh position (always attended: its mask bit was just set), as its codes' values
+    float kf[16], vf[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { kf[j] = sk[sub * 16 + j]; vf[j] = sv[sub * 16 + j]; }
+    fold(ssl[pos] >= 0, kf, vf);
+  }
+  if (sub == 0) { gm[g] = mx; gl[g] = l; }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) go[g * D + sub * 16 + j] = o[j];
+  __syncthreads();
+  if (tid < D) {
+    float gmax = -1e30f;
+    for (int i = 0; i < NG; ++i) gmax = fmaxf(gmax, gm[i]);
+    float num = 0.0f, den = 0.0f;
+    for (int i = 0; i < NG; ++i) {
+      const float w = fast_exp(gm[i] - gmax);
+      num = fmaf(w, go[i * D + tid], num);
+      den = fmaf(w, gl[i], den);
+    }
+    p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den * sV);
+  }
+}
+
+// The beams of one sample in one workgroup (grid: head x sample), as decode_attn_beams_mfma_kernel: shared positions read once, both
+// products on the 16-bit matrix cores (16x16x32 for K Q^T, 16x16x16 for V^T P), P rounded to 16 bits.  A tile is 16 positions x D
+// bytes -- half the DMA instructions and half the LDS of the twin -- and a fragment becomes 16-bit elements AFTER its LDS read (a
+// code's value is exact in bf16 and fp16, so the MFMA operands are plain code values; the scales enter as in the per-row kernel).
+//   K: lane (pos = l16, q4) reads the 8 bytes K[pos][32 kk + 8 q4 .. + 8) with one ds_read_b64 and widens them to an A operand;
+//   V: lane (d = 16 dt + l16, q4) reads the four bytes V[4 q4 .. 4 q4 + 3][d] one by one (DESIGN.md 4.7 on the 8-bit transpose read).
+// The DMA writes LDS linearly, so the swizzle is on the source address, per 16-byte unit: rows D bytes apart share banks every
+// 256 / D rows; XOR-ing the unit index with (row >> 2) & 3 (D = 64) / (row >> 1) & 7 (D = 128) spreads the 16 rows of a K read over
+// all 64 banks twice (the minimum for 512 bytes) and gives the four rows of a V byte read (4 q4 + i) four different units.
+template <int D> __device__ __forceinline__ int attn_tile8_key(int row) { return D == 64 ? ((row >> 2) & 3) : ((row >> 1) & 7); }
+template <int D> __device__ __forceinline__ int attn_tile8_off(int row, int unit) { return row * D + ((unit ^ attn_tile8_key<D>(row)) << 4); }
+
+template <typename E, int D, int NB, int NW>
+__global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const AttnArgsKv8 pa) {
+  const AttnArgs& p = pa.a;
+  typedef short s16x4 __attribute__((ext_vector_type(4)));
+  typedef elt_u32x4 bf16x8;      // eight 16-bit elements of a lane (E decides what they mean)
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  static_assert(D == 64 || D == 128, "the fp8 cache serves head_dim 64 and 128");
+  constexpr int UPR = D / 16, RPI = 64 / UPR;    // 16-byte units per cache row; rows per DMA instruction (1 KB)
+  constexpr int TILE = 16, NI = TILE / RPI;      // positions per tile; DMA instructions per K (or V) tile
+  constexpr int TB = TILE * D, STAGE = 2 * TB, NST = 2, OPS = 2 * NI;
+  constexpr int NKK = D / 32, NDT = D / 16, NT = NW * 64, NWP = NW + 1;
+  static_assert(NW * NST * STAGE >= NB * NWP * D * 4, "wo reuses the ring");
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int T = p.max_len;
+  char* ring_all = (char*)sm;                                   // [NW][NST][K tile | V tile]; after the loop: wo [NB][NWP][D] fp32
+  uint16_t* sqb = (uint16_t*)(ring_all + NW * NST * STAGE);     // [16][D] rotated queries, 16-bit (rows nb .. 15 zero)
+  float* sq = (float*)(sqb + 16 * D);                           // [NB][D] rotated queries x softmax scale x K scale (fresh position)
+  float* sk = sq + NB * D;                                      // [NB][D] rotated new keys, as the values of their codes
+  float* sv = sk + NB * D;                                      // [NB][D] new values, as the values of their codes
+  float* wm = sv + NB * D;                                      // [NB][NWP] partial maxima
+  float* wl = wm + NB * NWP;                                    // [NB][NWP] partial sums
+  int* ssl = (int*)(wl + NB * NWP);                             // [NB][T] slot of each position, -1 = masked
+  float* wo = (float*)ring_all;
+  __shared__ int s_nsh;
+  uint8_t* const kc8 = (uint8_t*)p.kc;
+  uint8_t* const vc8 = (uint8_t*)p.vc;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = blockIdx.x, m0 = blockIdx.y * NB;
+  const int group = p.H / p.Hkv, hk = h / group;
+  const int pos = (int)*p.pos;
+  const float sK = pa.kvs[0], sV = pa.kvs[1];
+  constexpr int RI = (NB * D + NT - 1) / NT;
+  uint16_t rope_q[RI], rope_qo[RI], rope_k[RI], rope_ko[RI], rope_v[RI];
+  float rope_c[RI], rope_s[RI];
+#pragma unroll
+  for (int it = 0; it < RI; ++it) {
+    const int i = tid + it * NT < NB * D ? tid + it * NT : 0;
+    const int r = i / D, d = i - r * D, half = D / 2, m = m0 + r;
+    const int dp = d < half ? d + half : d - half;
+    const size_t row = (size_t)m * (p.H + 2 * p.Hkv) * D;
+    const uint16_t* q = p.qkv + row + (size_t)h * D;
+    const uint16_t* kn = p.qkv + row + (size_t)(p.H + hk) * D;
+    const uint16_t* vn = p.qkv + row + (size_t)(p.H + p.Hkv + hk) * D;
+    rope_q[it] = q[d]; rope_qo[it] = q[dp]; rope_k[it] = kn[d]; rope_ko[it] = kn[dp]; rope_v[it] = vn[d];
+    rope_c[it] = p.cosv[(size_t)m * D + d]; rope_s[it] = p.sinv[(size_t)m * D + d];
+  }
+  int64_t mk0[NB];
+  int sl0[NB];
+  {
+    const int t = tid < T ? tid : T - 1;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      mk0[r] = p.mask[(size_t)(m0 + r) * T + t];
+      sl0[r] = p.slot[(size_t)(m0 + r) * T + t];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  for (int i = tid; i < (16 - NB) * D; i += NT) sqb[NB * D + i] = 0;
+  if (tid == 0) s_nsh = pos;
+  __syncthreads();
+  for (int t = tid; t <= pos; t += NT) {
+    int64_t mk[NB];
+    int sl[NB];
+    if (t == tid) {
+#pragma unroll
+      for (int r = 0; r < NB; ++r) { mk[r] = mk0[r]; sl[r] = sl0[r]; }
+    } else {
+#pragma unroll
+      for (int r = 0; r < NB; ++r) {
+        mk[r] = p.mask[(size_t)(m0 + r) * T + t];
+        sl[r] = p.slot[(size_t)(m0 + r) * T + t];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    bool same = true;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      const int v = mk[r] != 0 ? sl[r] : -1;
+      ssl[r * T + t] = v;
+      same = same && v == (mk[0] != 0 ? sl[0] : -1);
+    }
+    const unsigned long long differ = __ballot(!same && t < pos);
+    if (differ != 0 && lane == __ffsll(differ) - 1) atomicMin(&s_nsh, t);
+  }
+  // RoPE of the nb rows' q / k, encode, cache append by one head of each KV group
+  const float rK = pow2_recip(sK), rV = pow2_recip(sV);
+#pragma unroll
+  for (int it = 0; it < RI; ++it) {
+    const int i = tid + it * NT;
+    if (i < NB * D) {
+      const int r = i / D, d = i - r * D, half = D / 2, m = m0 + r;
+      const float c = E::rr(rope_c[it]), sn = E::rr(rope_s[it]);
+      const float qd = E::f(rope_q[it]), qo = d < half ? -E::f(rope_qo[it]) : E::f(rope_qo[it]);
+      const float kd = E::f(rope_k[it]), ko = d < half ? -E::f(rope_ko[it]) : E::f(rope_ko[it]);
+      const float qr = E::rr(E::rr(qd * c) + E::rr(qo * sn));
+      const float kr = E::rr(E::rr(kd * c) + E::rr(ko * sn));
+      const uint32_t ck = e4m3_encode(kr * rK), cv = e4m3_encode(E::f(rope_v[it]) * rV);
+      sq[i] = qr * p.scale * sK;
+      sqb[i] = E::r(qr);
+      if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
+      sk[i] = e4m3_decode(ck);
+      sv[i] = e4m3_decode(cv);
+      if (h % group == 0) {
+        const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
+        kc8[o] = (uint8_t)ck;
+        vc8[o] = (uint8_t)cv;
+      }
+    }
+  }
+  __syncthreads();
+  const int nsh = s_nsh;
+  const int l16 = lane & 15, q4 = lane >> 4;
+  const int ns = (nsh + TILE - 1) / TILE, nt = (pos - nsh + TILE - 1) / TILE, ntiles = ns + NB * nt;
+  // tile iterators (wave-uniform): tile k of this wave -> shared (r < 0) tile k, or tile i of beam r
+  struct Tile { int k, r, i; };
+  auto tile_first = [&](Tile& it) {
+    it.k = wave; it.r = -1; it.i = 0;
+    if (it.k >= ns && it.k < ntiles) { it.r = 0; it.i = it.k - ns; while (it.i >= nt) { it.i -= nt; ++it.r; } }
+  };
+  auto tile_next = [&](Tile& it) {
+    it.k += NW;
+    if (it.k >= ns && it.k < ntiles) {
+      if (it.r < 0) { it.r = 0; it.i = it.k - ns; } else it.i += NW;
+      while (it.i >= nt) { it.i -= nt; ++it.r; }
+    }
+  };
+  char* ring = ring_all + wave * (NST * STAGE);
+  const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
+  const uint32_t c1 = (uint32_t)p.Hkv * (uint32_t)T * D;                    // bytes per cache row (slot); 32-bit offsets: the launcher checks the cache fits
+  const uint32_t hk_off = (uint32_t)hk * (uint32_t)T * D;
+  const uint32_t dummy = (uint32_t)m0 * c1 + hk_off;                        // a masked / out-of-range row re-reads the sample's first line
+  auto issue = [&](const Tile& it, int stage) {
+    if (it.k >= ntiles) return;
+    const int t0 = it.r < 0 ? it.k * TILE : nsh + it.i * TILE, lim = it.r < 0 ? nsh : pos;
+    const int* sp = ssl + (it.r < 0 ? 0 : it.r) * T;
+    const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)stage * STAGE);
+#pragma unroll
+    for (int ii = 0; ii < NI; ++ii) {
+      const int row = ii * RPI + lane / UPR, t = t0 + row;
+      const bool in = t < lim;
+      const int sl = sp[in ? t : 0];
+      const bool live = in && sl >= 0;
+      const uint32_t off = (live ? (uint32_t)sl * c1 + (uint32_t)t * D + hk_off : dummy) + (((lane % UPR) ^ attn_tile8_key<D>(row)) << 4);
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+                   "s_add_u32 m0, m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "s"(dst + ii * 1024), "v"(kc8 + off), "v"(vc8 + off), "n"(TB) : "memory", "scc");
+    }
+  };
+  // B operand of the first product: lane (beam = l16, q4) owns Q[beam][32 kk + 8 q4 .. + 8)
+  bf16x8 qb[NKK];
+#pragma unroll
+  for (int kk = 0; kk < NKK; ++kk) qb[kk] = *(const bf16x8*)(sqb + l16 * D + kk * 32 + q4 * 8);
+  f32x4 oacc[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  float m_run = -1e30f, l_run = 0.0f;            // this lane's beam column; l_run sums this lane's four rows only until the end
+  const float sscale = p.scale * sK;
+  Tile ti, tc;
+  tile_first(ti);
+  tc = ti;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the counts below are counts of ring tiles only
+  issue(ti, 0);
+  tile_next(ti);
+  issue(ti, 1);
+  tile_next(ti);
+  int stage = 0;
+  for (; tc.k < ntiles; tile_next(tc), stage ^= 1) {
+    if (tc.k + NW < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const char* kt = ring + stage * STAGE;
+    const uint8_t* vt = (const uint8_t*)kt + TB;
+    uint2 kraw[NKK];
+    uint32_t vraw[NDT][4];
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) kraw[kk] = *(const uint2*)(kt + attn_tile8_off<D>(l16, kk * 2 + (q4 >> 1)) + (q4 & 1) * 8);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) vraw[dt][i] = vt[attn_tile8_off<D>(q4 * 4 + i, dt) + l16];
+    const int t0 = tc.r < 0 ? tc.k * TILE : nsh + tc.i * TILE, lim = tc.r < 0 ? nsh : pos;
+    const int* sp = ssl + (tc.r < 0 ? 0 : tc.r) * T;
+    bool ok[4];
+    const bool colok = l16 < NB && (tc.r < 0 || l16 == tc.r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = t0 + q4 * 4 + i;
+      ok[i] = colok && t < lim && sp[t < lim ? t : 0] >= 0;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every fragment of the stage is in registers: it may be refilled
+    issue(ti, stage);
+    tile_next(ti);
+    f32x4 sc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) sc = E::mfma32(e4m3_unpack8_elt<E>(kraw[kk].x, kraw[kk].y), qb[kk], sc);
+    float s[4], tmax = -1e30f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      s[i] = sc[i] * sscale;
+      tmax = ok[i] ? fmaxf(tmax, s[i]) : tmax;
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mn = fmaxf(m_run, tmax), corr = fast_exp(m_run - mn);
+    m_run = mn;
+    float pr[4], psum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      pr[i] = ok[i] ? fast_exp(s[i] - mn) : 0.0f;
+      psum += pr[i];
+    }
+    l_run = fmaf(l_run, corr, psum);
+    s16x4 pb;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pb[i] = (short)E::r(pr[i]);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      s16x4 vf;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        vf[i] = (short)e4m3_elt_bits<E>(e4m3_decode(vraw[dt][i]));
+        oacc[dt][i] *= corr;
+      }
+      oacc[dt] = E::mfma16(vf, pb, oacc[dt]);
+    }
+  }
+  // ---- merge: the q-lanes of a column by shuffles, the waves (+ the fresh position as partial NW) through LDS ----------------------
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+  __syncthreads();                          // every wave is done with its ring: wo reuses the memory
+  if (l16 < NB) {
+    if (q4 == 0) { wm[l16 * NWP + wave] = m_run; wl[l16 * NWP + wave] = l_run; }
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      *(f32x4*)(wo + (l16 * NWP + wave) * D + dt * 16 + q4 * 4) = oacc[dt];
+  }
+  for (int r = wave; r < NB; r += NW) {     // the fresh position of beam r: score by one wave
+    float part = 0.0f;
+    for (int d = lane; d < D; d += 64) part = fmaf(sq[r * D + d], sk[r * D + d], part);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+    const bool live = ssl[r * T + pos] >= 0;
+    if (lane == 0) { wm[r * NWP + NW] = live ? part : -1e30f; wl[r * NWP + NW] = live ? 1.0f : 0.0f; }
+    for (int d = lane; d < D; d += 64) wo[(r * NWP + NW) * D + d] = live ? sv[r * D + d] : 0.0f;
+  }
+  __syncthreads();
+  for (int i = tid; i < NB * D; i += NT) {
+    const int r = i / D, d = i - r * D;
+    float gmax = -1e30f;
+#pragma unroll
+    for (int w = 0; w < NWP; ++w) gmax = fmaxf(gmax, wm[r * NWP + w]);
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWP; ++w) {
+      const float c = fast_exp(wm[r * NWP + w] - gmax);
+      num = fmaf(c, wo[(r * NWP + w) * D + d], num);
+      den = fmaf(c, wl[r * NWP + w], den);
+    }
+    p.out[(size_t)(m0 + r) * p.H * D + (size_t)h * D + d] = E::r(num / den * sV);
+  }
+}
+
 // Image cross-attention of a hybrid decoder layer for ONE new token per row (EMRRG/models/hybrid_decoder_layer.py:653-697,
 // `all2media_cross_attn`): ctx = softmax(q K_img^T * scale + mask) V_img from the layer's RoPE'd query to the image keys /
 // values (constant over a generation: projected once when the layer is conditioned), then
@@ -961,6 +1389,68 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
   return launch_status();
 }
 
+// MXVL_KV_FP8: the same two dispatch rules over the byte caches (head_dim 64 / 128; the caller refused 256)
+template <typename E>
+static int launch_decode_attn_kv8(const AttnArgsKv8& ka, int beams, hipStream_t s) {
+  const AttnArgs& a = ka.a;
+  if (beams > 1) {
+    if (beams > 5 || a.rows % beams != 0) return MXVL_ERR_UNSUPPORTED;
+    if ((uint64_t)a.rows * a.Hkv * a.max_len * a.D >= (1ull << 31)) return MXVL_ERR_UNSUPPORTED;   // 32-bit cache offsets
+    const int nb = beams;
+    const size_t stage = (size_t)2 * 16 * a.D;
+    auto lds_of = [&](int nw) {
+      return (size_t)nw * 2 * stage + (size_t)16 * a.D * 2 + sizeof(float) * ((size_t)3 * nb * a.D + 2 * nb * (nw + 1) + (size_t)nb * a.max_len);
+    };
+    const int nw = lds_of(8) > 160 * 1024 ? 4 : 8;
+    const size_t lds = lds_of(nw);
+    if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
+    const dim3 grid(a.H, a.rows / nb), block(nw * 64);
+#define MXVL_ATTN_BEAMS8(DD, NB)                                                                                                   \
+  do {                                                                                                                             \
+    void (*kern)(const AttnArgsKv8) = nw == 8 ? decode_attn_beams_kv8_kernel<E, DD, NB, 8> : decode_attn_beams_kv8_kernel<E, DD, NB, 4>; \
+    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
+      return MXVL_ERR_LAUNCH;                                                                                                      \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, ka);                                                                             \
+  } while (0)
+#define MXVL_ATTN_BEAMS8_D(NB)                                                                                                     \
+  switch (a.D) {                                                                                                                   \
+    case 64: MXVL_ATTN_BEAMS8(64, NB); break;                                                                                      \
+    default: MXVL_ATTN_BEAMS8(128, NB); break;                                                                                     \
+  }
+    switch (nb) {
+      case 2: MXVL_ATTN_BEAMS8_D(2); break;
+      case 3: MXVL_ATTN_BEAMS8_D(3); break;
+      case 4: MXVL_ATTN_BEAMS8_D(4); break;
+      default: MXVL_ATTN_BEAMS8_D(5); break;
+    }
+#undef MXVL_ATTN_BEAMS8_D
+#undef MXVL_ATTN_BEAMS8
+    return launch_status();
+  }
+  constexpr int nw = kAttnWaves;
+  const int NG = nw * 64 / (a.D / 16);
+  const size_t lds0 = sizeof(float) * ((size_t)3 * a.D + 2 * NG + (size_t)NG * a.D + a.max_len);
+  int depth = (size_t)a.H * a.rows <= 256 ? 4 : 2;     // (the 16-bit kernel's rule)
+  while (depth > 2 && lds0 + (size_t)nw * depth * 2048 > 160 * 1024) depth /= 2;
+  const size_t lds = lds0 + (size_t)nw * depth * 2048;
+  if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
+  const dim3 grid(a.H, a.rows), block(nw * 64);
+#define MXVL_ATTN_ROW8(DD) \
+  do { \
+    void (*kern)(const AttnArgsKv8) = depth == 4 ? decode_attn_kv8_kernel<E, DD, nw, 4> : decode_attn_kv8_kernel<E, DD, nw, 2>; \
+    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
+      return MXVL_ERR_LAUNCH; \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, ka); \
+  } while (0)
+  switch (a.D) {
+    case 64: MXVL_ATTN_ROW8(64); break;
+    case 128: MXVL_ATTN_ROW8(128); break;
+    default: return MXVL_ERR_UNSUPPORTED;
+  }
+#undef MXVL_ATTN_ROW8
+  return launch_status();
+}
+
 template <typename E>
 static void launch_cross_attn(const CrossAttnArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
   switch (a.D) {
@@ -1013,9 +1503,14 @@ int mxvl_decode_gemv(const mxvl_gemv_desc* d, void* hip_stream) {
 int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
   if (!d || !d->qkv || !d->cos || !d->sin || !d->k_cache || !d->v_cache || !d->slot_table || !d->pos || !d->mask || !d->out)
     return MXVL_ERR_NULL;
-  if (!decode_dtype_ok(d->dtype)) return MXVL_ERR_DTYPE;
+  // MXVL_KV_FP8 is the one flag this entry knows: a weight flag (or anything else) beside it leaves a value no dtype check accepts
+  const bool kv8 = (d->dtype & MXVL_KV_FP8) != 0;         // kv_scale exists in the caller's struct only behind the flag
+  const int32_t dt = d->dtype & ~MXVL_KV_FP8;
+  if (!decode_dtype_ok(dt)) return MXVL_ERR_DTYPE;
+  if (kv8 && !d->kv_scale) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->n_heads <= 0 || d->n_kv_heads <= 0 || d->n_heads % d->n_kv_heads != 0) return MXVL_ERR_SHAPE;
   if (d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256) return MXVL_ERR_UNSUPPORTED;
+  if (kv8 && d->head_dim == 256) return MXVL_ERR_UNSUPPORTED;   // no fp8-cache kernel at head_dim 256
   AttnArgs a;
   a.rows = d->rows; a.H = d->n_heads; a.Hkv = d->n_kv_heads; a.D = d->head_dim; a.max_len = d->max_len;
   a.scale = d->scale; a.qkv = (const uint16_t*)d->qkv; a.cosv = (const float*)d->cos; a.sinv = (const float*)d->sin;
@@ -1024,7 +1519,13 @@ int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
   a.q_rope = (uint16_t*)d->q_rope;
   a.ablate = MXVL_ABL_ENV("MXVL_ATTN_ABLATE");
   const hipStream_t s = (hipStream_t)hip_stream;
-  return decode_dtype(d->dtype) == MXVL_F16 ? launch_decode_attn<EltF16>(a, d->beams, s) : launch_decode_attn<EltBf16>(a, d->beams, s);
+  if (kv8) {
+    AttnArgsKv8 ka;
+    ka.a = a;
+    ka.kvs = (const float*)d->kv_scale;
+    return decode_dtype(dt) == MXVL_F16 ? launch_decode_attn_kv8<EltF16>(ka, d->beams, s) : launch_decode_attn_kv8<EltBf16>(ka, d->beams, s);
+  }
+  return decode_dtype(dt) == MXVL_F16 ? launch_decode_attn<EltF16>(a, d->beams, s) : launch_decode_attn<EltBf16>(a, d->beams, s);
 }
 
 int mxvl_decode_prologue(const mxvl_decode_prologue_desc* d, void* hip_stream) {

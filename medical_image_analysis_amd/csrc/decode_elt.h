@@ -76,6 +76,40 @@ template <typename E> __device__ inline void elt_unpack8(const uint4 v, float* o
   }
 }
 
+// ---- OCP E4M3 (torch.float8_e4m3fn) codes of the fp8 KV cache (MXVL_KV_FP8, include/mxvl.h) ---------------------------------------
+// gfx950's v_cvt_*_fp8 instructions are the OCP format (gfx942's were FNUZ: another bias, no negative zero).  A code times the
+// tensor's power-of-two scale is exact in the model's 16-bit dtype, so code -> element needs no rounding: bf16 is the upper half of
+// the fp32 bits, fp16 an exact narrowing.
+// code = rne_e4m3(clamp(x, -448, 448)): the clamp is explicit (what the convert does above 448 depends on a mode bit); NaN stays NaN
+__device__ inline uint32_t e4m3_encode(float x) {
+  const float c = fminf(fmaxf(x, -448.0f), 448.0f);
+  x = x != x ? x : c;
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xffu;
+}
+__device__ inline float e4m3_decode(uint32_t code) { return __builtin_amdgcn_cvt_f32_fp8((int)code, 0); }
+// the four codes of a dword as fp32
+__device__ inline void e4m3_unpack4(uint32_t w, float* out) {
+  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  out[0] = lo[0]; out[1] = lo[1]; out[2] = hi[0]; out[3] = hi[1];
+}
+// an E4M3 value (3 mantissa bits, |x| <= 448) as element bits: exact in both types
+template <typename E> __device__ inline uint32_t e4m3_elt_bits(float x) {
+  if constexpr (E::dtype == MXVL_BF16) return __builtin_bit_cast(uint32_t, x) >> 16;
+  else return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);
+}
+// two dwords of codes (eight elements) as the four packed dwords of a 16x16x32 MFMA operand
+template <typename E> __device__ inline elt_u32x4 e4m3_unpack8_elt(uint32_t w0, uint32_t w1) {
+  float f[8];
+  e4m3_unpack4(w0, f);
+  e4m3_unpack4(w1, f + 4);
+  elt_u32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = e4m3_elt_bits<E>(f[2 * j]) | (e4m3_elt_bits<E>(f[2 * j + 1]) << 16);
+  return r;
+}
+// 1 / s of a power-of-two scale s (a normal fp32): exact, no divide
+__device__ inline float pow2_recip(float s) { return __builtin_bit_cast(float, 0x7f000000u - __builtin_bit_cast(uint32_t, s)); }
+
 // mxvl_dtype of a decode descriptor: 0 (what ABI <= 7 callers leave in the reserved field) means bf16
 inline int decode_dtype(int32_t v) { return v == 0 ? MXVL_BF16 : v; }
 // anything but bf16 / fp16 behind that default is refused (MXVL_ERR_DTYPE), not decoded as bf16

@@ -242,7 +242,8 @@ class MambaXrayVLDownStream(nn.Module):
             max_new_tokens=_get(a, "max_new_tokens", 120), repetition_penalty=_get(a, "repetition_penalty", 2.0),
             length_penalty=_get(a, "length_penalty", 2.0), temperature=_get(a, "temperature", 0),
             top_k=_get(a, "top_k", None), top_p=_get(a, "top_p", 1.0), seed=_get(a, "seed", None),
-            eos_token_id=_get(self.llama_tokenizer, "eos_token_id", None), pad_token_id=self.llama_tokenizer.pad_token_id)
+            eos_token_id=_get(self.llama_tokenizer, "eos_token_id", None), pad_token_id=self.llama_tokenizer.pad_token_id,
+            kv_cache_dtype=_get(a, "kv_cache_dtype", None))      # None / "auto": 16-bit KV cache; "fp8": E4M3 (ReportDecoder.generate)
 
     def _eval_step(self, samples, sink):
         refs = self._tokenize_reports(samples["input_text"], "cpu")
@@ -410,6 +411,7 @@ def default_args(**kw):
     base = dict(vision_model="None", type="base", dataset="mimic_cxr", freeze_vm=True, vis_use_lora=False, llm_use_lora=False,
                 low_resource=False, end_sym="</s>", delta_file=None, max_length=100, beam_size=3, do_sample=False,
                 min_new_tokens=80, max_new_tokens=120, repetition_penalty=2.0, length_penalty=2.0, temperature=0,
+                kv_cache_dtype=None,
                 learning_rate=1e-4, max_epochs=1, projection_dim=512, text_encoder_type="Bio_ClinicalBERT")
     base.update(kw)
     return SimpleNamespace(**base)

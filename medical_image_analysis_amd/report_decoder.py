@@ -36,16 +36,60 @@ from .mxfp4_linear import MxFp4Linear
 from .quant_linear import DequantScratch, QuantLinear
 
 
-class KVCache:
-    """Minimal per-layer key/value store with the `update` signature the attention module expects."""
+# ---- kv_cache_dtype="fp8": the quantisation contract of the E4M3 KV cache (include/mxvl.h MXVL_KV_FP8), restated with torch ops ----
+# Per layer and per tensor (K after RoPE, V) one power-of-two scale s = 2^j and OCP float8_e4m3fn codes:
+#   j = ceil(log2(amax / 224)), amax over the whole prompt (224 = 448 / 2: a factor two for the generated positions), clamped so
+#   that every code times s is exact in the cache's 16-bit dtype, 0 for amax = 0 or non-finite;
+#   code = rne_e4m3(clamp(x / s, -448, 448));   x^ = float(code) * s   (exact in the model dtype: no second rounding).
+# The caches below store and return x^ ("fake-quantised"), which makes the eager loop, the torch-module stepper and the CPU the
+# oracle of the fp8 kernels, and the prompt prefill on a HIP device what those kernels continue.
+KV_FP8_MAX, KV_FP8_TARGET = 448.0, 224.0
+KV_FP8_EXP_RANGE = {torch.float16: (-15, 7)}      # every finite code x 2^j survives fp16 there; bf16 / fp32: (-100, 100)
 
-    def __init__(self):
+
+def kv_fp8_scale(x):
+    """The power-of-two scale of a tensor as a 0-dim fp32 tensor on its device (no host read)."""
+    amax = x.detach().float().abs().amax()
+    m, e = torch.frexp(amax)                     # amax = m * 2^e, m in [0.5, 1); 224 = 0.875 * 2^8: the ceil without a log
+    j = e - 8 + (m > 0.875).to(e.dtype)
+    lo, hi = KV_FP8_EXP_RANGE.get(x.dtype, (-100, 100))
+    j = torch.where(torch.isfinite(amax) & (amax > 0), j, torch.zeros_like(j)).clamp(lo, hi)
+    return torch.ldexp(torch.ones_like(amax), j)
+
+
+def kv_fp8_encode(x, s):
+    """E4M3 codes of x under scale s.  The clamp is explicit: torch's cast alone gives NaN above 448."""
+    return (x.float() / s).clamp(-KV_FP8_MAX, KV_FP8_MAX).to(torch.float8_e4m3fn)
+
+
+def kv_fp8_fake_quant(x, s):
+    return (kv_fp8_encode(x, s).float() * s).to(x.dtype)
+
+
+def _kv_mode(kv_dtype):
+    if kv_dtype is None or (isinstance(kv_dtype, str) and kv_dtype in ("auto", "fp8")):
+        return "fp8" if kv_dtype == "fp8" else None
+    raise ValueError(f"`kv_cache_dtype` (={kv_dtype!r}) has to be None, \"auto\" (the model's 16-bit dtype) or \"fp8\"")
+
+
+class KVCache:
+    """Minimal per-layer key/value store with the `update` signature the attention module expects.
+    kv_dtype="fp8": stores and returns fake-quantised values; a layer's scales are fixed by its first `update` (the prompt)."""
+
+    def __init__(self, kv_dtype=None):
         self.k, self.v = {}, {}
+        self.fp8 = _kv_mode(kv_dtype) == "fp8"
+        self.scale = {}                  # fp8: layer -> (2,) fp32, the K and the V scale
 
     def get_seq_length(self, layer_idx=0):
         return 0 if layer_idx not in self.k else self.k[layer_idx].shape[-2]
 
     def update(self, k, v, layer_idx, cache_kwargs=None):
+        if self.fp8:
+            if layer_idx not in self.scale:
+                self.scale[layer_idx] = torch.stack([kv_fp8_scale(k), kv_fp8_scale(v)])
+            sk, sv = self.scale[layer_idx]
+            k, v = kv_fp8_fake_quant(k, sk), kv_fp8_fake_quant(v, sv)
         if layer_idx in self.k:
             k = torch.cat([self.k[layer_idx], k], dim=-2)
             v = torch.cat([self.v[layer_idx], v], dim=-2)
@@ -65,9 +109,12 @@ class KVCache:
 
 class StaticKVCache:
     """Pre-allocated (rows, Hkv, max_len, D) buffers per layer, written in place at `cache_position` -- fixed
-    addresses and shapes, which is what lets one decode step be captured in a hipGraph and replayed."""
+    addresses and shapes, which is what lets one decode step be captured in a hipGraph and replayed.
+    kv_dtype="fp8": fake-quantised like `KVCache`; the scales are the prompt's (`load_prefix`), held in one (n_layers, 2) tensor."""
 
-    def __init__(self, n_layers, rows, kv_heads, max_len, head_dim, dtype, device):
+    def __init__(self, n_layers, rows, kv_heads, max_len, head_dim, dtype, device, kv_dtype=None):
+        self.fp8 = _kv_mode(kv_dtype) == "fp8"
+        self.scale = torch.ones(n_layers, 2, dtype=torch.float32, device=device) if self.fp8 else None
         self.k = [torch.zeros(rows, kv_heads, max_len, head_dim, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(rows, kv_heads, max_len, head_dim, dtype=dtype, device=device) for _ in range(n_layers)]
         self.filled = 0
@@ -80,10 +127,14 @@ class StaticKVCache:
             n = dyn.k[i].shape[-2]
             self.k[i][:, :, :n] = dyn.k[i].repeat_interleave(repeat, dim=0)
             self.v[i][:, :, :n] = dyn.v[i].repeat_interleave(repeat, dim=0)
+        if self.fp8:
+            self.scale.copy_(torch.stack([dyn.scale[i] for i in range(len(self.k))]))
         self.filled = dyn.get_seq_length()
 
     def update(self, k, v, layer_idx, cache_kwargs=None):
         pos = cache_kwargs["cache_position"]
+        if self.fp8:
+            k, v = kv_fp8_fake_quant(k, self.scale[layer_idx, 0]), kv_fp8_fake_quant(v, self.scale[layer_idx, 1])
         self.k[layer_idx].index_copy_(2, pos, k)
         self.v[layer_idx].index_copy_(2, pos, v)
         return self.k[layer_idx], self.v[layer_idx]
@@ -134,14 +185,14 @@ class _GraphStepper(_Stepper):
     """One decode step (beam re-order of the cache + one-token forward) captured ONCE in a hipGraph and replayed per
     token: a 32-layer decoder is ~1400 kernel launches per token in eager mode -- launch-bound at batch 1-3."""
 
-    def __init__(self, model: "ReportDecoder", rows, prompt_mask, dyn_cache, max_new, dtype):
+    def __init__(self, model: "ReportDecoder", rows, prompt_mask, dyn_cache, max_new, dtype, kv_dtype=None):
         dev = prompt_mask.device
         cfg = model.config
         self.model = model
         self.P = prompt_mask.shape[1]
         self.max_len = self.P + max_new
         self.cache = StaticKVCache(cfg.num_hidden_layers, rows, cfg.num_key_value_heads, self.max_len,
-                                   cfg.hidden_size // cfg.num_attention_heads, dtype, dev)
+                                   cfg.hidden_size // cfg.num_attention_heads, dtype, dev, kv_dtype)
         self.mask = torch.zeros(rows, self.max_len, dtype=torch.long, device=dev)
         self.n_real = torch.zeros(rows, 1, dtype=torch.long, device=dev)
         self.tok = torch.zeros(rows, dtype=torch.long, device=dev)
@@ -546,11 +597,13 @@ class _KernelStepper(_Stepper):
                      for i in _KernelStepper._cond_layers(model))
 
     @staticmethod
-    def supported(model, rows, dtype, device):
+    def supported(model, rows, dtype, device, kv_dtype=None):
         if torch.device(device).type == "cuda":
             _abi.load()          # a missing libmxvl.so is an error on a GPU box, never a silent torch path
         cfg = model.config
         D = cfg.hidden_size // cfg.num_attention_heads
+        if _kv_mode(kv_dtype) == "fp8" and D == 256:
+            return False         # the fp8-cache attention kernels (MXVL_KV_FP8) are built for head_dim 64 and 128
         for i in _KernelStepper._cond_layers(model):
             lay = model.model.layers[i]
             at = lay.self_attn
@@ -575,10 +628,11 @@ class _KernelStepper(_Stepper):
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
 
-    def __init__(self, model, rows, prompt_mask, dyn_cache, max_new, dtype):
+    def __init__(self, model, rows, prompt_mask, dyn_cache, max_new, dtype, kv_dtype=None):
         dev = prompt_mask.device
         cfg = model.config
         self.model, self.rows = model, rows
+        self.kv8 = _kv_mode(kv_dtype) == "fp8"
         self.H, self.Hkv = cfg.num_attention_heads, cfg.num_key_value_heads
         self.D = cfg.hidden_size // self.H
         self.hidden, self.inter, self.V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
@@ -590,8 +644,11 @@ class _KernelStepper(_Stepper):
         self.dt = _abi.dtype_code(dtype)
         bf = dict(dtype=dtype, device=dev)
         L = cfg.num_hidden_layers
-        self.kc = [torch.zeros(rows, self.Hkv, self.max_len, self.D, **bf) for _ in range(L)]
-        self.vc = [torch.zeros(rows, self.Hkv, self.max_len, self.D, **bf) for _ in range(L)]
+        # kv_cache_dtype="fp8": one byte per element (E4M3 codes, code 0 = 0.0) and the layers' (K, V) scales, refilled by reset()
+        cbf = dict(dtype=torch.uint8, device=dev) if self.kv8 else bf
+        self.kc = [torch.zeros(rows, self.Hkv, self.max_len, self.D, **cbf) for _ in range(L)]
+        self.vc = [torch.zeros(rows, self.Hkv, self.max_len, self.D, **cbf) for _ in range(L)]
+        self.kv_scale = torch.ones(L, 2, dtype=torch.float32, device=dev) if self.kv8 else None
         self.x = torch.zeros(rows, self.hidden, **bf)
         self.x2 = torch.zeros(rows, self.hidden, **bf)
         # rows > 8 need the matrix-core projections; below that they are still ~3 % faster per token than the GEMV kernels wherever
@@ -650,10 +707,18 @@ class _KernelStepper(_Stepper):
 
     def reset(self, prompt_mask, dyn_cache):
         rep = self.rows // prompt_mask.shape[0]
+        if self.kv8:
+            if not getattr(dyn_cache, "fp8", False):
+                raise RuntimeError("an fp8 KV cache continues a prompt cache built with kv_dtype=\"fp8\" (its values are on the grid already)")
+            self.kv_scale.copy_(torch.stack([dyn_cache.scale[i] for i in range(len(self.kc))]))
         for i in range(len(self.kc)):
             n = dyn_cache.k[i].shape[-2]
-            self.kc[i][:, :, :n] = dyn_cache.k[i].repeat_interleave(rep, dim=0)
-            self.vc[i][:, :, :n] = dyn_cache.v[i].repeat_interleave(rep, dim=0)
+            k, v = dyn_cache.k[i], dyn_cache.v[i]
+            if self.kv8:             # on-grid values back to their codes: exact
+                k = kv_fp8_encode(k, self.kv_scale[i, 0]).view(torch.uint8)
+                v = kv_fp8_encode(v, self.kv_scale[i, 1]).view(torch.uint8)
+            self.kc[i][:, :, :n] = k.repeat_interleave(rep, dim=0)
+            self.vc[i][:, :, :n] = v.repeat_interleave(rep, dim=0)
         self._load_prompt_mask(prompt_mask)
         self.slot.copy_(self.own.expand(-1, self.max_len))
         # the beams of a sample continue the SAME prompt: their prompt positions name one physical copy (the sample's first row), so
@@ -776,7 +841,7 @@ class _KernelStepper(_Stepper):
         self._prologue(tok, beam, cur)
         a = _abi.DecodeAttnDesc()
         a.rows, a.n_heads, a.n_kv_heads, a.head_dim, a.max_len = self.rows, self.H, self.Hkv, self.D, self.max_len
-        a.scale, a.dtype = self.D ** -0.5, self.dt
+        a.scale, a.dtype = self.D ** -0.5, self.dt | (_abi.MXVL_KV_FP8 if self.kv8 else 0)
         # the beams of a sample share a workgroup (and the cache lines they have in common) once head x sample workgroups fill the
         # chip; below that a workgroup per (head, row) keeps more requests in flight (batch 1 x beam 3: 9 vs 15 us per layer)
         a.beams = self.beams if (2 <= self.beams <= 5 and self.H * (self.rows // self.beams) >= 128 and self._beams_attn_fits()) else 0
@@ -795,6 +860,7 @@ class _KernelStepper(_Stepper):
                 self._gemv(self.x, at.qkv_weight, self.qkv, self.hidden, self.qkv.shape[1], norm=ln1.weight, eps=ln1.variance_epsilon,
                            bias=at.qkv_bias)
             a.k_cache, a.v_cache = self.kc[i].data_ptr(), self.vc[i].data_ptr()
+            a.kv_scale = self.kv_scale[i].data_ptr() if self.kv8 else None
             a.q_rope = self.q_rope.data_ptr() if i in self.cond else None
             _abi.launch("mxvl_decode_attn", a, device=self.x.device)
             att = self.att
@@ -1147,7 +1213,9 @@ class ReportDecoder(nn.Module):
 
     def _generate(self, inputs_embeds, attention_mask=None, num_beams=1, do_sample=False, min_new_tokens=0,
                   max_new_tokens=20, repetition_penalty=1.0, length_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                  early_stopping=False, temperature=None, use_graph=None, top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=0):
+                  early_stopping=False, temperature=None, use_graph=None, top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=0,
+                  kv_cache_dtype=None):
+        kv_dtype = _kv_mode(kv_cache_dtype)          # None / "auto": the model's dtype; "fp8": E4M3.  Checked before anything is enqueued
         # HF: a strictly positive integer or unset; 0 (the default here) switches the processor off.  Checked before anything is enqueued
         if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or no_repeat_ngram_size < 0:
             raise ValueError(f"`no_repeat_ngram_size` (={no_repeat_ngram_size}) has to be a non-negative integer (0 = off)")
@@ -1182,7 +1250,7 @@ class ReportDecoder(nn.Module):
             from .pretrain_engine import enable_tuned_gemms
             ReportDecoder._tuned_gemms_checked = True
             enable_tuned_gemms()
-        cache = KVCache()
+        cache = KVCache(kv_dtype)
         logits = self.forward(inputs_embeds, attention_mask=attention_mask, past_key_values=cache)[:, -1]   # (B, V)
         if use_graph is None:
             use_graph = inputs_embeds.is_cuda
@@ -1200,21 +1268,22 @@ class ReportDecoder(nn.Module):
                 self.__dict__["_steppers"] = {}
                 self.__dict__["_stepper_weights"] = ident
             key = (B * nb, nb, attention_mask.shape[1], max_new_tokens, inputs_embeds.dtype, str(dev), str(use_graph), conditioned,
-                   _KernelStepper.cond_signature(self))
+                   _KernelStepper.cond_signature(self), kv_dtype)
             stepper = getattr(self, "_steppers", {}).get(key)
             if stepper is None:
                 cls = _GraphStepper
                 if use_graph != "torch":
                     # ONE decode path on a HIP device: the kernels, or an error naming what they cannot serve -- the torch-module
                     # stepper is an explicit request (use_graph="torch": CPU-parity experiments), never a silent substitute
-                    if not _KernelStepper.supported(self, B * nb, inputs_embeds.dtype, dev):
+                    if not _KernelStepper.supported(self, B * nb, inputs_embeds.dtype, dev, kv_dtype):
                         raise RuntimeError(
-                            f"report decoding on {dev}: the HIP decode kernels serve bf16 / fp16 models with head_dim 64/128/256 and "
+                            f"report decoding on {dev}: the HIP decode kernels serve bf16 / fp16 models with head_dim 64/128/256 "
+                            f"(64/128 with kv_cache_dtype=\"fp8\") and "
                             f"batch * beams <= 80 (got rows={B * nb}, dtype={inputs_embeds.dtype}, head_dim="
-                            f"{self.config.hidden_size // self.config.num_attention_heads}); pass use_graph=\"torch\" for the "
+                            f"{self.config.hidden_size // self.config.num_attention_heads}, kv_cache_dtype={kv_cache_dtype!r}); pass use_graph=\"torch\" for the "
                             f"torch-module stepper or use_graph=False for the eager loop")
                     cls = _KernelStepper
-                stepper = cls(self, B * nb, attention_mask, cache, max_new_tokens, inputs_embeds.dtype)
+                stepper = cls(self, B * nb, attention_mask, cache, max_new_tokens, inputs_embeds.dtype, kv_dtype)
                 self.__dict__.setdefault("_steppers", {})[key] = stepper
             else:
                 stepper.reset(attention_mask, cache)
