@@ -225,13 +225,14 @@ struct AttnArgs {
   float scale;
   const uint16_t* qkv;       // (rows, (H + 2*Hkv) * D)
   const float *cosv, *sinv;  // (rows, D)
-  uint16_t *kc, *vc;         // (rows, Hkv, max_len, D)
+  uint16_t *kc, *vc;         // (rows, Hkv, max_len, D); bytes with the E4M3 cache (KV::cache_t, decode_elt.h)
   const int* slot;           // (rows, max_len)
   const int64_t* pos;        // device scalar
   const int64_t* mask;       // (rows, max_len), nonzero = attend
   uint16_t* out;             // (rows, H * D)
   uint16_t* q_rope;          // optional (rows, H * D): the rotated, UNscaled query (what the hybrid layers' image cross-attention reads)
   int ablate;                // measurement build only (MXVL_ATTN_ABLATE): the beams kernel returns after 1 the prologue, 3 the cached positions
+  const float* kvs;          // E4M3 cache: device {K scale, V scale} of this layer; null for the 16-bit cache
 };
 
 struct CrossAttnArgs {
@@ -247,12 +248,12 @@ struct CrossAttnArgs {
 };
 
 // measurement build only (python -m medical_image_analysis_amd.build --ablate; tools/decode_attn_probe.py): MXVL_ATTN_WAVES = 8 / 16
-// pins the workgroup size of the per-row kernel (beams kernel: 8 / 4 waves).  The product library reads no environment: always 0.
+// pins the workgroup size of the per-row kernel (16-bit cache only; beams kernels, either cache: 8 / 4 waves).  The product library reads no environment: always 0.
 static int attn_waves_env() {
   static const int v = MXVL_ABL_ENV("MXVL_ATTN_WAVES");
   return (v == 8 || v == 16) ? v : 0;
 }
-// Sum over the LPR lanes that share a cache row (LPR = head_dim / 8 consecutive lanes), result in every lane.  DPP moves inside a
+// Sum over the LPR lanes that share a cache row (LPR = head_dim / EPL consecutive lanes), result in every lane.  DPP moves inside a
 // 16-lane row -- quad_perm for the partners at distance 1 and 2, row_half_mirror / row_mirror for the other half of 8 / 16 (every
 // lane of a half already holds the same partial sum, so the mirrored partner is as good as the xor one and the additions are the
 // same additions: bit-identical to the __shfl_xor butterfly) -- instead of ds_bpermute_b32: four DEPENDENT LDS-crossbar round trips
@@ -274,27 +275,34 @@ __device__ __forceinline__ float group_sum(float s) {
 constexpr int kAttnWaves = 8;    // (16 waves x 8 positions per group -- one trip of cache loads for a 358-position report instead of
                                  //  three -- measured slower: 9.7 vs 8.9 us per launch, profiles/r03_decode_timeline.txt)
 
-// One workgroup per (head, row).  A cached K or V line of D bf16 is read by LPR = D/8 lanes with one 16-byte load
-// each, so a wave covers 64/LPR positions per load and the workgroup 8 x 64/LPR; K and V of a position are loaded
-// together and folded into a running (max, sum, out[8]) per lane group (one-pass softmax), merged once at the end.
-template <typename E, int D, int NW, int DEPTH>
-__global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) {
-  constexpr int LPR = D / 8, RPW = 64 / LPR, NG = NW * RPW;
+// One workgroup per (head, row), for either cache format KV (decode_elt.h).  A cached K or V line of D elements is read by
+// LPR = D/EPL lanes with one 16-byte load each (EPL = 8 elements of 16 bits, 16 of the E4M3 cache), so a wave covers 64/LPR
+// positions per load and the workgroup NW x 64/LPR; K and V of a position are loaded together and folded into a running
+// (max, sum, out[EPL]) per lane group (one-pass softmax), merged once at the end.  decode_attn_kernel / decode_attn_kv8_kernel
+// are this body over Kv16 / KvE4m3 (p by value: taken by reference, every instantiation compiled ten instructions longer).
+template <typename E, typename KV, int D, int NW, int DEPTH>
+__device__ __forceinline__ void decode_attn_body(const AttnArgs p) {
+  typedef typename KV::cache_t cache_t;
+  constexpr int EPL = KV::EPL, LPR = D / EPL, RPW = 64 / LPR, NG = NW * RPW;
   static_assert((DEPTH & (DEPTH - 1)) == 0, "ring slots are picked with a mask");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int T = p.max_len;
   char* ring_all = (char*)sm;     // [NW][DEPTH][K 1 KB | V 1 KB]: landing ring of the cache rows (see the loop)
-  float* sq = sm + NW * DEPTH * 512;   // [D] rotated query
-  float* sk = sq + D;             // [D] rotated new key
-  float* sv = sk + D;             // [D] new value
+  float* sq = sm + NW * DEPTH * 512;   // [D] rotated query x softmax scale (x K scale)
+  float* sk = sq + D;             // [D] rotated new key, as the value of its cache bits
+  float* sv = sk + D;             // [D] new value, as the value of its cache bits
   float* gm = sv + D;             // [NG] group maxima
   float* gl = gm + NG;            // [NG] group sums
   float* go = gl + NG;            // [NG][D] group outputs
   int* ssl = (int*)(go + NG * D); // [T] slot of each position, -1 = masked
+  cache_t* const kc = (cache_t*)p.kc;
+  cache_t* const vc = (cache_t*)p.vc;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = blockIdx.x, m = blockIdx.y;
   const int group = p.H / p.Hkv, hk = h / group;
   const int pos = (int)*p.pos;
+  float sK = 1.0f, sV = 1.0f;
+  if constexpr (KV::scaled) { sK = p.kvs[0]; sV = p.kvs[1]; }
   const size_t row = (size_t)m * (p.H + 2 * p.Hkv) * D;
   const uint16_t* q = p.qkv + row + (size_t)h * D;
   const uint16_t* kn = p.qkv + row + (size_t)(p.H + hk) * D;
@@ -326,35 +334,40 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) 
     const float kd = E::f(rk), ko = d < half ? -E::f(rko) : E::f(rko);
     const float qr = E::rr(E::rr(qd * c) + E::rr(qo * s));
     const float kr = E::rr(E::rr(kd * c) + E::rr(ko * s));
-    sq[d] = qr * p.scale;
+    if constexpr (KV::scaled) sq[d] = qr * p.scale * sK;   // the K scale rides on the query
+    else sq[d] = qr * p.scale;
     if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
-    sk[d] = kr;
-    sv[d] = E::f(rv);
+    // the new K / V as cache bits, and as the values those bits stand for: a position is seen as the cache holds it from this step on
+    float kval, vval;
+    const uint32_t ck = KV::encode(kr, pow2_recip(sK), kval);
+    sk[d] = kval;
+    const uint32_t cv = KV::encode(E::f(rv), pow2_recip(sV), vval);
+    sv[d] = vval;
     if (h % group == 0) {  // one head of the group appends to the cache (slot m owns position pos of beam m)
       const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
-      p.kc[o] = E::r(kr);
-      p.vc[o] = rv;
+      kc[o] = (cache_t)ck;
+      vc[o] = (cache_t)cv;
     }
   }
   __syncthreads();
   const int sub = lane % LPR, g = wave * RPW + lane / LPR;
-  float qv[8];
+  float qv[EPL];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) qv[j] = sq[sub * 8 + j];
-  float mx = -1e30f, l = 0.0f, o[8];
+  for (int j = 0; j < EPL; ++j) qv[j] = sq[sub * EPL + j];
+  float mx = -1e30f, l = 0.0f, o[EPL];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = 0.0f;
+  for (int j = 0; j < EPL; ++j) o[j] = 0.0f;
   auto fold = [&](bool live, const float* kf, const float* vf) {
     float s = 0.0f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s = fmaf(qv[j], kf[j], s);
+    for (int j = 0; j < EPL; ++j) s = fmaf(qv[j], kf[j], s);
     s = group_sum<LPR>(s);
     const float mn = live ? fmaxf(mx, s) : mx;
     const float corr = fast_exp(mx - mn), pr = live ? fast_exp(s - mn) : 0.0f;
     mx = mn;
     l = fmaf(l, corr, pr);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = fmaf(o[j], corr, pr * vf[j]);
+    for (int j = 0; j < EPL; ++j) o[j] = fmaf(o[j], corr, pr * vf[j]);
   };
   // The cache rows land in LDS, not in registers: a wave owns a ring of DEPTH trips; a trip = one global_load_lds_dwordx4 of K and
   // one of V, each lane moving the 16 bytes IT reads back (LDS address = lane * 16: no swizzle, no cross-lane traffic, no barrier)
@@ -365,7 +378,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) 
   const int ntrips = (pos + NG - 1) / NG;
   char* ring = ring_all + wave * (DEPTH * 2048);
   const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
-  const size_t c1 = (size_t)p.Hkv * T * D, lane_off = (size_t)hk * T * D + sub * 8;
+  const size_t c1 = (size_t)p.Hkv * T * D, lane_off = (size_t)hk * T * D + sub * EPL;   // cache elements
   uint32_t livebits = 0;                 // bit (j & 31): trip j of this lane group carries an attended position
   int iss = 0;
   auto issue = [&]() {
@@ -380,7 +393,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) 
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
                  "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(dst), "v"(p.kc + off), "v"(p.vc + off) : "memory", "scc");
+                 : "=&s"(keep) : "s"(dst), "v"(kc + off), "v"(vc + off) : "memory", "scc");
     ++iss;
   };
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the counts below are counts of ring trips only
@@ -394,20 +407,20 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) 
     const bool live = (livebits >> (j & 31)) & 1u;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // both rows are in registers: the slot may be refilled
     issue();
-    float kf[8], vf[8];
-    elt_unpack8<E>(kq, kf);
-    elt_unpack8<E>(vq, vf);
+    float kf[EPL], vf[EPL];
+    KV::unpack(kq, kf);
+    KV::unpack(vq, vf);
     fold(live, kf, vf);
   }
   if (g == 0) {  // the fresh position (always attended: its mask bit was just set)
-    float kf[8], vf[8];
+    float kf[EPL], vf[EPL];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { kf[j] = sk[sub * 8 + j]; vf[j] = sv[sub * 8 + j]; }
+    for (int j = 0; j < EPL; ++j) { kf[j] = sk[sub * EPL + j]; vf[j] = sv[sub * EPL + j]; }
     fold(ssl[pos] >= 0, kf, vf);
   }
   if (sub == 0) { gm[g] = mx; gl[g] = l; }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) go[g * D + sub * 8 + j] = o[j];
+  for (int j = 0; j < EPL; ++j) go[g * D + sub * EPL + j] = o[j];
   __syncthreads();
   if (tid < D) {
     float gmax = -1e30f;
@@ -418,9 +431,14 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) 
       num = fmaf(w, go[i * D + tid], num);
       den = fmaf(w, gl[i], den);
     }
-    p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den);
+    if constexpr (KV::scaled) p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den * sV);   // the V scale rides on the output
+    else p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den);
   }
 }
+template <typename E, int D, int NW, int DEPTH>
+__global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) { decode_attn_body<E, Kv16<E>, D, NW, DEPTH>(p); }
+template <typename E, int D, int NW, int DEPTH>
+__global__ __launch_bounds__(NW * 64) void decode_attn_kv8_kernel(const AttnArgs p) { decode_attn_body<E, KvE4m3<E>, D, NW, DEPTH>(p); }
 
 // The same step for the nb beams of ONE sample in one workgroup (grid: head x sample).  Beams continue a common ancestor: the prompt
 // (whose slots the stepper points at one physical copy) and usually the first generated tokens name the SAME cache lines for every
@@ -712,161 +730,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
   }
 }
 
-// ---- MXVL_KV_FP8 (include/mxvl.h): the two kernels above over a cache of OCP E4M3 codes, one power-of-two scale per tensor ---------
-// Same structure as their 16-bit twins -- RoPE of the new q / k, append at *pos, slot-table indirection, mask, one-pass softmax, the
-// fresh position as its own partial -- over cache rows of D BYTES.  The new K / V are encoded first (code = rne_e4m3(clamp(x / s)))
-// and enter this step's attention as code * s, like every cached position: a position is seen quantised from the step that writes
-// it.  The scales never touch an element: the K scale rides on the (already scaled) query, the V scale on the final output -- both
-// exact, they are powers of two -- so what is summed are plain code values.
-struct AttnArgsKv8 {
-  AttnArgs a;          // kc / vc hold bytes (rows, Hkv, max_len, D)
-  const float* kvs;    // device: {K scale, V scale} of this layer
-};
-
-// One workgroup per (head, row).  LDS-DMA moves 16 bytes per lane, so a lane owns 16 elements of a cache row and LPR = D/16 lanes
-// (4 or 8) share it: a wave covers 64/LPR positions per trip, twice decode_attn_kernel's, with the same ring ([K 1 KB | V 1 KB] per
-// trip, each lane reading back the 16 bytes it moved) and the same wait counts.
-template <typename E, int D, int NW, int DEPTH>
-__global__ __launch_bounds__(NW * 64) void decode_attn_kv8_kernel(const AttnArgsKv8 pa) {
-  const AttnArgs& p = pa.a;
-  constexpr int LPR = D / 16, RPW = 64 / LPR, NG = NW * RPW;
-  static_assert((DEPTH & (DEPTH - 1)) == 0, "ring slots are picked with a mask");
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = p.max_len;
-  char* ring_all = (char*)sm;     // [NW][DEPTH][K 1 KB | V 1 KB]
-  float* sq = sm + NW * DEPTH * 512;   // [D] rotated query x softmax scale x K scale
-  float* sk = sq + D;             // [D] rotated new key, as the value of its code
-  float* sv = sk + D;             // [D] new value, as the value of its code
-  float* gm = sv + D;             // [NG] group maxima
-  float* gl = gm + NG;            // [NG] group sums
-  float* go = gl + NG;            // [NG][D] group outputs
-  int* ssl = (int*)(go + NG * D); // [T] slot of each position, -1 = masked
-  uint8_t* const kc8 = (uint8_t*)p.kc;
-  uint8_t* const vc8 = (uint8_t*)p.vc;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = blockIdx.x, m = blockIdx.y;
-  const int group = p.H / p.Hkv, hk = h / group;
-  const int pos = (int)*p.pos;
-  const float sK = pa.kvs[0], sV = pa.kvs[1];
-  const size_t row = (size_t)m * (p.H + 2 * p.Hkv) * D;
-  const uint16_t* q = p.qkv + row + (size_t)h * D;
-  const uint16_t* kn = p.qkv + row + (size_t)(p.H + hk) * D;
-  const uint16_t* vn = p.qkv + row + (size_t)(p.H + p.Hkv + hk) * D;
-  // (the prologue's loads all go out before anything is used: see decode_attn_kernel)
-  {
-    const int t = tid < T ? tid : T - 1;
-    const int64_t mk = p.mask[(size_t)m * T + t];
-    const int sl = p.slot[(size_t)m * T + t];
-    __builtin_amdgcn_sched_barrier(0);
-    ssl[t] = mk != 0 ? sl : -1;
-  }
-  for (int t = tid + NW * 64; t <= pos; t += NW * 64) {
-    const int64_t mk = p.mask[(size_t)m * T + t];
-    const int sl = p.slot[(size_t)m * T + t];
-    ssl[t] = mk != 0 ? sl : -1;
-  }
-  if (tid < D) {
-    const int d = tid, half = D / 2;
-    const int dp = d < half ? d + half : d - half;
-    const uint16_t rq = q[d], rqo = q[dp], rk = kn[d], rko = kn[dp], rv = vn[d];
-    const float rc = p.cosv[(size_t)m * D + d], rs = p.sinv[(size_t)m * D + d];
-    const float c = E::rr(rc), s = E::rr(rs);
-    const float qd = E::f(rq), qo = d < half ? -E::f(rqo) : E::f(rqo);
-    const float kd = E::f(rk), ko = d < half ? -E::f(rko) : E::f(rko);
-    const float qr = E::rr(E::rr(qd * c) + E::rr(qo * s));
-    const float kr = E::rr(E::rr(kd * c) + E::rr(ko * s));
-    const uint32_t ck = e4m3_encode(kr * pow2_recip(sK)), cv = e4m3_encode(E::f(rv) * pow2_recip(sV));
-    sq[d] = qr * p.scale * sK;
-    if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
-    sk[d] = e4m3_decode(ck);
-    sv[d] = e4m3_decode(cv);
-    if (h % group == 0) {  // one head of the group appends to the cache (slot m owns position pos of beam m)
-      const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
-      kc8[o] = (uint8_t)ck;
-      vc8[o] = (uint8_t)cv;
-    }
-  }
-  __syncthreads();
-  const int sub = lane % LPR, g = wave * RPW + lane / LPR;
-  float qv[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) qv[j] = sq[sub * 16 + j];
-  float mx = -1e30f, l = 0.0f, o[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) o[j] = 0.0f;
-  auto fold = [&](bool live, const float* kf, const float* vf) {
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s = fmaf(qv[j], kf[j], s);
-    s = group_sum<LPR>(s);
-    const float mn = live ? fmaxf(mx, s) : mx;
-    const float corr = fast_exp(mx - mn), pr = live ? fast_exp(s - mn) : 0.0f;
-    mx = mn;
-    l = fmaf(l, corr, pr);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) o[j] = fmaf(o[j], corr, pr * vf[j]);
-  };
-  const int ntrips = (pos + NG - 1) / NG;
-  char* ring = ring_all + wave * (DEPTH * 2048);
-  const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
-  const size_t c1 = (size_t)p.Hkv * T * D, lane_off = (size_t)hk * T * D + sub * 16;   // bytes
-  uint32_t livebits = 0;                 // bit (j & 31): trip j of this lane group carries an attended position
-  int iss = 0;
-  auto issue = [&]() {
-    if (iss >= ntrips) return;
-    const int t = g + iss * NG;
-    const int sl = ssl[t < pos ? t : 0];
-    const bool live = t < pos && sl >= 0;    // a masked / out-of-range group re-reads the row's first cache line
-    const size_t off = (live ? (size_t)sl * c1 + (size_t)t * D : (size_t)m * c1) + lane_off;
-    const int bit = iss & 31;
-    livebits = (livebits & ~(1u << bit)) | ((uint32_t)live << bit);
-    const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(iss & (DEPTH - 1)) * 2048u);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(dst), "v"(kc8 + off), "v"(vc8 + off) : "memory", "scc");
-    ++iss;
-  };
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the counts below are counts of ring trips only
-#pragma unroll
-  for (int j = 0; j < DEPTH; ++j) issue();
-  for (int j = 0; j < ntrips; ++j) {                       // cached positions 0 .. pos-1
-    if (j + DEPTH <= ntrips) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (DEPTH - 1)) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const char* slot = ring + (j & (DEPTH - 1)) * 2048 + lane * 16;
-    const uint4 kq = *(const uint4*)slot, vq = *(const uint4*)(slot + 1024);
-    const bool live = (livebits >> (j & 31)) & 1u;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // both rows are in registers: the slot may be refilled
-    issue();
-    float kf[16], vf[16];
-    e4m3_unpack4(kq.x, kf); e4m3_unpack4(kq.y, kf + 4); e4m3_unpack4(kq.z, kf + 8); e4m3_unpack4(kq.w, kf + 12);
-    e4m3_unpack4(vq.x, vf); e4m3_unpack4(vq.y, vf + 4); e4m3_unpack4(vq.z, vf + 8); e4m3_unpack4(vq.w, vf + 12);
-    fold(live, kf, vf);
-  }
-  if (g == 0) {  // the fresh position (always attended: its mask bit was just set), as its codes' values
-    float kf[16], vf[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { kf[j] = sk[sub * 16 + j]; vf[j] = sv[sub * 16 + j]; }
-    fold(ssl[pos] >= 0, kf, vf);
-  }
-  if (sub == 0) { gm[g] = mx; gl[g] = l; }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) go[g * D + sub * 16 + j] = o[j];
-  __syncthreads();
-  if (tid < D) {
-    float gmax = -1e30f;
-    for (int i = 0; i < NG; ++i) gmax = fmaxf(gmax, gm[i]);
-    float num = 0.0f, den = 0.0f;
-    for (int i = 0; i < NG; ++i) {
-      const float w = fast_exp(gm[i] - gmax);
-      num = fmaf(w, go[i * D + tid], num);
-      den = fmaf(w, gl[i], den);
-    }
-    p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den * sV);
-  }
-}
-
-// The beams of one sample in one workgroup (grid: head x sample), as decode_attn_beams_mfma_kernel: shared positions read once, both
+// decode_attn_beams_mfma_kernel over the E4M3 cache (bytes, one power-of-two scale per tensor: KvE4m3 in decode_elt.h): shared positions read once, both
 // products on the 16-bit matrix cores (16x16x32 for K Q^T, 16x16x16 for V^T P), P rounded to 16 bits.  A tile is 16 positions x D
 // bytes -- half the DMA instructions and half the LDS of the twin -- and a fragment becomes 16-bit elements AFTER its LDS read (a
 // code's value is exact in bf16 and fp16, so the MFMA operands are plain code values; the scales enter as in the per-row kernel).
@@ -879,8 +743,7 @@ template <int D> __device__ __forceinline__ int attn_tile8_key(int row) { return
 template <int D> __device__ __forceinline__ int attn_tile8_off(int row, int unit) { return row * D + ((unit ^ attn_tile8_key<D>(row)) << 4); }
 
 template <typename E, int D, int NB, int NW>
-__global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const AttnArgsKv8 pa) {
-  const AttnArgs& p = pa.a;
+__global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const AttnArgs p) {
   typedef short s16x4 __attribute__((ext_vector_type(4)));
   typedef elt_u32x4 bf16x8;      // eight 16-bit elements of a lane (E decides what they mean)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -908,7 +771,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
   const int h = blockIdx.x, m0 = blockIdx.y * NB;
   const int group = p.H / p.Hkv, hk = h / group;
   const int pos = (int)*p.pos;
-  const float sK = pa.kvs[0], sV = pa.kvs[1];
+  const float sK = p.kvs[0], sV = p.kvs[1];
   constexpr int RI = (NB * D + NT - 1) / NT;
   uint16_t rope_q[RI], rope_qo[RI], rope_k[RI], rope_ko[RI], rope_v[RI];
   float rope_c[RI], rope_s[RI];
@@ -988,6 +851,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
     }
   }
   __syncthreads();
+  if (MXVL_ABL(p.ablate == 1)) return;      // launch + slot sweep + RoPE + cache append
   const int nsh = s_nsh;
   const int l16 = lane & 15, q4 = lane >> 4;
   const int ns = (nsh + TILE - 1) / TILE, nt = (pos - nsh + TILE - 1) / TILE, ntiles = ns + NB * nt;
@@ -1104,6 +968,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
       oacc[dt] = E::mfma16(vf, pb, oacc[dt]);
     }
   }
+  if (MXVL_ABL(p.ablate == 3)) return;      // + every cached position
   // ---- merge: the q-lanes of a column by shuffles, the waves (+ the fresh position as partial NW) through LDS ----------------------
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
@@ -1320,14 +1185,38 @@ static int launch_gemv_rows(const GemvArgs& a, hipStream_t s) {
   }
 }
 
-template <typename E>
+// the __global__ wrapper of a kernel body for the cache format KV
+template <typename E, typename KV, int D, int NW, int DEPTH>
+static constexpr auto attn_row_kernel() {
+  if constexpr (KV::scaled) return &decode_attn_kv8_kernel<E, D, NW, DEPTH>;
+  else return &decode_attn_kernel<E, D, NW, DEPTH>;
+}
+template <typename E, typename KV, int D, int NB, int NW>
+static constexpr auto attn_beams_kernel() {
+  if constexpr (KV::scaled) return &decode_attn_beams_kv8_kernel<E, D, NB, NW>;
+  else return &decode_attn_beams_mfma_kernel<E, D, NB, NW>;
+}
+
+// per call: the dynamic-LDS attribute belongs to the (kernel, device) pair, and a process may drive several devices
+static int launch_attn(void (*kern)(const AttnArgs), dim3 grid, dim3 block, size_t lds, hipStream_t s, const AttnArgs& a) {
+  if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
+    return MXVL_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+  return launch_status();
+}
+
+// KV = Kv16<E> or KvE4m3<E>.  head_dim 256 is instantiated for the 16-bit cache only (mxvl_decode_attn refuses it for the E4M3 cache).
+template <typename E, typename KV>
 static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
+  constexpr bool kv16 = !KV::scaled;
+  constexpr size_t EB = sizeof(typename KV::cache_t);    // bytes per cache element
+  if (!kv16 && a.D == 256) return MXVL_ERR_UNSUPPORTED;
   if (beams > 1) {       // the beams of a sample share a workgroup (and every cache line they have in common)
     if (beams > 5 || a.rows % beams != 0) return MXVL_ERR_UNSUPPORTED;
     if ((uint64_t)a.rows * a.Hkv * a.max_len * a.D >= (1ull << 31)) return MXVL_ERR_UNSUPPORTED;   // 32-bit cache offsets
     const int nb = beams;
     // matrix-core kernel: 8 waves (4 when head_dim 256 or a long slot table would not leave room for the ring)
-    const size_t stage = (size_t)2 * 16 * a.D * 2;
+    const size_t stage = (size_t)2 * 16 * a.D * EB;
     auto lds_of = [&](int nw) {
       return (size_t)nw * 2 * stage + (size_t)16 * a.D * 2 + sizeof(float) * ((size_t)3 * nb * a.D + 2 * nb * (nw + 1) + (size_t)nb * a.max_len);
     };
@@ -1337,31 +1226,27 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
     const size_t lds = lds_of(nw);
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
     const dim3 grid(a.H, a.rows / nb), block(nw * 64);
-#define MXVL_ATTN_BEAMS(DD, NB)                                                                                                    \
-  do {                                                                                                                             \
-    void (*kern)(const AttnArgs) = nw == 8 ? decode_attn_beams_mfma_kernel<E, DD, NB, (DD <= 128 ? 8 : 4)> : decode_attn_beams_mfma_kernel<E, DD, NB, 4>; \
-    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
-      return MXVL_ERR_LAUNCH;                                                                                                      \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);                                                                              \
-  } while (0)
-#define MXVL_ATTN_BEAMS_D(NB)                                                                                                      \
-  switch (a.D) {                                                                                                                   \
-    case 64: MXVL_ATTN_BEAMS(64, NB); break;                                                                                       \
-    case 128: MXVL_ATTN_BEAMS(128, NB); break;                                                                                     \
-    default: MXVL_ATTN_BEAMS(256, NB); break;                                                                                      \
-  }
+#define MXVL_ATTN_BEAMS(DD, NB) \
+  return launch_attn(nw == 8 ? attn_beams_kernel<E, KV, DD, NB, (DD <= 128 ? 8 : 4)>() : attn_beams_kernel<E, KV, DD, NB, 4>(), grid, block, lds, s, a)
+#define MXVL_ATTN_BEAMS_D(NB) \
+  switch (a.D) { \
+    case 64: MXVL_ATTN_BEAMS(64, NB); \
+    case 128: MXVL_ATTN_BEAMS(128, NB); \
+    default: if constexpr (kv16) MXVL_ATTN_BEAMS(256, NB); \
+  } \
+  break
     switch (nb) {
-      case 2: MXVL_ATTN_BEAMS_D(2); break;
-      case 3: MXVL_ATTN_BEAMS_D(3); break;
-      case 4: MXVL_ATTN_BEAMS_D(4); break;
-      default: MXVL_ATTN_BEAMS_D(5); break;
+      case 2: MXVL_ATTN_BEAMS_D(2);
+      case 3: MXVL_ATTN_BEAMS_D(3);
+      case 4: MXVL_ATTN_BEAMS_D(4);
+      default: MXVL_ATTN_BEAMS_D(5);
     }
 #undef MXVL_ATTN_BEAMS_D
 #undef MXVL_ATTN_BEAMS
-    return launch_status();
+    return MXVL_ERR_UNSUPPORTED;
   }
-  const int nw = attn_waves_env() ? attn_waves_env() : kAttnWaves;
-  const int NG = nw * 64 / (a.D / 8);
+  const int nw = kv16 && attn_waves_env() ? attn_waves_env() : kAttnWaves;   // (the 16-wave probe shape exists for the 16-bit cache only)
+  const int NG = nw * 64 / (a.D / KV::EPL);
   // ring depth (measured, profiles/r04_attn_row_ring_probe*.txt): 4 trips in flight while one workgroup per CU is all the grid asks
   // for -- 8 buy nothing at 96 workgroups (the kernel's floor there is launch + three dependent round trips), 2 lose 0.4 us on a
   // 231-position report -- and 2 beyond, where several workgroups per CU hide each other's round trips (10 % at 18+ rows)
@@ -1373,82 +1258,17 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
   const dim3 grid(a.H, a.rows), block(nw * 64);
 #define MXVL_ATTN_ROW(DD) \
   do { \
-    void (*kern)(const AttnArgs) = nw == 16 ? (depth == 8 ? decode_attn_kernel<E, DD, 16, 4> : depth == 4 ? decode_attn_kernel<E, DD, 16, 4> : decode_attn_kernel<E, DD, 16, 2>) \
-                                            : (depth == 8 ? decode_attn_kernel<E, DD, 8, 8> : depth == 4 ? decode_attn_kernel<E, DD, 8, 4> : decode_attn_kernel<E, DD, 8, 2>); \
-    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
-      return MXVL_ERR_LAUNCH; \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a); \
+    void (*kern)(const AttnArgs) = depth == 4 ? attn_row_kernel<E, KV, DD, 8, 4>() : attn_row_kernel<E, KV, DD, 8, 2>(); \
+    if constexpr (kv16) if (nw == 16) kern = depth == 4 ? decode_attn_kernel<E, DD, 16, 4> : decode_attn_kernel<E, DD, 16, 2>; \
+    return launch_attn(kern, grid, block, lds, s, a); \
   } while (0)
   switch (a.D) {
-    case 64: MXVL_ATTN_ROW(64); break;
-    case 128: MXVL_ATTN_ROW(128); break;
-    case 256: MXVL_ATTN_ROW(256); break;
-    default: return MXVL_ERR_UNSUPPORTED;
+    case 64: MXVL_ATTN_ROW(64);
+    case 128: MXVL_ATTN_ROW(128);
+    case 256: if constexpr (kv16) MXVL_ATTN_ROW(256);
   }
 #undef MXVL_ATTN_ROW
-  return launch_status();
-}
-
-// MXVL_KV_FP8: the same two dispatch rules over the byte caches (head_dim 64 / 128; the caller refused 256)
-template <typename E>
-static int launch_decode_attn_kv8(const AttnArgsKv8& ka, int beams, hipStream_t s) {
-  const AttnArgs& a = ka.a;
-  if (beams > 1) {
-    if (beams > 5 || a.rows % beams != 0) return MXVL_ERR_UNSUPPORTED;
-    if ((uint64_t)a.rows * a.Hkv * a.max_len * a.D >= (1ull << 31)) return MXVL_ERR_UNSUPPORTED;   // 32-bit cache offsets
-    const int nb = beams;
-    const size_t stage = (size_t)2 * 16 * a.D;
-    auto lds_of = [&](int nw) {
-      return (size_t)nw * 2 * stage + (size_t)16 * a.D * 2 + sizeof(float) * ((size_t)3 * nb * a.D + 2 * nb * (nw + 1) + (size_t)nb * a.max_len);
-    };
-    const int nw = lds_of(8) > 160 * 1024 ? 4 : 8;
-    const size_t lds = lds_of(nw);
-    if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
-    const dim3 grid(a.H, a.rows / nb), block(nw * 64);
-#define MXVL_ATTN_BEAMS8(DD, NB)                                                                                                   \
-  do {                                                                                                                             \
-    void (*kern)(const AttnArgsKv8) = nw == 8 ? decode_attn_beams_kv8_kernel<E, DD, NB, 8> : decode_attn_beams_kv8_kernel<E, DD, NB, 4>; \
-    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
-      return MXVL_ERR_LAUNCH;                                                                                                      \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, ka);                                                                             \
-  } while (0)
-#define MXVL_ATTN_BEAMS8_D(NB)                                                                                                     \
-  switch (a.D) {                                                                                                                   \
-    case 64: MXVL_ATTN_BEAMS8(64, NB); break;                                                                                      \
-    default: MXVL_ATTN_BEAMS8(128, NB); break;                                                                                     \
-  }
-    switch (nb) {
-      case 2: MXVL_ATTN_BEAMS8_D(2); break;
-      case 3: MXVL_ATTN_BEAMS8_D(3); break;
-      case 4: MXVL_ATTN_BEAMS8_D(4); break;
-      default: MXVL_ATTN_BEAMS8_D(5); break;
-    }
-#undef MXVL_ATTN_BEAMS8_D
-#undef MXVL_ATTN_BEAMS8
-    return launch_status();
-  }
-  constexpr int nw = kAttnWaves;
-  const int NG = nw * 64 / (a.D / 16);
-  const size_t lds0 = sizeof(float) * ((size_t)3 * a.D + 2 * NG + (size_t)NG * a.D + a.max_len);
-  int depth = (size_t)a.H * a.rows <= 256 ? 4 : 2;     // (the 16-bit kernel's rule)
-  while (depth > 2 && lds0 + (size_t)nw * depth * 2048 > 160 * 1024) depth /= 2;
-  const size_t lds = lds0 + (size_t)nw * depth * 2048;
-  if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
-  const dim3 grid(a.H, a.rows), block(nw * 64);
-#define MXVL_ATTN_ROW8(DD) \
-  do { \
-    void (*kern)(const AttnArgsKv8) = depth == 4 ? decode_attn_kv8_kernel<E, DD, nw, 4> : decode_attn_kv8_kernel<E, DD, nw, 2>; \
-    if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK) \
-      return MXVL_ERR_LAUNCH; \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, ka); \
-  } while (0)
-  switch (a.D) {
-    case 64: MXVL_ATTN_ROW8(64); break;
-    case 128: MXVL_ATTN_ROW8(128); break;
-    default: return MXVL_ERR_UNSUPPORTED;
-  }
-#undef MXVL_ATTN_ROW8
-  return launch_status();
+  return MXVL_ERR_UNSUPPORTED;
 }
 
 template <typename E>
@@ -1518,14 +1338,11 @@ int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
   a.pos = (const int64_t*)d->pos; a.mask = (const int64_t*)d->mask; a.out = (uint16_t*)d->out;
   a.q_rope = (uint16_t*)d->q_rope;
   a.ablate = MXVL_ABL_ENV("MXVL_ATTN_ABLATE");
+  a.kvs = kv8 ? (const float*)d->kv_scale : nullptr;
   const hipStream_t s = (hipStream_t)hip_stream;
-  if (kv8) {
-    AttnArgsKv8 ka;
-    ka.a = a;
-    ka.kvs = (const float*)d->kv_scale;
-    return decode_dtype(dt) == MXVL_F16 ? launch_decode_attn_kv8<EltF16>(ka, d->beams, s) : launch_decode_attn_kv8<EltBf16>(ka, d->beams, s);
-  }
-  return decode_dtype(dt) == MXVL_F16 ? launch_decode_attn<EltF16>(a, d->beams, s) : launch_decode_attn<EltBf16>(a, d->beams, s);
+  const bool f16 = decode_dtype(dt) == MXVL_F16;
+  if (kv8) return f16 ? launch_decode_attn<EltF16, KvE4m3<EltF16>>(a, d->beams, s) : launch_decode_attn<EltBf16, KvE4m3<EltBf16>>(a, d->beams, s);
+  return f16 ? launch_decode_attn<EltF16, Kv16<EltF16>>(a, d->beams, s) : launch_decode_attn<EltBf16, Kv16<EltBf16>>(a, d->beams, s);
 }
 
 int mxvl_decode_prologue(const mxvl_decode_prologue_desc* d, void* hip_stream) {

@@ -110,6 +110,36 @@ template <typename E> __device__ inline elt_u32x4 e4m3_unpack8_elt(uint32_t w0, 
 // 1 / s of a power-of-two scale s (a normal fp32): exact, no divide
 __device__ inline float pow2_recip(float s) { return __builtin_bit_cast(float, 0x7f000000u - __builtin_bit_cast(uint32_t, s)); }
 
+// ---- the format of the decode KV cache as a trait: what differs between the 16-bit and the E4M3 cache in decode_attn_body -----------
+// (decode.hip).  LDS-DMA moves 16 bytes per lane, so a lane owns EPL elements of a cache row and D / EPL lanes share the row.
+//   cache_t               one cache element: its size is the bytes per element
+//   scaled                one power-of-two scale per tensor: K's rides on the (already scaled) query, V's on the final output, both
+//                         exact, so what is summed are plain code values; without it (16-bit) no multiply is emitted at all
+//   encode(x, 1/s, val)   the cache bits of a new element; val = the fp32 value those bits stand for: a new K / V enters this step's
+//                         attention as the cache holds it, like every cached position (16-bit: x is already an element's value)
+//   unpack(v, out)        the EPL elements of one 16-byte load as fp32
+template <typename E> struct Kv16 {
+  typedef uint16_t cache_t;
+  static constexpr int EPL = 8;
+  static constexpr bool scaled = false;
+  __device__ static __forceinline__ uint32_t encode(float x, float, float& val) { val = x; return E::r(x); }
+  __device__ static __forceinline__ void unpack(const uint4 v, float* out) { elt_unpack8<E>(v, out); }
+};
+// rows of D bytes: code = rne_e4m3(clamp(x / s)), widened with v_cvt_pk_f32_fp8, four codes per dword
+template <typename E> struct KvE4m3 {
+  typedef uint8_t cache_t;
+  static constexpr int EPL = 16;
+  static constexpr bool scaled = true;
+  __device__ static __forceinline__ uint32_t encode(float x, float recip_scale, float& val) {
+    const uint32_t c = e4m3_encode(x * recip_scale);
+    val = e4m3_decode(c);
+    return c;
+  }
+  __device__ static __forceinline__ void unpack(const uint4 v, float* out) {
+    e4m3_unpack4(v.x, out); e4m3_unpack4(v.y, out + 4); e4m3_unpack4(v.z, out + 8); e4m3_unpack4(v.w, out + 12);
+  }
+};
+
 // mxvl_dtype of a decode descriptor: 0 (what ABI <= 7 callers leave in the reserved field) means bf16
 inline int decode_dtype(int32_t v) { return v == 0 ? MXVL_BF16 : v; }
 // anything but bf16 / fp16 behind that default is refused (MXVL_ERR_DTYPE), not decoded as bf16
