@@ -1,4 +1,4 @@
-"""What the kernel-against-float64 test files share (test_conv1d_gpu.py, test_dwconv2d_gpu.py, test_norm_act_gpu.py): the rounding model
+"""What the kernel-against-float64 test files share (test_conv1d_gpu.py, test_dwconv2d_gpu.py, test_norm_act_gpu.py, test_gemm_gpu.py): the rounding model
 of the fp32 kernels, the err / tol ratio, and the NaN-patterned buffers with guard bands that every tensor a kernel touches is a view into."""
 import torch
 
