@@ -893,10 +893,20 @@ typedef struct mxvl_attn_bwd_desc {
 int mxvl_attn_fwd(const mxvl_attn_desc *desc, void *hip_stream);
 int mxvl_attn_bwd(const mxvl_attn_bwd_desc *desc, void *hip_stream);
 
-/* Stage-2 contrastive step (CXPMRG_Bench_MambaXray_VL/models/MambaXrayVL_CLIP.py:133-148) as one kernel: L2-normalise both
+/* Stage-2 contrastive step (CXPMRG_Bench_MambaXray_VL/models/MambaXrayVL_CLIP.py:133-148): L2-normalise both
  * feature sets, logits = exp(logit_scale) * img_n @ txt_n^T, loss = (CE(logits, arange) + CE(logits^T, arange)) / 2, plus the
  * gradients for d(loss) = 1.  Features fp32 (batch, dim) contiguous; logit_scale (device
- * scalar) is the parameter, i.e. the log of the multiplier; loss and d_logit_scale are device scalars.  batch <= 89. */
+ * scalar) is the parameter, i.e. the log of the multiplier; loss and d_logit_scale are device scalars.
+ *   batch <= 89: one kernel, one workgroup (the logits and their gradient live in LDS).
+ *   90 <= batch <= 4096 and dim >= 16 (a global batch gathered over data-parallel ranks): a fixed sequence of five launches on
+ *   hip_stream -- norms, row / column log-sum-exp, text gradient, image gradient rows >= ceil(8 batch / dim), and one workgroup for
+ *   the two scalars and the remaining image rows -- with the n x n logits recomputed per 32 x 32 tile on the exact-f32 MFMA, never
+ *   stored.  The entry has no workspace parameter: the 8 batch fp32 values that cross a launch boundary (inverse norms, row and
+ *   column maxima and log-sums, per-index loss terms, per-column sums of g l) live in the first 8 batch floats of d_image, which
+ *   is why dim >= 16; d_image and d_text hold INTERMEDIATE values until the last launch of the call has finished.  Nothing is
+ *   allocated, no device state is kept, no atomics, no workgroup waits for another, every sum has one fixed order: the same bits on
+ *   every run in both settings of mxvl_set_deterministic, and the call can be captured in a graph.
+ *   batch > 4096, or batch >= 90 with dim < 16: MXVL_ERR_UNSUPPORTED, before any launch. */
 int mxvl_clip_loss(const float *image_features, const float *text_features, const float *logit_scale, int batch, int dim,
                    float *loss, float *d_image, float *d_text, float *d_logit_scale, void *hip_stream);
 

@@ -336,6 +336,35 @@ def clip_contrastive_loss(image_features, text_features, logit_scale):
     return _ClipLoss.apply(image_features.float(), text_features.float(), logit_scale)
 
 
+def clip_loss_takes(n, dim):
+    """What mxvl_clip_loss serves (csrc/clip_loss.hip): up to 89 rows on the single-workgroup kernel, 90 .. 4096 rows of at least
+    16 features on the multi-workgroup path (its scratch lives in the first 8 n floats of d_image)."""
+    return 1 <= n <= 89 and dim >= 1 or 90 <= n <= 4096 and dim >= 16
+
+
+class _GatherWithGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        import torch.distributed as dist
+        ctx.world, ctx.rank, ctx.n = dist.get_world_size(), dist.get_rank(), x.shape[0]
+        out = x.new_empty((ctx.world * ctx.n,) + tuple(x.shape[1:]))
+        dist.all_gather(list(out.split(ctx.n)), x.contiguous())
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        return ctx.world * grad[ctx.rank * ctx.n:(ctx.rank + 1) * ctx.n]
+
+
+def gather_with_grad(x):
+    """(n, P) of every rank -> (W n, P) in rank order, on every rank.  Every rank must hold the SAME n (the reference samples with
+    drop_last=True).  Every rank then evaluates the same loss L over the global batch, so its encoders receive dL/dF_rank and the true
+    parameter gradient is the SUM of those over ranks: the backward returns W * grad[rank n : (rank + 1) n] and performs no
+    collective, so that DDP's average equals the single-process gradient of L on the concatenated batch.  A parameter that enters L
+    after the gather (logit_scale) already receives the full, identical gradient on every rank; the loss itself is not scaled."""
+    return _GatherWithGrad.apply(x)
+
+
 class MambaXrayVLCLIP(nn.Module):
     """Stage 2: image/report contrastive alignment (MambaXrayVL_CLIP.py:106-150).  `text_encoder` is any module that
     returns `.last_hidden_state` / ["last_hidden_state"] (the reference: HF Bio_ClinicalBERT, third-party)."""
@@ -385,8 +414,11 @@ class MambaXrayVLCLIP(nn.Module):
         image = samples["image"]
         toks = self.tokenizer(samples["input_text"], padding="max_length", truncation=True, return_tensors="pt", max_length=128).to(image[0].device)
         img, txt = self.encode_img(image).float(), self.encode_txt(toks).float()
-        if img.is_cuda and img.shape[0] <= 89:
-            return {"loss": clip_contrastive_loss(img, txt, self.logit_scale)}       # one HIP kernel (csrc/clip_loss.hip)
+        if _get(getattr(self, "args", None), "global_batch", False) and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            img, txt = gather_with_grad(img), gather_with_grad(txt)                  # every rank: the loss over the W n global batch
+        if img.is_cuda and clip_loss_takes(img.shape[0], img.shape[1]):
+            return {"loss": clip_contrastive_loss(img, txt, self.logit_scale)}       # HIP kernels (csrc/clip_loss.hip)
         img, txt = F.normalize(img, dim=1), F.normalize(txt, dim=1)
         logits = self.logit_scale.exp() * img @ txt.t()
         labels = torch.arange(logits.shape[0], device=logits.device)
@@ -411,7 +443,7 @@ def default_args(**kw):
     base = dict(vision_model="None", type="base", dataset="mimic_cxr", freeze_vm=True, vis_use_lora=False, llm_use_lora=False,
                 low_resource=False, end_sym="</s>", delta_file=None, max_length=100, beam_size=3, do_sample=False,
                 min_new_tokens=80, max_new_tokens=120, repetition_penalty=2.0, length_penalty=2.0, temperature=0,
-                kv_cache_dtype=None,
+                kv_cache_dtype=None, global_batch=False,
                 learning_rate=1e-4, max_epochs=1, projection_dim=512, text_encoder_type="Bio_ClinicalBERT")
     base.update(kw)
     return SimpleNamespace(**base)
