@@ -251,6 +251,22 @@ typedef struct mxvl_conv1d_bwd_desc {
  * most 24320 columns, 12032 with swiglu: MXVL_ERR_UNSUPPORTED beyond.
  * As with MXVL_W_INT8 the flag is one high bit of `dtype` and w_scale / w2_scale are read only behind it. */
 #define MXVL_W_MXFP4 0x200
+/* FP8 weights (W8A16): `dtype | MXVL_W_FP8`.  W / W2 are then (N, K) row-major bytes of OCP E4M3 codes (torch.float8_e4m3fn: bias 7, no
+ * infinities, largest finite 448, 0x7f / 0xff NaN), w_scale / w2_scale the (N) fp32 row scales -- the per-channel layout of FP8
+ * checkpoints (`weight` + `weight_scale` (N, 1), viewed flat); x, bias, residual, y stay `dtype & ~MXVL_W_FP8`:
+ *   y[m][n] = epi( s[n] * fp32( sum_k e4m3(W[n][k]) * float(x[m][k]) ) ),   s[n] = w_scale[n]
+ * E4M3 -> bf16 / fp16 is exact (4 significant bits, 2^-9 .. 448) and so is every product in fp32; only the order of the fp32 sum and
+ * the final rounding are the kernel's.  The row scale is any fp32 number and is applied to the fp32 sums.  A NaN code is what
+ * v_cvt_scalef32_pk_{bf16,f16}_fp8 makes of it (NaN, and so the whole output element): the library does not look for them, the
+ * quantiser never produces one and the Python module refuses to load one.
+ * epi, shapes and error codes as MXVL_W_INT8: + bias, + residual, swiglu, split_acc planes (plane p holds s[n] * its partial sum);
+ * rows 1..80, K % 64 == 0, K >= 64, norm_weight == NULL, out_f32 == 0 (MXVL_ERR_SHAPE otherwise, before any launch); a NULL w_scale
+ * (w2_scale with swiglu) is MXVL_ERR_NULL; any two weight flags set is MXVL_ERR_DTYPE.  One kernel serves every row count and
+ * k_splits value (csrc/decode_gemm.h decode_gemm_w8f_kernel: the int8 kernel's geometry, two conversion instructions per four
+ * codes): there is no FP8 form of the <= 8-row GEMV.
+ * As with the other two the flag is one high bit of `dtype` (0x400 is MXVL_KV_FP8, of another descriptor) and w_scale / w2_scale are
+ * read only behind it. */
+#define MXVL_W_FP8 0x800
 typedef struct mxvl_gemv_desc {
   int32_t rows, K, N;
   int32_t swiglu, out_f32;
@@ -276,8 +292,8 @@ typedef struct mxvl_gemv_desc {
                                fp16 (|x| <= 65504 already), and a layer of uniformly small gains (Llama's first input_layernorm: 1e-2 ..
                                1e-3) no longer pushes g * x into fp16's subnormals.  The modules normalise in fp32 FIRST (x * rstd is O(1)),
                                so they never had either failure; bf16 has fp32's exponent range and does not need it. */
-  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8 or MXVL_W_MXFP4 only (never read otherwise).  INT8: (N) fp32 row-wise absmax of W / W2;
-                                       MXFP4: (N, K / 32) E8M0 block scales of W / W2; w2_scale with swiglu */
+  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8, MXVL_W_MXFP4 or MXVL_W_FP8 only (never read otherwise).  INT8: (N) fp32 row-wise absmax
+                                       of W / W2; MXFP4: (N, K / 32) E8M0 block scales of W / W2; FP8: (N) fp32 row scales; w2_scale with swiglu */
 } mxvl_gemv_desc;
 
 /*
@@ -297,7 +313,7 @@ typedef struct mxvl_gemv_desc {
  * The arithmetic is that of the 16-bit kernels over x^ (fp32 sums, beams: 16-bit matrix-core products of code values, P rounded to
  * 16 bits); the K scale multiplies the score, the V scale the output, once each.
  * head_dim 64 and 128 (256: MXVL_ERR_UNSUPPORTED); kv_scale == NULL is MXVL_ERR_NULL; `dtype & ~MXVL_KV_FP8` is validated as `dtype`
- * was, so the flag beside MXVL_W_INT8 / MXVL_W_MXFP4 or an unknown dtype is MXVL_ERR_DTYPE -- all before any launch.  Every other decode
+ * was, so the flag beside MXVL_W_INT8 / MXVL_W_MXFP4 / MXVL_W_FP8 or an unknown dtype is MXVL_ERR_DTYPE -- all before any launch.  Every other decode
  * entry refuses the flag with MXVL_ERR_DTYPE.  kv_scale is a TRAILING field added without a new ABI version, read only behind the
  * flag (the argument of w_scale / w2_scale above). */
 #define MXVL_KV_FP8 0x400
@@ -438,7 +454,7 @@ int mxvl_set_deterministic(int on);
 /* Diagnostic (ABI v8): which kernel mxvl_decode_gemv would launch for a descriptor -- the dispatch as a pure function, nothing is launched
  * and no GPU is needed.  out[0] = 2 the per-row GEMV kernel (<= 8 rows, k_splits == 0), 1 = decode_gemm_wide_kernel, 0 = the K-split
  * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count), 4 = decode_gemm_w4_kernel (MXVL_W_MXFP4,
- * likewise); for 1, 3 and 4: out[1] waves per
+ * likewise), 5 = decode_gemm_w8f_kernel (MXVL_W_FP8, likewise); for 1, 3, 4 and 5: out[1] waves per
  * workgroup, out[2] weight tiles per wave, out[3] LDS ring stages, out[4] workgroups.  Same argument checks and error codes as
  * mxvl_decode_gemv. */
 int mxvl_decode_gemm_plan(const mxvl_gemv_desc *desc, int32_t out[5]);

@@ -1295,7 +1295,7 @@ extern "C" {
 int mxvl_decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   if (!d || !out || !d->x || !d->W || (!d->y && !d->split_acc)) return MXVL_ERR_NULL;
   out[0] = out[1] = out[2] = out[3] = out[4] = 0;
-  if (d->rows > kMaxRows || d->k_splits != 0 || d->split_acc || (d->dtype & (MXVL_W_INT8 | MXVL_W_MXFP4))) return decode_gemm_plan(d, out);
+  if (d->rows > kMaxRows || d->k_splits != 0 || d->split_acc || (d->dtype & kWeightFlags)) return decode_gemm_plan(d, out);
   if (d->rows <= 0 || d->K <= 0 || d->N <= 0) return MXVL_ERR_SHAPE;
   out[0] = 2;
   return MXVL_OK;
@@ -1303,10 +1303,10 @@ int mxvl_decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
 
 int mxvl_decode_gemv(const mxvl_gemv_desc* d, void* hip_stream) {
   if (!d || !d->x || !d->W || (!d->y && !d->split_acc)) return MXVL_ERR_NULL;
-  if (!decode_dtype_ok(d->dtype & ~(MXVL_W_INT8 | MXVL_W_MXFP4))) return MXVL_ERR_DTYPE;
-  // k_splits != 0 asks for the matrix-core kernels at any row count (1 = no split); 0 = by row count.  MXVL_W_INT8 / MXVL_W_MXFP4: there is no quantised
+  if (!decode_dtype_ok(d->dtype & ~kWeightFlags)) return MXVL_ERR_DTYPE;
+  // k_splits != 0 asks for the matrix-core kernels at any row count (1 = no split); 0 = by row count.  MXVL_W_INT8 / MXVL_W_MXFP4 / MXVL_W_FP8: there is no quantised
   // form of the <= 8-row GEMV, the matrix-core kernel takes every row count
-  if (d->rows > kMaxRows || d->k_splits != 0 || d->split_acc || (d->dtype & (MXVL_W_INT8 | MXVL_W_MXFP4))) return decode_gemm_dispatch(d, (hipStream_t)hip_stream);
+  if (d->rows > kMaxRows || d->k_splits != 0 || d->split_acc || (d->dtype & kWeightFlags)) return decode_gemm_dispatch(d, (hipStream_t)hip_stream);
   if (d->rows <= 0 || d->K <= 0 || d->N <= 0) return MXVL_ERR_SHAPE;
   if (d->K % 8 != 0) return MXVL_ERR_UNSUPPORTED;  // 16-byte weight loads
   if (d->norm_weight && d->K > 8192) return MXVL_ERR_UNSUPPORTED;  // fused RMSNorm keeps a whole row in registers

@@ -38,10 +38,11 @@ struct DecodeGemmArgs {
   const uint16_t* g;    // RMSNorm gain (K) of the activation rows, fused (NORM instantiations of the LDS-DMA kernel); else NULL
   float eps;
   float g_scale, g_inv;   // NORM: power-of-two scale on the gain (mxvl_gemv_desc.norm_gain_scale) and its reciprocal, folded into rstd
-  const float *ws, *ws2;  // MXVL_W_INT8: W / W2 are (N, K) int8 codes, ws / ws2 (N) their row-wise absmax (decode_gemm_w8_kernel); else NULL
+  const float *ws, *ws2;  // MXVL_W_INT8: W / W2 are (N, K) int8 codes, ws / ws2 (N) their row-wise absmax (decode_gemm_w8_kernel);
+                          // MXVL_W_FP8: W / W2 are (N, K) E4M3 codes, ws / ws2 (N) their row scales (decode_gemm_w8f_kernel); else NULL
   const uint8_t *wx, *wx2; // MXVL_W_MXFP4: W / W2 are (N, K / 2) packed E2M1 codes, wx / wx2 (N, K / 32) their E8M0 block scales (decode_gemm_w4_kernel); else NULL
+  int w_fp8;              // ws / ws2 belong to MXVL_W_FP8 (host side only: the kernels are instantiated per format)
 };
-constexpr int kWeightFlags = MXVL_W_INT8 | MXVL_W_MXFP4;   // the weight-format bits of mxvl_gemv_desc.dtype
 
 // Reduction over the waves' K split + the epilogue of mxvl_decode_gemv, one round per output tile (SwiGLU: per gate / up pair).
 // acc[r][mt] is lane (col = l%16 -> activation row, 4 * (l/16) + v -> weight row) of the 16x16 tile (weight tile r, row tile mt).
@@ -456,13 +457,14 @@ __device__ __forceinline__ void dgw_epilogue(const DecodeGemmArgs& p, const dg_f
 // pull next to its weight share, and the CUs a grid leaves idle, are what the 80-row projections pay for: NW = 3 where that fills
 // the chip (decode_gemm.hip), and the walk over K staggered per workgroup (below).
 //
-// ONE body for the three weight formats of this decomposition (decode_gemm_wide_kernel: 16-bit; decode_gemm_w8_kernel: MXVL_W_INT8;
-// decode_gemm_w4_kernel: MXVL_W_MXFP4; the latter two at every row count).  A weight row always arrives as whole 128-byte lines, so a
-// chunk is 64 x IMGS columns (IMGS = 1 / 2 / 4), the weight image of a stage is byte for byte the same in all three (16 rows x 128
-// bytes per tile, two DMA instructions, same XOR swizzle) and the activation image is IMGS of the 16-bit kernel's (columns 64 a ..
-// 64 a + 63 of the chunk, 2 IMGS MT one-kilobyte pieces).  Set-up, chunk arithmetic, the two LDS-DMA statements and the ring driver
-// are written once; a format trait (DgW16 / DgW8 / DgW4, below) supplies the constants and the tail rule, and the three steps that
-// really differ -- LDS image -> MFMAs of a stage, mxfp4's scale staging, int8's row scales -- are `if constexpr` branches of the
+// ONE body for the four weight formats of this decomposition (decode_gemm_wide_kernel: 16-bit; decode_gemm_w8_kernel: MXVL_W_INT8;
+// decode_gemm_w8f_kernel: MXVL_W_FP8; decode_gemm_w4_kernel: MXVL_W_MXFP4; the quantised ones at every row count).  A weight row
+// always arrives as whole 128-byte lines, so a chunk is 64 x IMGS columns (IMGS = 1 / 2 / 4), the weight image of a stage is byte
+// for byte the same in all of them (16 rows x 128 bytes per tile, two DMA instructions, same XOR swizzle) and the activation image is
+// IMGS of the 16-bit kernel's (columns 64 a .. 64 a + 63 of the chunk, 2 IMGS MT one-kilobyte pieces).  Set-up, chunk arithmetic, the
+// two LDS-DMA statements and the ring driver are written once; a format trait (DgW16 / DgW8 / DgW8F / DgW4, below) supplies the
+// constants and the tail rule, and the steps that really differ -- LDS image -> MFMAs of a stage (the two one-byte formats: the
+// conversion alone), mxfp4's scale staging, the row scales of int8 and fp8 -- are `if constexpr` branches of the
 // body, not calls into the trait: hipcc forms the LDS addresses of a called step differently (v_add3 becomes two v_add, the mxfp4
 // kernels gain 4..14 VGPRs and lose a wave or two of occupancy), whatever the inlining attribute.
 
@@ -501,6 +503,28 @@ template <> struct W8Cvt<EltF16> {
     const h2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
     lo = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, a) - off);
     hi = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, b) - off);
+  }
+};
+
+// ---- MXVL_W_FP8: OCP E4M3 weights (torch.float8_e4m3fn), one fp32 scale per output row, 16-bit activations, rows 1..80 --------------
+//   y[m][n] = epi( s[n] * fp32( sum_k e4m3(W[n][k]) * float(x[m][k]) ) ),   s[n] = ws[n]
+// The int8 kernel byte for byte -- geometry, LDS images, half-chunk tail, ring depths, plan -- except for the two steps a code's
+// meaning enters: the conversion and the row scale.  v_cvt_scalef32_pk_{bf16,f16}_fp8 turns two codes (the low or, with op_sel, the
+// high half of a word) into one packed 16-bit word: two VALU instructions per four codes where int8 needs about nine.  Its scale
+// operand is the constant 1.0: a row scale is an arbitrary fp32 number, not a power of two, so it stays on the fp32 sums.  E4M3 ->
+// bf16 / fp16 is exact (4 significant bits, 2^-9 .. 448) and so is every product in fp32.  A NaN code (0x7f / 0xff) converts to NaN.
+template <typename E> struct W8FCvt;
+template <> struct W8FCvt<EltBf16> {
+  // four codes (one word) -> two packed words: codes 0, 1 and codes 2, 3
+  __device__ static inline void cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+    lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
+  }
+};
+template <> struct W8FCvt<EltF16> {
+  __device__ static inline void cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+    lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+    hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true));
   }
 };
 
@@ -550,12 +574,16 @@ struct DgW16 {                                           // a chunk is one image
 };
 struct DgW8 {                                            // weight units 4..7 re-read units 0..3, the second image's pieces re-read the first
   static constexpr int IMGS = 2;
+  static constexpr bool E4M3 = false;                    // the byte is an int8 code (row scale ws[n] / 127), not an E4M3 one (ws[n])
   static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * K; }
   static __device__ __forceinline__ bool vq(int K) { return (K & 64) != 0; }
   // bit 2 of a lane's source unit depends on bit 1 of the row only: the same for both DMA calls of a tile
   static __device__ __forceinline__ int wback(bool, int ul, int row) { return ((ul ^ dg_key(row & 7)) & 4) ? 64 : 0; }
   static __device__ __forceinline__ int aback(bool, int img) { return img * 128; }
   __host__ __device__ static constexpr int scale_lds(int, int, int) { return 0; }
+};
+struct DgW8F : DgW8 {                                    // DgW8's geometry; the body picks W8FCvt and the plain row scale
+  static constexpr bool E4M3 = true;
 };
 struct DgW4 {                                            // weight units >= 2 vq re-read unit 0, images >= vq re-read image 0
   static constexpr int IMGS = 4;
@@ -723,7 +751,7 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
           for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(av, bf[mt], acc[r][mt]);
         }
       }
-    } else if constexpr (IMGS == 2) {                              // int8: 16 codes of row l16 widened to two A operands
+    } else if constexpr (IMGS == 2) {                              // int8 / fp8: 16 codes of row l16 widened to two A operands
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (j == 1 && tail) break;
@@ -733,10 +761,17 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
         for (int r = 0; r < R; ++r) {
           const dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
           uint32_t o[8];
-          W8Cvt<E>::cvt4(av.x, o[0], o[1]);
-          W8Cvt<E>::cvt4(av.y, o[2], o[3]);
-          W8Cvt<E>::cvt4(av.z, o[4], o[5]);
-          W8Cvt<E>::cvt4(av.w, o[6], o[7]);
+          if constexpr (Fmt::E4M3) {
+            W8FCvt<E>::cvt4(av.x, o[0], o[1]);
+            W8FCvt<E>::cvt4(av.y, o[2], o[3]);
+            W8FCvt<E>::cvt4(av.z, o[4], o[5]);
+            W8FCvt<E>::cvt4(av.w, o[6], o[7]);
+          } else {
+            W8Cvt<E>::cvt4(av.x, o[0], o[1]);
+            W8Cvt<E>::cvt4(av.y, o[2], o[3]);
+            W8Cvt<E>::cvt4(av.z, o[4], o[5]);
+            W8Cvt<E>::cvt4(av.w, o[6], o[7]);
+          }
           cv[r][0] = dg_u32x4{o[0], o[1], o[2], o[3]};
           cv[r][1] = dg_u32x4{o[4], o[5], o[6], o[7]};
         }
@@ -815,7 +850,7 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ranges shorter than the ring: the prologue's repeats may not land after the workgroup is gone)
 
-  if constexpr (IMGS == 2) {                           // int8: the row scales on the fp32 sums
+  if constexpr (IMGS == 2) {                           // int8, fp8: the row scales on the fp32 sums
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int t = p.swiglu ? (r % (R / 2 > 0 ? R / 2 : 1)) : r;
@@ -823,7 +858,9 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         const int n = n0 + t * 16 + 4 * q + v;
-        const float sc = n < N ? sp[n] / 127.0f : 0.0f;
+        float sc = 0.0f;
+        if constexpr (Fmt::E4M3) sc = n < N ? sp[n] : 0.0f;
+        else sc = n < N ? sp[n] / 127.0f : 0.0f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[r][mt][v] *= sc;
       }
@@ -836,6 +873,8 @@ template <typename E, int MT, int R, int NW, int PF>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW16, E, MT, R, NW, PF>(p); }
 template <typename E, int MT, int R, int NW, int PF>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_w8_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW8, E, MT, R, NW, PF>(p); }
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w8f_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW8F, E, MT, R, NW, PF>(p); }
 template <typename E, int MT, int R, int NW, int PF>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW4, E, MT, R, NW, PF>(p); }
 

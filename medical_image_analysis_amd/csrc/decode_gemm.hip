@@ -42,7 +42,7 @@ static int launch_direct(const DecodeGemmArgs& a, int splits, hipStream_t s) {
 }
 
 // ---- the N-split ring kernels (decode_gemm.h dg_nsplit_body): 16-bit weights at 17..80 rows (decode_gemm_wide_kernel), MXVL_W_INT8
-// (decode_gemm_w8_kernel) and MXVL_W_MXFP4 (decode_gemm_w4_kernel) at every row count ------------------------------------------------
+// (decode_gemm_w8_kernel), MXVL_W_FP8 (decode_gemm_w8f_kernel) and MXVL_W_MXFP4 (decode_gemm_w4_kernel) at every row count ------------
 // ring depth: as many stages of `stage` bytes as `budget` bytes of LDS hold (one workgroup per CU is all these grids ask for), capped
 // by the 6-bit vmcnt field (`ops` requests per stage) and at 8 -- against the first version's 3 stages: 48-row token +5 %, 80-row
 // +0.7 % (profiles/r05_decode_gemm_ring_ab.txt)
@@ -75,6 +75,7 @@ static int launch_nsplit(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   const size_t lds = (size_t)PF * nsplit_stage<Fmt>(MT, R, NW) + (size_t)Fmt::scale_lds(NW, R, nsplit_cpw<Fmt>(a, splits));
   void (*kern)(const DecodeGemmArgs);
   if constexpr (std::is_same_v<Fmt, DgW8>) kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
+  else if constexpr (std::is_same_v<Fmt, DgW8F>) kern = decode_gemm_w8f_kernel<E, MT, R, NW, PF>;
   else if constexpr (std::is_same_v<Fmt, DgW4>) kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
   else kern = decode_gemm_wide_kernel<E, MT, R, NW, PF>;
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
@@ -106,14 +107,14 @@ static WidePlan nsplit_plan(int f, int MT, const DecodeGemmArgs& a, int splits, 
   }
   return pl;
 }
-// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 = the 16-bit / int8 / mxfp4 N-split kernel with `pl`, 0 = the
-// K-split kernels keep it, < 0 = an error
+// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 / 5 = the 16-bit / int8 / mxfp4 / fp8 N-split kernel with `pl`,
+// 0 = the K-split kernels keep it, < 0 = an error
 static int decode_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
   // quantised: four waves, one or two tiles per wave (four leave the ring two or three stages at 33..80 rows and no registers for
   // the widened operands)
-  if (a.ws) {
+  if (a.ws) {     // int8 and fp8 move the same bytes through the same geometry: one plan
     pl = nsplit_plan(DgW8::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [](const WidePlan&) { return true; });
-    return 3;
+    return a.w_fp8 ? 5 : 3;
   }
   if (a.wx) {     // the scale rows' share of LDS: two tiles per wave up to a K range of 12032 columns per workgroup, one tile up to 24320
     const int cpw = nsplit_cpw<DgW4>(a, splits);
@@ -155,6 +156,7 @@ static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s
     case 1: return launch_planned<DgW16, E, MT>(pl, a, splits, s);
     case 3: return launch_planned<DgW8, E, MT>(pl, a, splits, s);
     case 4: return launch_planned<DgW4, E, MT>(pl, a, splits, s);
+    case 5: return launch_planned<DgW8F, E, MT>(pl, a, splits, s);
     default: return kind;
   }
   // R = weight tiles per workgroup.  Two effects, both measured (tools/decode_gemm_bench.py A/B at 18 rows, profiles/r04_decode_gemm_r_sweep.txt):
@@ -221,14 +223,15 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   if (kind < 0) return kind;
   if (kind == 0) pl = WidePlan{0, 0, 0};
   out[0] = kind; out[1] = pl.nw; out[2] = pl.r; out[4] = (int32_t)pl.g;
-  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : plan_pf<DgW4>(MT, pl);
+  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : kind == 5 ? plan_pf<DgW8F>(MT, pl) : plan_pf<DgW4>(MT, pl);
   return MXVL_OK;
 }
 
 // argument checks of mxvl_decode_gemv + the kernel-side argument block (nothing is launched here)
 static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& splits) {
-  if (!decode_dtype_ok(d->dtype & ~kWeightFlags) || (d->dtype & kWeightFlags) == kWeightFlags) return MXVL_ERR_DTYPE;   // one weight format at most
-  const bool w8 = (d->dtype & MXVL_W_INT8) != 0, w4 = (d->dtype & MXVL_W_MXFP4) != 0;   // w_scale / w2_scale exist in the caller's struct only behind these flags
+  const int wf = d->dtype & kWeightFlags;
+  if (!decode_dtype_ok(d->dtype & ~kWeightFlags) || (wf & (wf - 1))) return MXVL_ERR_DTYPE;   // one weight format at most
+  const bool w8f = wf == MXVL_W_FP8, w8 = wf == MXVL_W_INT8 || w8f, w4 = wf == MXVL_W_MXFP4;   // w_scale / w2_scale exist in the caller's struct only behind these flags
   if ((w8 || w4) && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
   if ((w8 || w4) && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no quantised form of these
@@ -247,6 +250,7 @@ static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& spl
   a.ws2 = (w8 && d->swiglu) ? (const float*)d->w2_scale : nullptr;
   a.wx = w4 ? (const uint8_t*)d->w_scale : nullptr;
   a.wx2 = (w4 && d->swiglu) ? (const uint8_t*)d->w2_scale : nullptr;
+  a.w_fp8 = w8f;
   if (d->norm_weight && d->norm_gain_scale != 0.0f) {
     int e = 0;
     const float m = frexpf(d->norm_gain_scale, &e);

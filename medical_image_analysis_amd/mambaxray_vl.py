@@ -14,7 +14,9 @@ Differences, all at the edges of the hot path:
   * `low_resource` (the reference loads the frozen LLM with load_in_8bit=True, MambaXrayVL_DownStream.py:82-92) stores the layer
     projections of the LLM as row-wise absmax int8 -- bitsandbytes' weight format -- served by this build's own kernels
     (ReportDecoder.quantize_int8_, int8_linear.py; W8A16: activations stay 16-bit, no bitsandbytes needed); `low_resource="mxfp4"`
-    (this build's own option) stores them as OCP MXFP4 instead (ReportDecoder.quantize_mxfp4_, mxfp4_linear.py; W4A16);
+    (this build's own option) stores them as OCP MXFP4 instead (ReportDecoder.quantize_mxfp4_, mxfp4_linear.py; W4A16) and
+    `low_resource="fp8"` (likewise) as OCP E4M3 codes with one fp32 scale per output row, the per-channel layout of FP8 checkpoints
+    (ReportDecoder.quantize_fp8_, fp8_linear.py; W8A16);
   * PEFT-LoRA wrappers (`vis_use_lora`, `llm_use_lora`) are not built: they wrap third-party modules outside the path and raise
     NotImplementedError when requested.
 """
@@ -47,7 +49,8 @@ def _get(args, name, default=None):
 
 def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
-    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading, "mxfp4": MXFP4 ones (quantize_mxfp4_)."""
+    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading, "mxfp4": MXFP4 ones (quantize_mxfp4_),
+    "fp8": row-wise E4M3 ones (quantize_fp8_); every other truthy value is int8."""
     sd = None
     if source is None or source == "llama2-7b":
         cfg = dict(LLAMA2_7B)
@@ -75,6 +78,8 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         llm.load_hf_state_dict(sd)
     if low_resource == "mxfp4":
         llm.quantize_mxfp4_()
+    elif low_resource == "fp8":
+        llm.quantize_fp8_()
     elif low_resource:
         llm.quantize_int8_()
     return llm
@@ -154,9 +159,12 @@ class MambaXrayVLDownStream(nn.Module):
                           cross_attn_gating_type=_get(args, "cross_attn_gating_type", "channel-wise-dynamic-sigmoid"))
         self.llama_model = llm if llm is not None else build_report_decoder(source, **hybrid)
         low = _get(args, "low_resource", False)
-        if low == "mxfp4":                      # OCP MXFP4 layer projections (mxfp4_linear.py); every other truthy value is the reference's int8
+        if low == "mxfp4":                      # OCP MXFP4 layer projections (mxfp4_linear.py)
             if not self.llama_model.is_mxfp4():
                 self.llama_model.quantize_mxfp4_()
+        elif low == "fp8":                      # row-wise E4M3 layer projections (fp8_linear.py); every other truthy value is the reference's int8
+            if not self.llama_model.is_fp8():
+                self.llama_model.quantize_fp8_()
         elif low and not self.llama_model.is_int8():
             self.llama_model.quantize_int8_()
         self.llama_tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(_get(args, "llama_model"))

@@ -1,4 +1,4 @@
-"""What the quantised Linear modules of the frozen report LLM share (int8_linear.Int8Linear, mxfp4_linear.MxFp4Linear): the decode step
+"""What the quantised Linear modules of the frozen report LLM share (int8_linear.Int8Linear, mxfp4_linear.MxFp4Linear, fp8_linear.Fp8Linear): the decode step
 reads their codes and scales directly (mxvl_decode_gemv with the class's ABI flag); the multi-token paths -- prompt prefill, stage-3
 training through the frozen LLM -- dequantise one weight at a time into a scratch buffer shared by every layer of a decoder and run
 F.linear on it: eager torch on purpose, it runs once per generate / training step and layer, not once per token."""
@@ -92,7 +92,7 @@ class QuantLinear(nn.Module):
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         local = {k: v for k, v in state_dict.items() if k.startswith(prefix) and k[len(prefix):] not in self.IGNORED_KEYS}
         w = local.get(prefix + "weight")
-        if w is not None and w.is_floating_point():
+        if w is not None and w.is_floating_point() and w.dtype != self.codes.dtype:       # (floating codes -- fp8 -- load as they are)
             del local[prefix + "weight"]
             local[prefix + self.CODES], local[prefix + self.SCALES] = self.quantize(w)
         super()._load_from_state_dict(local, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)

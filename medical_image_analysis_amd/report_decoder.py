@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
+from .fp8_linear import Fp8Linear
 from .int8_linear import Int8Linear
 from .mxfp4_linear import MxFp4Linear
 from .quant_linear import DequantScratch, QuantLinear
@@ -623,7 +624,7 @@ class _KernelStepper(_Stepper):
         fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
             (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
         if model.weight_format() is not None and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
-            return False         # int8 / mxfp4 projections (MXVL_W_INT8, MXVL_W_MXFP4): K % 64 == 0 on the one kernel each has
+            return False         # int8 / mxfp4 / fp8 projections (MXVL_W_INT8, MXVL_W_MXFP4, MXVL_W_FP8): K % 64 == 0 on the one kernel each has
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
@@ -656,8 +657,8 @@ class _KernelStepper(_Stepper):
         self.batched = rows > 8 or (self.hidden % 64 == 0 and self.inter % 64 == 0 and (self.H * self.D) % 64 == 0)
         # int8 layer projections (ReportDecoder.quantize_int8_): the matrix-core kernel at every row count, explicit norm launches
         # ("split" mode) -- there is no int8 form of the fused RMSNorm; lm_head and the embedding stay 16-bit
-        # mxfp4 layer projections (ReportDecoder.quantize_mxfp4_) take the same route with MXVL_W_MXFP4
-        self.wfmt = model.weight_format()                # None, Int8Linear or MxFp4Linear
+        # mxfp4 / fp8 layer projections (ReportDecoder.quantize_mxfp4_, quantize_fp8_) take the same route with MXVL_W_MXFP4 / MXVL_W_FP8
+        self.wfmt = model.weight_format()                # None, Int8Linear, MxFp4Linear or Fp8Linear
         self.quantised = self.wfmt is not None
         # rows <= 8: RMSNorm fused into the MFMA projection that consumes the rows (csrc/decode_gemm.h NORM, K % 64 == 0): no
         # mxvl_decode_rmsnorm launches (65 of a token's 229), o_proj / down_proj add their residual in their own epilogue instead of
@@ -774,6 +775,7 @@ class _KernelStepper(_Stepper):
 
     int8 = property(lambda self: self.wfmt is Int8Linear)
     mxfp4 = property(lambda self: self.wfmt is MxFp4Linear)
+    fp8 = property(lambda self: self.wfmt is Fp8Linear)
 
     def _rmsnorm(self, x, norm, eps, K, fold_res=None, x_out=None, splits=1):
         """rows > 8: RMSNorm ahead of an MFMA projection (the GEMV kernel, rows <= 8, normalises in its own prologue).  With
@@ -789,7 +791,7 @@ class _KernelStepper(_Stepper):
     def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0, scale=None, scale2=None):
         d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
-        if scale is not None:                   # W / W2 are int8 codes + row-wise absmax (SCB), or packed E2M1 codes + E8M0 block scales
+        if scale is not None:                   # W / W2 are int8 codes + row-wise absmax (SCB), packed E2M1 codes + E8M0 block scales, or E4M3 codes + row scales
             d.dtype |= self.wfmt.W_FLAG
             d.w_scale, d.w2_scale = scale.data_ptr(), _abi.ptr(scale2)
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
@@ -963,7 +965,7 @@ class ReportDecoder(nn.Module):
                 b = torch.cat([at.q_proj.bias, at.k_proj.bias, at.v_proj.bias], dim=0).contiguous()
                 nq, nk = w0.shape[0], _codes(at.k_proj).shape[0]
                 if isinstance(at.q_proj, QuantLinear):
-                    # int8 / mxfp4: the codes' rows and the per-row (per-block) scales concatenate exactly; the buffers become views of
+                    # int8 / mxfp4 / fp8: the codes' rows and the per-row (per-block) scales concatenate exactly; the buffers become views of
                     # the fused ones (assigned, not .data: the unfused storage is released, no second copy of the bytes)
                     S = torch.cat([lin.scales for lin in qkv], dim=0).contiguous()
                     for lin, lo, hi in ((at.q_proj, 0, nq), (at.k_proj, nq, nq + nk), (at.v_proj, nq + nk, W.shape[0])):
@@ -978,7 +980,7 @@ class ReportDecoder(nn.Module):
     _INT8_TARGETS = (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj")))
 
     def weight_format(self):
-        """None (16-bit), Int8Linear or MxFp4Linear: the class of the layer projections"""
+        """None (16-bit), Int8Linear, MxFp4Linear or Fp8Linear: the class of the layer projections"""
         cls = type(self.model.layers[0].mlp.down_proj)
         return cls if issubclass(cls, QuantLinear) else None
 
@@ -988,13 +990,32 @@ class ReportDecoder(nn.Module):
     def is_mxfp4(self):
         return self.weight_format() is MxFp4Linear
 
+    def is_fp8(self):
+        return self.weight_format() is Fp8Linear
+
+    _FORMAT_NAMES = {Int8Linear: "int8", MxFp4Linear: "mxfp4", Fp8Linear: "fp8"}
+
+    def _refuse_other_format(self, cls):
+        """Formats do not mix on one decoder: a quantised decoder's 16-bit weights are gone, and codes are not re-quantised."""
+        cur = self.weight_format()
+        if cur is not None and cur is not cls:
+            new, old = self._FORMAT_NAMES[cls], self._FORMAT_NAMES[cur]
+            raise RuntimeError(f"quantize_{new}_() on an {old} decoder: quantise the 16-bit weights, not their {old} codes")
+
+    def quantize_fp8_(self):
+        """`low_resource="fp8"`: the projections quantize_int8_ covers become Fp8Linear (OCP E4M3 codes, one fp32 scale per output
+        row; fp8_linear.py) and their 16-bit storage is released; the same modules stay 16-bit.  The bytes of int8, on the 8-bit
+        format gfx950 converts in one instruction per two codes.  An int8 or mxfp4 decoder is refused: its 16-bit weights are gone."""
+        self._refuse_other_format(Fp8Linear)
+        self._quantize_layers(Fp8Linear)
+        return self
+
     def quantize_mxfp4_(self):
         """`low_resource="mxfp4"`: the projections quantize_int8_ covers become MxFp4Linear (OCP MXFP4: E2M1 codes, one E8M0 scale
         per 32 along K; mxfp4_linear.py) and their 16-bit storage is released; the same modules stay 16-bit.  Every in_features
-        must be a multiple of 32; an fp16 weight outside fp16's exact range raises (quantize_mxfp4).  An int8 decoder is refused:
-        its 16-bit weights are gone."""
-        if self.is_int8():
-            raise RuntimeError("quantize_mxfp4_() on an int8 decoder: quantise the 16-bit weights, not their int8 codes")
+        must be a multiple of 32; an fp16 weight outside fp16's exact range raises (quantize_mxfp4).  An int8 or fp8 decoder is
+        refused: its 16-bit weights are gone."""
+        self._refuse_other_format(MxFp4Linear)
         self._quantize_layers(MxFp4Linear)
         return self
 
@@ -1018,8 +1039,7 @@ class ReportDecoder(nn.Module):
         (row-wise absmax int8, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head (HF's 8-bit loader
         skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The layers share
         one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly."""
-        if self.is_mxfp4():
-            raise RuntimeError("quantize_int8_() on an mxfp4 decoder: quantise the 16-bit weights, not their 4-bit codes")
+        self._refuse_other_format(Int8Linear)
         self._quantize_layers(Int8Linear)
         return self
 
