@@ -267,6 +267,26 @@ typedef struct mxvl_conv1d_bwd_desc {
  * As with the other two the flag is one high bit of `dtype` (0x400 is MXVL_KV_FP8, of another descriptor) and w_scale / w2_scale are
  * read only behind it. */
 #define MXVL_W_FP8 0x800
+/* Group-wise int4 weights (W4A16): `dtype | MXVL_W_INT4`, the arithmetic of GPTQ 4-bit checkpoints at group size 128 without act-order.
+ * W / W2 are then (N, K / 2) bytes of unsigned 4-bit codes q in 0..15.  The eight codes of columns 8 i .. 8 i + 7 of a row form ONE
+ * little-endian 32-bit word, the code of column 8 i + e in nibble (e >> 1) + 4 * (e & 1):
+ *   word = sum_e q[8 i + e] << 4 * ((e >> 1) + 4 * (e & 1))       (bytes: e0 | e2 << 4,  e4 | e6 << 4,  e1 | e3 << 4,  e5 | e7 << 4)
+ * so that (word >> 4 p) & 0x000f000f is the pair of columns 8 i + 2 p (low half) and 8 i + 2 p + 1 (high half), the order of a
+ * packed 16-bit matrix-core operand (a GPTQ `qweight` holds the same eight codes in nibble order e: a permutation inside the word).
+ * w_scale / w2_scale are (N, K / 128) 32-bit words, 4-byte aligned: the low half holds the IEEE fp16 bits of the group scale s
+ * (whatever the activation dtype is), the high half the zero point z in 0..15.  x, bias, residual, y stay 16-bit.
+ *   w[n][k] = dtype_rne( float(s[n][k / 128]) * (q[n][k] - z[n][k / 128]) )       y[m][n] = epi( fp32( sum_k w[n][k] * x[m][k] ) )
+ * The product s (q - z) is exact in fp32 (11 x 5 significant bits) and rounded ONCE to the activation dtype (fp16: GPTQ's own
+ * `scales * (q - zeros)`); it rides on the weight operand, not on the sums.  Conversion and products are exact, only the order of the
+ * fp32 sum and the final rounding are the kernel's.  An s that is inf or NaN gives what the arithmetic gives; z above 15 is not handled.
+ * epi, shapes and error codes as MXVL_W_MXFP4: + bias, + residual, swiglu, split_acc planes; rows 1..80, norm_weight == NULL,
+ * out_f32 == 0, and here K % 128 == 0, K >= 128 (MXVL_ERR_SHAPE otherwise, before any launch); a NULL w_scale (w2_scale with swiglu)
+ * is MXVL_ERR_NULL; any two weight flags set is MXVL_ERR_DTYPE.  One kernel serves every row count and k_splits value
+ * (csrc/decode_gemm.h decode_gemm_w4i_kernel: the MXFP4 kernel's geometry; a 128-column group is what the four lane groups of one
+ * weight read cover); it keeps its rows' scale words in LDS at the MXFP4 kernel's pitch, so the same K range per workgroup applies
+ * (24320 columns, 12032 with swiglu: MXVL_ERR_UNSUPPORTED beyond).
+ * The flag is a new high bit of `dtype` (refused with MXVL_ERR_DTYPE until now); w_scale / w2_scale are read only behind it. */
+#define MXVL_W_INT4 0x1000
 typedef struct mxvl_gemv_desc {
   int32_t rows, K, N;
   int32_t swiglu, out_f32;
@@ -292,8 +312,9 @@ typedef struct mxvl_gemv_desc {
                                fp16 (|x| <= 65504 already), and a layer of uniformly small gains (Llama's first input_layernorm: 1e-2 ..
                                1e-3) no longer pushes g * x into fp16's subnormals.  The modules normalise in fp32 FIRST (x * rstd is O(1)),
                                so they never had either failure; bf16 has fp32's exponent range and does not need it. */
-  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8, MXVL_W_MXFP4 or MXVL_W_FP8 only (never read otherwise).  INT8: (N) fp32 row-wise absmax
-                                       of W / W2; MXFP4: (N, K / 32) E8M0 block scales of W / W2; FP8: (N) fp32 row scales; w2_scale with swiglu */
+  const void *w_scale, *w2_scale;   /* with MXVL_W_INT8, MXVL_W_MXFP4, MXVL_W_FP8 or MXVL_W_INT4 only (never read otherwise).  INT8: (N) fp32 row-wise
+                                       absmax of W / W2; MXFP4: (N, K / 32) E8M0 block scales of W / W2; FP8: (N) fp32 row scales; INT4: (N, K / 128)
+                                       words, fp16 scale | zero point << 16; w2_scale with swiglu */
 } mxvl_gemv_desc;
 
 /*
@@ -454,7 +475,7 @@ int mxvl_set_deterministic(int on);
 /* Diagnostic (ABI v8): which kernel mxvl_decode_gemv would launch for a descriptor -- the dispatch as a pure function, nothing is launched
  * and no GPU is needed.  out[0] = 2 the per-row GEMV kernel (<= 8 rows, k_splits == 0), 1 = decode_gemm_wide_kernel, 0 = the K-split
  * matrix-core kernels, 3 = decode_gemm_w8_kernel (a descriptor with MXVL_W_INT8, at every row count), 4 = decode_gemm_w4_kernel (MXVL_W_MXFP4,
- * likewise), 5 = decode_gemm_w8f_kernel (MXVL_W_FP8, likewise); for 1, 3, 4 and 5: out[1] waves per
+ * likewise), 5 = decode_gemm_w8f_kernel (MXVL_W_FP8, likewise), 6 = decode_gemm_w4i_kernel (MXVL_W_INT4, likewise); for 1, 3, 4, 5 and 6: out[1] waves per
  * workgroup, out[2] weight tiles per wave, out[3] LDS ring stages, out[4] workgroups.  Same argument checks and error codes as
  * mxvl_decode_gemv. */
 int mxvl_decode_gemm_plan(const mxvl_gemv_desc *desc, int32_t out[5]);

@@ -21,6 +21,7 @@ MXVL_F32, MXVL_BF16, MXVL_F16 = 0, 1, 2
 MXVL_W_INT8 = 0x100      # mxvl_gemv_desc.dtype flag: W / W2 are int8 codes, w_scale / w2_scale their row-wise absmax
 MXVL_W_MXFP4 = 0x200     # mxvl_gemv_desc.dtype flag: W / W2 are packed E2M1 codes (N, K / 2), w_scale / w2_scale their E8M0 block scales (N, K / 32)
 MXVL_W_FP8 = 0x800       # mxvl_gemv_desc.dtype flag: W / W2 are OCP E4M3 codes (N, K), w_scale / w2_scale their fp32 row scales (N)
+MXVL_W_INT4 = 0x1000     # mxvl_gemv_desc.dtype flag: W / W2 are packed unsigned int4 codes (N, K / 2), w_scale / w2_scale (N, K / 128) words: fp16 group scale | zero point << 16
 MXVL_KV_FP8 = 0x400     # mxvl_decode_attn_desc.dtype flag: k_cache / v_cache are OCP E4M3 bytes, kv_scale their two power-of-two scales
 SCAN_DELTA_SOFTPLUS = 1
 SCAN_OUT_F32 = 2          # out / dout fp32 whatever io_dtype is (the oflex i16o32 mode)

@@ -145,6 +145,6 @@ inline int decode_dtype(int32_t v) { return v == 0 ? MXVL_BF16 : v; }
 // anything but bf16 / fp16 behind that default is refused (MXVL_ERR_DTYPE), not decoded as bf16
 inline bool decode_dtype_ok(int32_t v) { return v == 0 || v == MXVL_BF16 || v == MXVL_F16; }
 // the weight-format bits of mxvl_gemv_desc.dtype: at most one of them may be set
-constexpr int kWeightFlags = MXVL_W_INT8 | MXVL_W_MXFP4 | MXVL_W_FP8;
+constexpr int kWeightFlags = MXVL_W_INT8 | MXVL_W_MXFP4 | MXVL_W_FP8 | MXVL_W_INT4;
 
 }  // namespace mxvl

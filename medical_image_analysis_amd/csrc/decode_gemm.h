@@ -40,8 +40,11 @@ struct DecodeGemmArgs {
   float g_scale, g_inv;   // NORM: power-of-two scale on the gain (mxvl_gemv_desc.norm_gain_scale) and its reciprocal, folded into rstd
   const float *ws, *ws2;  // MXVL_W_INT8: W / W2 are (N, K) int8 codes, ws / ws2 (N) their row-wise absmax (decode_gemm_w8_kernel);
                           // MXVL_W_FP8: W / W2 are (N, K) E4M3 codes, ws / ws2 (N) their row scales (decode_gemm_w8f_kernel); else NULL
-  const uint8_t *wx, *wx2; // MXVL_W_MXFP4: W / W2 are (N, K / 2) packed E2M1 codes, wx / wx2 (N, K / 32) their E8M0 block scales (decode_gemm_w4_kernel); else NULL
+  const uint8_t *wx, *wx2; // MXVL_W_MXFP4: W / W2 are (N, K / 2) packed E2M1 codes, wx / wx2 (N, K / 32) their E8M0 block scales (decode_gemm_w4_kernel);
+                           // MXVL_W_INT4: W / W2 are (N, K / 2) packed int4 codes, wx / wx2 (N, K / 128) scale | zero-point words -- the same
+                           // K / 32 bytes per row (decode_gemm_w4i_kernel); else NULL
   int w_fp8;              // ws / ws2 belong to MXVL_W_FP8 (host side only: the kernels are instantiated per format)
+  int w_int4;             // wx / wx2 belong to MXVL_W_INT4 (host side only, likewise)
 };
 
 // Reduction over the waves' K split + the epilogue of mxvl_decode_gemv, one round per output tile (SwiGLU: per gate / up pair).
@@ -457,12 +460,13 @@ __device__ __forceinline__ void dgw_epilogue(const DecodeGemmArgs& p, const dg_f
 // pull next to its weight share, and the CUs a grid leaves idle, are what the 80-row projections pay for: NW = 3 where that fills
 // the chip (decode_gemm.hip), and the walk over K staggered per workgroup (below).
 //
-// ONE body for the four weight formats of this decomposition (decode_gemm_wide_kernel: 16-bit; decode_gemm_w8_kernel: MXVL_W_INT8;
-// decode_gemm_w8f_kernel: MXVL_W_FP8; decode_gemm_w4_kernel: MXVL_W_MXFP4; the quantised ones at every row count).  A weight row
+// ONE body for the five weight formats of this decomposition (decode_gemm_wide_kernel: 16-bit; decode_gemm_w8_kernel: MXVL_W_INT8;
+// decode_gemm_w8f_kernel: MXVL_W_FP8; decode_gemm_w4_kernel: MXVL_W_MXFP4; decode_gemm_w4i_kernel: MXVL_W_INT4; the quantised ones at
+// every row count).  A weight row
 // always arrives as whole 128-byte lines, so a chunk is 64 x IMGS columns (IMGS = 1 / 2 / 4), the weight image of a stage is byte
 // for byte the same in all of them (16 rows x 128 bytes per tile, two DMA instructions, same XOR swizzle) and the activation image is
 // IMGS of the 16-bit kernel's (columns 64 a .. 64 a + 63 of the chunk, 2 IMGS MT one-kilobyte pieces).  Set-up, chunk arithmetic, the
-// two LDS-DMA statements and the ring driver are written once; a format trait (DgW16 / DgW8 / DgW8F / DgW4, below) supplies the
+// two LDS-DMA statements and the ring driver are written once; a format trait (DgW16 / DgW8 / DgW8F / DgW4 / DgW4I, below) supplies the
 // constants and the tail rule, and the steps that really differ -- LDS image -> MFMAs of a stage (the two one-byte formats: the
 // conversion alone), mxfp4's scale staging, the row scales of int8 and fp8 -- are `if constexpr` branches of the
 // body, not calls into the trait: hipcc forms the LDS addresses of a called step differently (v_add3 becomes two v_add, the mxfp4
@@ -561,6 +565,56 @@ template <> struct W4Cvt<EltF16> {
 // bytes of LDS per scale row for a K range of `cpw` chunks (host and kernel agree through this one function)
 __host__ __device__ constexpr int w4_scale_pitch(int cpw) { return cpw * 8 + 4; }
 
+// ---- MXVL_W_INT4: unsigned 4-bit codes, one fp16 scale and one 4-bit zero point per 128 along K (GPTQ's arithmetic), rows 1..80 -----
+//   y[m][n] = epi( fp32( sum_k w[n][k] * x[m][k] ) ),   w[n][k] = dtype_rne( float(s[n][k / 128]) * (q[n][k] - z[n][k / 128]) )
+// decode_gemm_w4_kernel byte for byte -- chunks of 256 columns, LDS images, tail rule, ring depths, plan -- except for what a code
+// means.  One ds_read_b128 is 32 codes of row l16, columns 32 u .. 32 u + 31 with u = 4 j + q: for a fixed j the four lane groups
+// cover ONE 128-column group, so a lane needs one scale word per (tile, j), and a 256-column chunk 2 x 4 scale bytes per row: the
+// mxfp4 kernel's scale rows in LDS (w4_scale_pitch), filled by the same copy.  K % 128 == 0: a tail chunk is its first group alone.
+// gfx950 has no conversion instruction for this format.  A word holds the codes of columns 8 i + e in nibble (e >> 1) + 4 (e & 1)
+// (include/mxvl.h), so (w >> 4 p) & 0x000f000f is already the pair of operand word p:
+//   fp16: | 0x64006400 makes it (1024 + q0, 1024 + q1); one packed subtraction of 1024 + z leaves q - z exactly, one packed
+//         multiplication by s rounds s (q - z) once.  In the ISA: shift, v_and, v_or, v_pk_add_f16, v_pk_mul_f16 -- 5 VALU
+//         instructions per pair (hipcc does not form v_and_or_b32 from two literals; 3.75 with it)
+//   bf16: no packed bf16 arithmetic: the nibbles as integers -> fp32, fma(q, s, -z s) -- q s and z s are exact in fp32 and so is
+//         their difference: the fma rounds nothing --, v_cvt_pk_bf16_f32 rounds once.  In the ISA: per pair two v_cvt_f32_ubyte0
+//         behind about three shift / mask instructions (hipcc folds the byte masks away and with them v_cvt_f32_ubyte1..3), one
+//         v_pk_fma_f32, one v_cvt_pk_bf16_f32 -- 7 per pair (4.75 with the byte forms)
+// against one per pair for mxfp4's v_cvt_scalef32_pk_*_fp4.  What that costs beside the MFMAs: DESIGN.md 4.7h.
+template <typename E> struct W4ICvt;
+template <> struct W4ICvt<EltF16> {
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  h2 zo, s2;                                             // (1024 + z) and s, each in both halves
+  __device__ inline explicit W4ICvt(uint32_t sw)
+      : zo(__builtin_bit_cast(h2, 0x64006400u | ((sw >> 16) * 0x10001u))), s2(__builtin_bit_cast(h2, (sw & 0xffffu) * 0x10001u)) {}
+  __device__ inline dg_u32x4 cvt8(uint32_t w) const {   // the eight codes of one word -> one A operand
+    uint32_t o[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const uint32_t m = ((w >> (4 * p)) & 0x000f000fu) | 0x64006400u;
+      o[p] = __builtin_bit_cast(uint32_t, (__builtin_bit_cast(h2, m) - zo) * s2);
+    }
+    return dg_u32x4{o[0], o[1], o[2], o[3]};
+  }
+};
+template <> struct W4ICvt<EltBf16> {
+  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  float s, c;                                            // s and -z s
+  __device__ inline explicit W4ICvt(uint32_t sw) : s((float)__builtin_bit_cast(_Float16, (uint16_t)sw)), c(-(float)(sw >> 16) * s) {}
+  __device__ inline dg_u32x4 cvt8(uint32_t w) const {
+    const uint32_t even = w & 0x0f0f0f0fu, odd = (w >> 4) & 0x0f0f0f0fu;      // nibbles 0, 2, 4, 6 and 1, 3, 5, 7 as bytes
+    uint32_t o[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {                        // operand word p: nibbles p and p + 4
+      const uint32_t src = (p & 1) ? odd : even;
+      const float q0 = (float)((src >> (8 * (p >> 1))) & 0xffu), q1 = (float)((src >> (8 * (p >> 1) + 16)) & 0xffu);
+      o[p] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{__builtin_fmaf(q0, s, c), __builtin_fmaf(q1, s, c)}, b2));
+    }
+    return dg_u32x4{o[0], o[1], o[2], o[3]};
+  }
+};
+
 // Format traits of dg_nsplit_body.  K % 64 == 0 always, so the last chunk of a row holds vq = (K / 64) % IMGS 64-column images (0: it
 // is whole); its DMA sources past the row are pulled back inside it by wback (weights: source unit ul ^ dg_key(row) of a lane) and
 // aback (the activation pieces of image img) bytes.
@@ -587,12 +641,16 @@ struct DgW8F : DgW8 {                                    // DgW8's geometry; the
 };
 struct DgW4 {                                            // weight units >= 2 vq re-read unit 0, images >= vq re-read image 0
   static constexpr int IMGS = 4;
+  static constexpr bool INT4 = false;                    // a nibble is an E2M1 code (E8M0 scale per 32), not an int4 one (scale | zero point per 128)
   static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * (K >> 1); }
   static __device__ __forceinline__ int vq(int K) { return (K >> 6) & 3; }
   static __device__ __forceinline__ int wback(int vq, int ul, int row) { const int su = ul ^ dg_key(row); return su >= 2 * vq ? su << 4 : 0; }
   static __device__ __forceinline__ int aback(int vq, int img) { return img >= vq ? img * 128 : 0; }
   // LDS behind the ring: the waves' scale rows over a K range of `cpw` chunks (host and kernel agree through this one function)
   __host__ __device__ static constexpr int scale_lds(int NW, int R, int cpw) { return NW * R * 16 * w4_scale_pitch(cpw); }
+};
+struct DgW4I : DgW4 {                                    // DgW4's geometry (K % 128 == 0: vq is 0 or 2); the body picks W4ICvt and the scale words
+  static constexpr bool INT4 = true;
 };
 
 template <typename Fmt, typename E, int MT, int R, int NW, int PF>
@@ -687,7 +745,7 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
   };
 #pragma unroll
   for (int j = 0; j < PF - 1; ++j) issue(j, c_begin + j);
-  // mxfp4: this wave's scale bytes over the workgroup's K range into LDS behind the ring, 4 rows x 16 lanes per pass.  (The loads'
+  // mxfp4, int4: this wave's scale bytes over the workgroup's K range into LDS behind the ring, 4 rows x 16 lanes per pass.  (The loads'
   // results are waited for with vmcnt(0), i.e. together with the ring's prologue, which the first iteration needs anyway.)
   struct { const char* rows; int pitch; } sc{};
   if constexpr (IMGS == 4) {
@@ -729,7 +787,8 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
           }
       }
     };
-    if ((KS & 3) == 0) copy(uint32_t{0}); else copy(uint16_t{0});
+    if constexpr (Fmt::INT4) copy(uint32_t{0});          // (N, K / 128) words: the same K / 32 bytes per row, always whole words
+    else if ((KS & 3) == 0) copy(uint32_t{0}); else copy(uint16_t{0});
     sc = {sc_l, pitch};
   }
   auto consume = [&](int slot, int c) {
@@ -787,7 +846,7 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
             for (int mt = 0; mt < MT; ++mt) acc[r][mt] = E::mfma32(cv[r][h], bf[mt], acc[r][mt]);
         }
       }
-    } else {                                                       // mxfp4: 32 codes = one scale block, four A operands
+    } else {                                                       // mxfp4 / int4: 32 codes (mxfp4: one scale block), four A operands
       const char* scp = sc.rows + (cc - c_begin) * 8 + l16 * sc.pitch;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -799,13 +858,19 @@ __device__ __forceinline__ void dg_nsplit_body(const DecodeGemmArgs& p) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           dg_u32x4 av = *(const dg_u32x4*)(wt + r * 2048 + l16 * 128 + wunit);
-          const uint32_t e = *(const uint8_t*)(scp + r * 16 * sc.pitch + u);
-          const float s = __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);      // 2^(e - 127); e = 0 is fp32's subnormal 2^-127
-          if (dead) av = dg_u32x4{0u, 0u, 0u, 0u};
+          if constexpr (Fmt::INT4) {             // the lane groups' blocks 4 j .. 4 j + 3 are ONE group: word j of the chunk, never past the row
+            const W4ICvt<E> cvt(*(const uint32_t*)(scp + r * 16 * sc.pitch + 4 * j));
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-            cv[r][i] = dg_u32x4{W4Cvt<E>::template cvt2<0>(av[i], s), W4Cvt<E>::template cvt2<1>(av[i], s),
-                                W4Cvt<E>::template cvt2<2>(av[i], s), W4Cvt<E>::template cvt2<3>(av[i], s)};
+            for (int i = 0; i < 4; ++i) cv[r][i] = cvt.cvt8(av[i]);
+          } else {
+            const uint32_t e = *(const uint8_t*)(scp + r * 16 * sc.pitch + u);
+            const float s = __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);      // 2^(e - 127); e = 0 is fp32's subnormal 2^-127
+            if (dead) av = dg_u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              cv[r][i] = dg_u32x4{W4Cvt<E>::template cvt2<0>(av[i], s), W4Cvt<E>::template cvt2<1>(av[i], s),
+                                  W4Cvt<E>::template cvt2<2>(av[i], s), W4Cvt<E>::template cvt2<3>(av[i], s)};
+          }
         }
         const char* aq = act + (2 * j + (q >> 1)) * (MT * 2048) + l16 * 128;
 #pragma unroll
@@ -877,6 +942,8 @@ template <typename E, int MT, int R, int NW, int PF>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_w8f_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW8F, E, MT, R, NW, PF>(p); }
 template <typename E, int MT, int R, int NW, int PF>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_w4_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW4, E, MT, R, NW, PF>(p); }
+template <typename E, int MT, int R, int NW, int PF>
+__global__ __launch_bounds__(NW * 64) void decode_gemm_w4i_kernel(const DecodeGemmArgs p) { dg_nsplit_body<DgW4I, E, MT, R, NW, PF>(p); }
 
 // RMSNorm of the activation rows ahead of a projection (Qwen2RMSNorm / LlamaRMSNorm, EMRRG/models/hybrid_decoder_layer.py:185-199):
 // y = bf16( bf16(x * rsqrt(mean(x^2) + eps)) * g ), statistics in fp32.  One workgroup per row.  (At <= 8 rows the GEMV kernel

@@ -42,7 +42,8 @@ static int launch_direct(const DecodeGemmArgs& a, int splits, hipStream_t s) {
 }
 
 // ---- the N-split ring kernels (decode_gemm.h dg_nsplit_body): 16-bit weights at 17..80 rows (decode_gemm_wide_kernel), MXVL_W_INT8
-// (decode_gemm_w8_kernel), MXVL_W_FP8 (decode_gemm_w8f_kernel) and MXVL_W_MXFP4 (decode_gemm_w4_kernel) at every row count ------------
+// (decode_gemm_w8_kernel), MXVL_W_FP8 (decode_gemm_w8f_kernel), MXVL_W_MXFP4 (decode_gemm_w4_kernel) and MXVL_W_INT4 (decode_gemm_w4i_kernel)
+// at every row count ----------------------------------------------------------------------------------------------------------------
 // ring depth: as many stages of `stage` bytes as `budget` bytes of LDS hold (one workgroup per CU is all these grids ask for), capped
 // by the 6-bit vmcnt field (`ops` requests per stage) and at 8 -- against the first version's 3 stages: 48-row token +5 %, 80-row
 // +0.7 % (profiles/r05_decode_gemm_ring_ab.txt)
@@ -51,13 +52,13 @@ constexpr int ring_depth(int stage, int ops, int budget) {
   while (pf > 2 && (pf - 1) * ops > 63) --pf;
   return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
 }
-// LDS budgets: the ring gets 150 KB; with mxfp4 112 KB, and the waves' scale rows up to 48 KB (Llama-7B's K = 11008 unsplit at two
+// LDS budgets: the ring gets 150 KB; with mxfp4 / int4 112 KB, and the waves' scale rows up to 48 KB (Llama-7B's K = 11008 unsplit at two
 // tiles per wave needs 43.5)
 constexpr int kRingBytes = 150 * 1024, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
 // a stage: IMGS activation images of MT tiles + NW x R weight tiles, 2 R + ceil(2 IMGS MT / NW) requests per wave
 template <typename Fmt> constexpr int nsplit_stage(int MT, int R, int NW) { return Fmt::IMGS * MT * 2048 + NW * R * 2048; }
 template <typename Fmt> constexpr int nsplit_pf(int MT, int R, int NW) {
-  return ring_depth(nsplit_stage<Fmt>(MT, R, NW), 2 * R + (2 * Fmt::IMGS * MT + NW - 1) / NW, std::is_same_v<Fmt, DgW4> ? kW4RingBytes : kRingBytes);
+  return ring_depth(nsplit_stage<Fmt>(MT, R, NW), 2 * R + (2 * Fmt::IMGS * MT + NW - 1) / NW, Fmt::IMGS == 4 ? kW4RingBytes : kRingBytes);
 }
 template <typename Fmt> static int nsplit_cpw(const DecodeGemmArgs& a, int splits) {      // chunks of a workgroup's K range
   return ((a.K + 64 * Fmt::IMGS - 1) / (64 * Fmt::IMGS) + splits - 1) / splits;
@@ -77,6 +78,7 @@ static int launch_nsplit(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   if constexpr (std::is_same_v<Fmt, DgW8>) kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
   else if constexpr (std::is_same_v<Fmt, DgW8F>) kern = decode_gemm_w8f_kernel<E, MT, R, NW, PF>;
   else if constexpr (std::is_same_v<Fmt, DgW4>) kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
+  else if constexpr (std::is_same_v<Fmt, DgW4I>) kern = decode_gemm_w4i_kernel<E, MT, R, NW, PF>;
   else kern = decode_gemm_wide_kernel<E, MT, R, NW, PF>;
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
@@ -107,7 +109,7 @@ static WidePlan nsplit_plan(int f, int MT, const DecodeGemmArgs& a, int splits, 
   }
   return pl;
 }
-// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 / 5 = the 16-bit / int8 / mxfp4 / fp8 N-split kernel with `pl`,
+// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 / 5 / 6 = the 16-bit / int8 / mxfp4 / fp8 / int4 N-split kernel with `pl`,
 // 0 = the K-split kernels keep it, < 0 = an error
 static int decode_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
   // quantised: four waves, one or two tiles per wave (four leave the ring two or three stages at 33..80 rows and no registers for
@@ -116,10 +118,11 @@ static int decode_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl
     pl = nsplit_plan(DgW8::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [](const WidePlan&) { return true; });
     return a.w_fp8 ? 5 : 3;
   }
-  if (a.wx) {     // the scale rows' share of LDS: two tiles per wave up to a K range of 12032 columns per workgroup, one tile up to 24320
+  if (a.wx) {     // mxfp4 and int4 move the same bytes (codes and K / 32 scale bytes per row) through the same geometry: one plan.
+                  // the scale rows' share of LDS: two tiles per wave up to a K range of 12032 columns per workgroup, one tile up to 24320
     const int cpw = nsplit_cpw<DgW4>(a, splits);
     pl = nsplit_plan(DgW4::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [&](const WidePlan& c) { return DgW4::scale_lds(c.nw, c.r, cpw) <= kW4ScaleBytes; });
-    return pl.r ? 4 : MXVL_ERR_UNSUPPORTED;
+    return pl.r ? (a.w_int4 ? 6 : 4) : MXVL_ERR_UNSUPPORTED;
   }
   // 16-bit: from 17 rows and 64 workgroups on (profiles/r05_decode_gemm_wide_rows_ab.txt: against the K-split kernels the 18-row token
   // +7 %, the 24-row token +11 %, Qwen1.5-1.8B's 96..128-workgroup projections +4 % at 80 rows; the first version -- 3-stage
@@ -157,6 +160,7 @@ static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s
     case 3: return launch_planned<DgW8, E, MT>(pl, a, splits, s);
     case 4: return launch_planned<DgW4, E, MT>(pl, a, splits, s);
     case 5: return launch_planned<DgW8F, E, MT>(pl, a, splits, s);
+    case 6: return launch_planned<DgW4I, E, MT>(pl, a, splits, s);
     default: return kind;
   }
   // R = weight tiles per workgroup.  Two effects, both measured (tools/decode_gemm_bench.py A/B at 18 rows, profiles/r04_decode_gemm_r_sweep.txt):
@@ -223,7 +227,7 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   if (kind < 0) return kind;
   if (kind == 0) pl = WidePlan{0, 0, 0};
   out[0] = kind; out[1] = pl.nw; out[2] = pl.r; out[4] = (int32_t)pl.g;
-  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : kind == 5 ? plan_pf<DgW8F>(MT, pl) : plan_pf<DgW4>(MT, pl);
+  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : kind == 5 ? plan_pf<DgW8F>(MT, pl) : kind == 6 ? plan_pf<DgW4I>(MT, pl) : plan_pf<DgW4>(MT, pl);
   return MXVL_OK;
 }
 
@@ -231,10 +235,11 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
 static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& splits) {
   const int wf = d->dtype & kWeightFlags;
   if (!decode_dtype_ok(d->dtype & ~kWeightFlags) || (wf & (wf - 1))) return MXVL_ERR_DTYPE;   // one weight format at most
-  const bool w8f = wf == MXVL_W_FP8, w8 = wf == MXVL_W_INT8 || w8f, w4 = wf == MXVL_W_MXFP4;   // w_scale / w2_scale exist in the caller's struct only behind these flags
+  const bool w8f = wf == MXVL_W_FP8, w8 = wf == MXVL_W_INT8 || w8f, w4i = wf == MXVL_W_INT4, w4 = wf == MXVL_W_MXFP4 || w4i;   // w_scale / w2_scale exist in the caller's struct only behind these flags
   if ((w8 || w4) && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
   if ((w8 || w4) && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no quantised form of these
+  if (w4i && (d->K % 128 != 0 || d->K < 128)) return MXVL_ERR_SHAPE;                                        // whole 128-column groups
   if (d->K % 8 != 0) return MXVL_ERR_UNSUPPORTED;                      // 16-byte fragments
   if (d->swiglu && (!d->W2 || d->out_f32)) return MXVL_ERR_UNSUPPORTED;
   // RMSNorm fused into the projection (ABI v8): the LDS-DMA kernel only (K % 64 == 0); elsewhere rows come from mxvl_decode_rmsnorm
@@ -251,6 +256,7 @@ static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& spl
   a.wx = w4 ? (const uint8_t*)d->w_scale : nullptr;
   a.wx2 = (w4 && d->swiglu) ? (const uint8_t*)d->w2_scale : nullptr;
   a.w_fp8 = w8f;
+  a.w_int4 = w4i;
   if (d->norm_weight && d->norm_gain_scale != 0.0f) {
     int e = 0;
     const float m = frexpf(d->norm_gain_scale, &e);

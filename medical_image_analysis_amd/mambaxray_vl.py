@@ -16,7 +16,9 @@ Differences, all at the edges of the hot path:
     (ReportDecoder.quantize_int8_, int8_linear.py; W8A16: activations stay 16-bit, no bitsandbytes needed); `low_resource="mxfp4"`
     (this build's own option) stores them as OCP MXFP4 instead (ReportDecoder.quantize_mxfp4_, mxfp4_linear.py; W4A16) and
     `low_resource="fp8"` (likewise) as OCP E4M3 codes with one fp32 scale per output row, the per-channel layout of FP8 checkpoints
-    (ReportDecoder.quantize_fp8_, fp8_linear.py; W8A16);
+    (ReportDecoder.quantize_fp8_, fp8_linear.py; W8A16); `low_resource="int4"` (likewise) as unsigned 4-bit codes with one fp16
+    scale and one zero point per 128 input channels, the arithmetic of GPTQ checkpoints (ReportDecoder.quantize_int4_,
+    int4_linear.py; W4A16) -- and a GPTQ checkpoint directory (4 bits, group size 128, no act-order) loads in that format as it is;
   * PEFT-LoRA wrappers (`vis_use_lora`, `llm_use_lora`) are not built: they wrap third-party modules outside the path and raise
     NotImplementedError when requested.
 """
@@ -50,8 +52,10 @@ def _get(args, name, default=None):
 def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
     a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading, "mxfp4": MXFP4 ones (quantize_mxfp4_),
-    "fp8": row-wise E4M3 ones (quantize_fp8_); every other truthy value is int8."""
-    sd = None
+    "fp8": row-wise E4M3 ones (quantize_fp8_), "int4": group-wise int4 ones (quantize_int4_); every other truthy value is int8.
+    A checkpoint directory whose config.json carries `quantization_config.quant_method == "gptq"` is loaded AS int4 (prepare_int4_
+    swaps the layer projections before the load; the codes are repacked, not re-quantised): low_resource must then be falsy or "int4"."""
+    sd = gptq = None
     if source is None or source == "llama2-7b":
         cfg = dict(LLAMA2_7B)
     elif source == "qwen1.5-1.8b":
@@ -62,6 +66,11 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         with open(os.path.join(source, "config.json")) as f:
             raw = json.load(f)
         cfg = {k: raw[k] for k in _CFG_KEYS if k in raw}
+        qc = raw.get("quantization_config") or {}
+        if qc.get("quant_method") == "gptq":
+            if low_resource and low_resource != "int4":
+                raise ValueError(f"{source}: a GPTQ checkpoint decodes as int4; low_resource={low_resource!r} would need the 16-bit weights it does not hold")
+            gptq = qc
         from safetensors.torch import load_file
         sd = {}
         for name in sorted(os.listdir(source)):
@@ -72,6 +81,8 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
                                 "(this build never downloads weights)")
     cfg.update(overrides)
     llm = ReportDecoder(**cfg).to(dtype)
+    if gptq is not None:
+        llm.prepare_int4_(gptq)
     if sd is not None:
         if "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
             sd["lm_head.weight"] = sd["model.embed_tokens.weight"]          # tied embeddings
@@ -80,6 +91,8 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         llm.quantize_mxfp4_()
     elif low_resource == "fp8":
         llm.quantize_fp8_()
+    elif low_resource == "int4":
+        llm.quantize_int4_()                # (a GPTQ checkpoint is int4 already: nothing to do)
     elif low_resource:
         llm.quantize_int8_()
     return llm
@@ -162,9 +175,12 @@ class MambaXrayVLDownStream(nn.Module):
         if low == "mxfp4":                      # OCP MXFP4 layer projections (mxfp4_linear.py)
             if not self.llama_model.is_mxfp4():
                 self.llama_model.quantize_mxfp4_()
-        elif low == "fp8":                      # row-wise E4M3 layer projections (fp8_linear.py); every other truthy value is the reference's int8
+        elif low == "fp8":                      # row-wise E4M3 layer projections (fp8_linear.py)
             if not self.llama_model.is_fp8():
                 self.llama_model.quantize_fp8_()
+        elif low == "int4":                     # group-wise int4 layer projections (int4_linear.py); every other truthy value is the reference's int8
+            if not self.llama_model.is_int4():
+                self.llama_model.quantize_int4_()
         elif low and not self.llama_model.is_int8():
             self.llama_model.quantize_int8_()
         self.llama_tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(_get(args, "llama_model"))

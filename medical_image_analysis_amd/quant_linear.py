@@ -1,4 +1,5 @@
-"""What the quantised Linear modules of the frozen report LLM share (int8_linear.Int8Linear, mxfp4_linear.MxFp4Linear, fp8_linear.Fp8Linear): the decode step
+"""What the quantised Linear modules of the frozen report LLM share (int8_linear.Int8Linear, mxfp4_linear.MxFp4Linear, fp8_linear.Fp8Linear,
+int4_linear.Int4GroupLinear): the decode step
 reads their codes and scales directly (mxvl_decode_gemv with the class's ABI flag); the multi-token paths -- prompt prefill, stage-3
 training through the frozen LLM -- dequantise one weight at a time into a scratch buffer shared by every layer of a decoder and run
 F.linear on it: eager torch on purpose, it runs once per generate / training step and layer, not once per token."""
