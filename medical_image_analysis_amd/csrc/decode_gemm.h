@@ -43,9 +43,9 @@ struct DecodeGemmArgs {
   const uint8_t *wx, *wx2; // MXVL_W_MXFP4: W / W2 are (N, K / 2) packed E2M1 codes, wx / wx2 (N, K / 32) their E8M0 block scales (decode_gemm_w4_kernel);
                            // MXVL_W_INT4: W / W2 are (N, K / 2) packed int4 codes, wx / wx2 (N, K / 128) scale | zero-point words -- the same
                            // K / 32 bytes per row (decode_gemm_w4i_kernel); else NULL
-  int w_fp8;              // ws / ws2 belong to MXVL_W_FP8 (host side only: the kernels are instantiated per format)
-  int w_int4;             // wx / wx2 belong to MXVL_W_INT4 (host side only, likewise)
+  int w_flag;             // the MXVL_W_* flag of W / W2, 0: 16-bit (host side only: the kernels are instantiated per format)
 };
+static_assert(sizeof(DecodeGemmArgs) == 144, "the kernels' argument block: w_flag and the tail padding stand where two host-only ints stood");
 
 // Reduction over the waves' K split + the epilogue of mxvl_decode_gemv, one round per output tile (SwiGLU: per gate / up pair).
 // acc[r][mt] is lane (col = l%16 -> activation row, 4 * (l/16) + v -> weight row) of the 16x16 tile (weight tile r, row tile mt).
@@ -618,8 +618,14 @@ template <> struct W4ICvt<EltBf16> {
 // Format traits of dg_nsplit_body.  K % 64 == 0 always, so the last chunk of a row holds vq = (K / 64) % IMGS 64-column images (0: it
 // is whole); its DMA sources past the row are pulled back inside it by wback (weights: source unit ul ^ dg_key(row) of a lane) and
 // aback (the activation pieces of image img) bytes.
+// What the host dispatch (decode_gemm.hip with_format) reads of a format: W_FLAG its MXVL_W_* flag (0: 16-bit), KIND what
+// mxvl_decode_gemm_plan reports for its kernel, K_MULT the granularity of K, RING_BYTES the LDS budget of its ring, set_scales which
+// pointer pair of DecodeGemmArgs holds its scales.
+// LDS budgets: the ring gets 150 KB; with mxfp4 / int4 112 KB, and the waves' scale rows up to 48 KB (Llama-7B's K = 11008 unsplit at two
+// tiles per wave needs 43.5)
+constexpr int kRingBytes = 150 * 1024, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
 struct DgW16 {                                           // a chunk is one image: every chunk is whole
-  static constexpr int IMGS = 1;
+  static constexpr int IMGS = 1, W_FLAG = 0, KIND = 1, K_MULT = 64, RING_BYTES = kRingBytes;
   static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)(W + (size_t)n * K); }
   static __device__ __forceinline__ int vq(int) { return 0; }
   static __device__ __forceinline__ int wback(int, int, int) { return 0; }
@@ -627,7 +633,8 @@ struct DgW16 {                                           // a chunk is one image
   __host__ __device__ static constexpr int scale_lds(int, int, int) { return 0; }
 };
 struct DgW8 {                                            // weight units 4..7 re-read units 0..3, the second image's pieces re-read the first
-  static constexpr int IMGS = 2;
+  static constexpr int IMGS = 2, W_FLAG = MXVL_W_INT8, KIND = 3, K_MULT = 64, RING_BYTES = kRingBytes;
+  static void set_scales(DecodeGemmArgs& a, const void* s, const void* s2) { a.ws = (const float*)s; a.ws2 = (const float*)s2; }
   static constexpr bool E4M3 = false;                    // the byte is an int8 code (row scale ws[n] / 127), not an E4M3 one (ws[n])
   static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * K; }
   static __device__ __forceinline__ bool vq(int K) { return (K & 64) != 0; }
@@ -638,9 +645,11 @@ struct DgW8 {                                            // weight units 4..7 re
 };
 struct DgW8F : DgW8 {                                    // DgW8's geometry; the body picks W8FCvt and the plain row scale
   static constexpr bool E4M3 = true;
+  static constexpr int W_FLAG = MXVL_W_FP8, KIND = 5;
 };
 struct DgW4 {                                            // weight units >= 2 vq re-read unit 0, images >= vq re-read image 0
-  static constexpr int IMGS = 4;
+  static constexpr int IMGS = 4, W_FLAG = MXVL_W_MXFP4, KIND = 4, K_MULT = 64, RING_BYTES = kW4RingBytes;
+  static void set_scales(DecodeGemmArgs& a, const void* s, const void* s2) { a.wx = (const uint8_t*)s; a.wx2 = (const uint8_t*)s2; }
   static constexpr bool INT4 = false;                    // a nibble is an E2M1 code (E8M0 scale per 32), not an int4 one (scale | zero point per 128)
   static __device__ __forceinline__ const char* row(const uint16_t* W, int n, int K) { return (const char*)W + (size_t)n * (K >> 1); }
   static __device__ __forceinline__ int vq(int K) { return (K >> 6) & 3; }
@@ -651,6 +660,7 @@ struct DgW4 {                                            // weight units >= 2 vq
 };
 struct DgW4I : DgW4 {                                    // DgW4's geometry (K % 128 == 0: vq is 0 or 2); the body picks W4ICvt and the scale words
   static constexpr bool INT4 = true;
+  static constexpr int W_FLAG = MXVL_W_INT4, KIND = 6, K_MULT = 128;         // whole 128-column groups
 };
 
 template <typename Fmt, typename E, int MT, int R, int NW, int PF>

@@ -52,13 +52,11 @@ constexpr int ring_depth(int stage, int ops, int budget) {
   while (pf > 2 && (pf - 1) * ops > 63) --pf;
   return pf > 8 ? 8 : (pf < 2 ? 2 : pf);
 }
-// LDS budgets: the ring gets 150 KB; with mxfp4 / int4 112 KB, and the waves' scale rows up to 48 KB (Llama-7B's K = 11008 unsplit at two
-// tiles per wave needs 43.5)
-constexpr int kRingBytes = 150 * 1024, kW4RingBytes = 112 * 1024, kW4ScaleBytes = 48 * 1024;
-// a stage: IMGS activation images of MT tiles + NW x R weight tiles, 2 R + ceil(2 IMGS MT / NW) requests per wave
+// a stage: IMGS activation images of MT tiles + NW x R weight tiles, 2 R + ceil(2 IMGS MT / NW) requests per wave; the LDS budgets
+// (Fmt::RING_BYTES) stand beside the format traits in decode_gemm.h
 template <typename Fmt> constexpr int nsplit_stage(int MT, int R, int NW) { return Fmt::IMGS * MT * 2048 + NW * R * 2048; }
 template <typename Fmt> constexpr int nsplit_pf(int MT, int R, int NW) {
-  return ring_depth(nsplit_stage<Fmt>(MT, R, NW), 2 * R + (2 * Fmt::IMGS * MT + NW - 1) / NW, Fmt::IMGS == 4 ? kW4RingBytes : kRingBytes);
+  return ring_depth(nsplit_stage<Fmt>(MT, R, NW), 2 * R + (2 * Fmt::IMGS * MT + NW - 1) / NW, Fmt::RING_BYTES);
 }
 template <typename Fmt> static int nsplit_cpw(const DecodeGemmArgs& a, int splits) {      // chunks of a workgroup's K range
   return ((a.K + 64 * Fmt::IMGS - 1) / (64 * Fmt::IMGS) + splits - 1) / splits;
@@ -69,12 +67,25 @@ static int g_wide_min_mt = 2;  // wide from 17 rows on (A/B: mode 5 = from 33 ro
 static int g_wide_min_g = 64;  // ... for grids of at least 64 workgroups (A/B: mode 5 = 160)
 static int g_decode_gemm_wide = 1;        // mxvl_set_decode_gemm_wide: the A/B switch of tools / bench (default on; 2: also at 17..32 rows)
 
+// THE list of weight formats: f(the trait of weight flag `flag`), 0 = 16-bit.  Anything else -- two flags at once -- is no format.
+template <typename F>
+static int with_format(int flag, F&& f) {
+  switch (flag) {
+    case DgW16::W_FLAG: return f(DgW16{});
+    case DgW8::W_FLAG: return f(DgW8{});
+    case DgW4::W_FLAG: return f(DgW4{});
+    case DgW8F::W_FLAG: return f(DgW8F{});
+    case DgW4I::W_FLAG: return f(DgW4I{});
+    default: return MXVL_ERR_DTYPE;
+  }
+}
+
 template <typename Fmt, typename E, int MT, int R, int NW, int PF>
 static int launch_nsplit(const DecodeGemmArgs& a, int splits, hipStream_t s) {
   const int cols_per_wg = NW * (a.swiglu ? R / 2 : R) * 16;
   const dim3 grid((a.N + cols_per_wg - 1) / cols_per_wg, splits);
   const size_t lds = (size_t)PF * nsplit_stage<Fmt>(MT, R, NW) + (size_t)Fmt::scale_lds(NW, R, nsplit_cpw<Fmt>(a, splits));
-  void (*kern)(const DecodeGemmArgs);
+  void (*kern)(const DecodeGemmArgs);      // the __global__ wrapper of the format (decode_gemm.h): the one place that names them
   if constexpr (std::is_same_v<Fmt, DgW8>) kern = decode_gemm_w8_kernel<E, MT, R, NW, PF>;
   else if constexpr (std::is_same_v<Fmt, DgW8F>) kern = decode_gemm_w8f_kernel<E, MT, R, NW, PF>;
   else if constexpr (std::is_same_v<Fmt, DgW4>) kern = decode_gemm_w4_kernel<E, MT, R, NW, PF>;
@@ -109,42 +120,43 @@ static WidePlan nsplit_plan(int f, int MT, const DecodeGemmArgs& a, int splits, 
   }
   return pl;
 }
-// kind of the launch as mxvl_decode_gemm_plan reports it: 1 / 3 / 4 / 5 / 6 = the 16-bit / int8 / mxfp4 / fp8 / int4 N-split kernel with `pl`,
-// 0 = the K-split kernels keep it, < 0 = an error
+// kind of the launch as mxvl_decode_gemm_plan reports it: Fmt::KIND (1 / 3 / 4 / 5 / 6 = the 16-bit / int8 / mxfp4 / fp8 / int4 N-split kernel)
+// with `pl`, 0 = the K-split kernels keep it, < 0 = an error.  Three planning groups, by the bytes a weight takes (Fmt::IMGS).
+template <typename Fmt>
 static int decode_plan(int MT, const DecodeGemmArgs& a, int splits, WidePlan& pl) {
   // quantised: four waves, one or two tiles per wave (four leave the ring two or three stages at 33..80 rows and no registers for
   // the widened operands)
-  if (a.ws) {     // int8 and fp8 move the same bytes through the same geometry: one plan
-    pl = nsplit_plan(DgW8::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [](const WidePlan&) { return true; });
-    return a.w_fp8 ? 5 : 3;
-  }
-  if (a.wx) {     // mxfp4 and int4 move the same bytes (codes and K / 32 scale bytes per row) through the same geometry: one plan.
+  if constexpr (Fmt::IMGS == 2) {     // int8 and fp8 move the same bytes through the same geometry: one plan
+    pl = nsplit_plan(Fmt::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [](const WidePlan&) { return true; });
+    return Fmt::KIND;
+  } else if constexpr (Fmt::IMGS == 4) {     // mxfp4 and int4 move the same bytes (codes and K / 32 scale bytes per row) through the same geometry: one plan.
                   // the scale rows' share of LDS: two tiles per wave up to a K range of 12032 columns per workgroup, one tile up to 24320
-    const int cpw = nsplit_cpw<DgW4>(a, splits);
-    pl = nsplit_plan(DgW4::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [&](const WidePlan& c) { return DgW4::scale_lds(c.nw, c.r, cpw) <= kW4ScaleBytes; });
-    return pl.r ? (a.w_int4 ? 6 : 4) : MXVL_ERR_UNSUPPORTED;
+    const int cpw = nsplit_cpw<Fmt>(a, splits);
+    pl = nsplit_plan(Fmt::IMGS, MT, a, splits, {{4, 1}, {4, 2}}, [&](const WidePlan& c) { return Fmt::scale_lds(c.nw, c.r, cpw) <= kW4ScaleBytes; });
+    return pl.r ? Fmt::KIND : MXVL_ERR_UNSUPPORTED;
+  } else {
+    // 16-bit: from 17 rows and 64 workgroups on (profiles/r05_decode_gemm_wide_rows_ab.txt: against the K-split kernels the 18-row token
+    // +7 %, the 24-row token +11 %, Qwen1.5-1.8B's 96..128-workgroup projections +4 % at 80 rows; the first version -- 3-stage
+    // ring, aligned walks -- had lost to them below 160 workgroups and at 17..32 rows).  At 1..16 rows the K-split kernel keeps the
+    // launches: it carries the fused RMSNorm, and without it the wide kernel is +2 % (Llama) / 0 % (Qwen) there.
+    if (!(g_decode_gemm_wide && MT >= g_wide_min_mt && a.K % Fmt::K_MULT == 0 && a.K >= 256 && !a.g)) return 0;
+    pl = nsplit_plan(Fmt::IMGS, MT, a, splits, {{4, 1}, {4, 2}, {4, 4}, {3, 1}, {3, 2}}, [](const WidePlan& c) { return c.nw == 4 || !g_wide_nw4; });
+    return pl.g >= g_wide_min_g ? Fmt::KIND : 0;
   }
-  // 16-bit: from 17 rows and 64 workgroups on (profiles/r05_decode_gemm_wide_rows_ab.txt: against the K-split kernels the 18-row token
-  // +7 %, the 24-row token +11 %, Qwen1.5-1.8B's 96..128-workgroup projections +4 % at 80 rows; the first version -- 3-stage
-  // ring, aligned walks -- had lost to them below 160 workgroups and at 17..32 rows).  At 1..16 rows the K-split kernel keeps the
-  // launches: it carries the fused RMSNorm, and without it the wide kernel is +2 % (Llama) / 0 % (Qwen) there.
-  if (!(g_decode_gemm_wide && MT >= g_wide_min_mt && a.K % 64 == 0 && a.K >= 256 && !a.g)) return 0;
-  pl = nsplit_plan(DgW16::IMGS, MT, a, splits, {{4, 1}, {4, 2}, {4, 4}, {3, 1}, {3, 2}}, [](const WidePlan& c) { return c.nw == 4 || !g_wide_nw4; });
-  return pl.g >= g_wide_min_g ? 1 : 0;
 }
-// ring depth of a planned launch
+// ring depth of a planned launch (the 3-stage A/B ring is a 16-bit mode)
 template <typename Fmt> static int plan_pf(int MT, const WidePlan& pl) {
-  return std::is_same_v<Fmt, DgW16> && pl.nw == 4 && g_wide_pf3 ? 3 : nsplit_pf<Fmt>(MT, pl.r, pl.nw);
+  return Fmt::IMGS == 1 && pl.nw == 4 && g_wide_pf3 ? 3 : nsplit_pf<Fmt>(MT, pl.r, pl.nw);
 }
 
 template <typename Fmt, typename E, int MT, int R, int NW>
 static int launch_nsplit_r(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  if constexpr (std::is_same_v<Fmt, DgW16> && NW == 4) { if (g_wide_pf3) return launch_nsplit<Fmt, E, MT, R, 4, 3>(a, splits, s); }
+  if constexpr (Fmt::IMGS == 1 && NW == 4) { if (g_wide_pf3) return launch_nsplit<Fmt, E, MT, R, 4, 3>(a, splits, s); }
   return launch_nsplit<Fmt, E, MT, R, NW, nsplit_pf<Fmt>(MT, R, NW)>(a, splits, s);
 }
 template <typename Fmt, typename E, int MT>
 static int launch_planned(const WidePlan& pl, const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  if constexpr (std::is_same_v<Fmt, DgW16>) {
+  if constexpr (Fmt::IMGS == 1) {       // the geometries only the 16-bit plan proposes
     if (pl.nw == 3) return pl.r == 2 ? launch_nsplit_r<Fmt, E, MT, 2, 3>(a, splits, s) : launch_nsplit_r<Fmt, E, MT, 1, 3>(a, splits, s);
     if (pl.r == 4) return launch_nsplit_r<Fmt, E, MT, 4, 4>(a, splits, s);
   }
@@ -153,16 +165,13 @@ static int launch_planned(const WidePlan& pl, const DecodeGemmArgs& a, int split
 
 template <typename E, int MT>
 static int launch_decode_gemm(const DecodeGemmArgs& a, int splits, hipStream_t s) {
-  WidePlan pl;
-  switch (const int kind = decode_plan(MT, a, splits, pl)) {
-    case 0: break;
-    case 1: return launch_planned<DgW16, E, MT>(pl, a, splits, s);
-    case 3: return launch_planned<DgW8, E, MT>(pl, a, splits, s);
-    case 4: return launch_planned<DgW4, E, MT>(pl, a, splits, s);
-    case 5: return launch_planned<DgW8F, E, MT>(pl, a, splits, s);
-    case 6: return launch_planned<DgW4I, E, MT>(pl, a, splits, s);
-    default: return kind;
-  }
+  int kind = 0;
+  const int planned = with_format(a.w_flag, [&](auto fmt) -> int {
+    WidePlan pl;
+    kind = decode_plan<decltype(fmt)>(MT, a, splits, pl);
+    return kind > 0 ? launch_planned<decltype(fmt), E, MT>(pl, a, splits, s) : kind;
+  });
+  if (kind != 0 || planned != MXVL_OK) return planned;      // launched, or refused; kind 0: the K-split kernels below
   // R = weight tiles per workgroup.  Two effects, both measured (tools/decode_gemm_bench.py A/B at 18 rows, profiles/r04_decode_gemm_r_sweep.txt):
   // (1) a CU streams ~28 GB/s whatever it holds, so the workgroups must fill whole rounds of the 256 CUs -- 344 workgroups (gate / up
   //     at R = 4: 88 CUs with two, 168 with one) run at 4.7 TB/s, 688 (R = 2) at 5.3, 256 (qkv at R = 3) at 5.2 against 4.3 for 384;
@@ -222,24 +231,35 @@ int decode_gemm_plan(const mxvl_gemv_desc* d, int32_t* out) {
   const int chk = decode_gemm_args(d, a, splits);
   if (chk != MXVL_OK) return chk;
   const int MT = (a.rows + 15) / 16 > 5 ? 5 : (a.rows + 15) / 16;
-  WidePlan pl;
-  const int kind = decode_plan(MT, a, splits, pl);
-  if (kind < 0) return kind;
-  if (kind == 0) pl = WidePlan{0, 0, 0};
-  out[0] = kind; out[1] = pl.nw; out[2] = pl.r; out[4] = (int32_t)pl.g;
-  out[3] = kind == 0 ? 0 : kind == 1 ? plan_pf<DgW16>(MT, pl) : kind == 3 ? plan_pf<DgW8>(MT, pl) : kind == 5 ? plan_pf<DgW8F>(MT, pl) : kind == 6 ? plan_pf<DgW4I>(MT, pl) : plan_pf<DgW4>(MT, pl);
-  return MXVL_OK;
+  return with_format(a.w_flag, [&](auto fmt) -> int {
+    WidePlan pl;
+    const int kind = decode_plan<decltype(fmt)>(MT, a, splits, pl);
+    if (kind < 0) return kind;
+    if (kind == 0) pl = WidePlan{0, 0, 0};
+    out[0] = kind; out[1] = pl.nw; out[2] = pl.r; out[4] = (int32_t)pl.g;
+    out[3] = kind == 0 ? 0 : plan_pf<decltype(fmt)>(MT, pl);
+    return MXVL_OK;
+  });
 }
 
 // argument checks of mxvl_decode_gemv + the kernel-side argument block (nothing is launched here)
 static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& splits) {
-  const int wf = d->dtype & kWeightFlags;
-  if (!decode_dtype_ok(d->dtype & ~kWeightFlags) || (wf & (wf - 1))) return MXVL_ERR_DTYPE;   // one weight format at most
-  const bool w8f = wf == MXVL_W_FP8, w8 = wf == MXVL_W_INT8 || w8f, w4i = wf == MXVL_W_INT4, w4 = wf == MXVL_W_MXFP4 || w4i;   // w_scale / w2_scale exist in the caller's struct only behind these flags
-  if ((w8 || w4) && (!d->w_scale || (d->swiglu && !d->w2_scale))) return MXVL_ERR_NULL;
-  if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
-  if ((w8 || w4) && (d->K % 64 != 0 || d->K < 64 || d->norm_weight || d->out_f32)) return MXVL_ERR_SHAPE;   // no quantised form of these
-  if (w4i && (d->K % 128 != 0 || d->K < 128)) return MXVL_ERR_SHAPE;                                        // whole 128-column groups
+  if (!decode_dtype_ok(d->dtype & ~kWeightFlags)) return MXVL_ERR_DTYPE;
+  a.w_flag = d->dtype & kWeightFlags;
+  a.ws = a.ws2 = nullptr;
+  a.wx = a.wx2 = nullptr;
+  const int chk = with_format(a.w_flag, [&](auto fmt) -> int {      // one weight format at most: two flags are MXVL_ERR_DTYPE
+    using Fmt = decltype(fmt);
+    constexpr bool quantised = Fmt::W_FLAG != 0;                    // w_scale / w2_scale exist in the caller's struct only behind a flag
+    if constexpr (quantised) { if (!d->w_scale || (d->swiglu && !d->w2_scale)) return MXVL_ERR_NULL; }
+    if (d->rows <= 0 || d->rows > 80 || d->K < 32 || d->N <= 0) return MXVL_ERR_SHAPE;
+    if constexpr (quantised) {                                      // whole Fmt::K_MULT columns; no quantised form of the fused norm and the fp32 logits
+      if (d->K % Fmt::K_MULT != 0 || d->K < Fmt::K_MULT || d->norm_weight || d->out_f32) return MXVL_ERR_SHAPE;
+      Fmt::set_scales(a, d->w_scale, d->swiglu ? d->w2_scale : nullptr);
+    }
+    return MXVL_OK;
+  });
+  if (chk != MXVL_OK) return chk;
   if (d->K % 8 != 0) return MXVL_ERR_UNSUPPORTED;                      // 16-byte fragments
   if (d->swiglu && (!d->W2 || d->out_f32)) return MXVL_ERR_UNSUPPORTED;
   // RMSNorm fused into the projection (ABI v8): the LDS-DMA kernel only (K % 64 == 0); elsewhere rows come from mxvl_decode_rmsnorm
@@ -251,12 +271,6 @@ static int decode_gemm_args(const mxvl_gemv_desc* d, DecodeGemmArgs& a, int& spl
   a.split_acc = (float*)d->split_acc;
   a.g = (const uint16_t*)d->norm_weight; a.eps = d->eps;
   a.g_scale = 1.0f; a.g_inv = 1.0f;
-  a.ws = w8 ? (const float*)d->w_scale : nullptr;
-  a.ws2 = (w8 && d->swiglu) ? (const float*)d->w2_scale : nullptr;
-  a.wx = w4 ? (const uint8_t*)d->w_scale : nullptr;
-  a.wx2 = (w4 && d->swiglu) ? (const uint8_t*)d->w2_scale : nullptr;
-  a.w_fp8 = w8f;
-  a.w_int4 = w4i;
   if (d->norm_weight && d->norm_gain_scale != 0.0f) {
     int e = 0;
     const float m = frexpf(d->norm_gain_scale, &e);

@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 
 from ._abi import MXVL_W_FP8
-from .quant_linear import QuantLinear
+from .quant_linear import QuantLinear, dequant_result
 
 E4M3_MAX = 448.0
 
@@ -37,19 +37,14 @@ def quantize_rowwise_fp8(W):
 
 def dequantize_rowwise_fp8(codes, scale, dtype, out=None):
     """dtype(codes.float() * scale), written into `out` (a flat buffer of at least N * K elements of `dtype`) when given."""
-    w = codes.float() * scale.reshape(-1, 1)
-    if out is None:
-        return w.to(dtype)
-    view = out[:codes.numel()].view(codes.shape)
-    view.copy_(w)
-    return view
+    return dequant_result(codes.float() * scale.reshape(-1, 1), dtype, out)
 
 
 class Fp8Linear(QuantLinear):
     """nn.Linear with a frozen row-wise E4M3 weight.  Buffers `weight` (float8_e4m3fn, (N, K)), `weight_scale` (fp32, (N, 1)), optional
     `bias` (activation dtype) -- the state-dict keys of transformers' FbgemmFp8Linear, whose checkpoints load (`input_scale_ub` is
     ignored); a 16-bit or fp32 `weight` in a state dict is quantised on load, codes with a NaN byte are refused."""
-    CODES, SCALES, KIND, W_FLAG, IGNORED_KEYS = "weight", "weight_scale", "fp8 e4m3 row-wise", MXVL_W_FP8, ("input_scale_ub",)
+    NAME, CODES, SCALES, KIND, W_FLAG, IGNORED_KEYS = "fp8", "weight", "weight_scale", "fp8 e4m3 row-wise", MXVL_W_FP8, ("input_scale_ub",)
     quantize, dequantize_into = staticmethod(quantize_rowwise_fp8), staticmethod(dequantize_rowwise_fp8)
 
     @staticmethod
@@ -61,11 +56,3 @@ class Fp8Linear(QuantLinear):
         if w is not None and w.dtype == torch.float8_e4m3fn and bool(((w.view(torch.uint8) & 0x7f) == 0x7f).any()):
             raise ValueError(f"{prefix[:-1] or type(self).__name__}: the E4M3 codes of `weight` hold NaN bytes (0x7f / 0xff)")
         super()._load_from_state_dict(state_dict, prefix, *args)
-
-    def _apply(self, fn, *args, **kwargs):
-        # .to(dtype) / .half() / .float() cast every floating buffer, and here the CODES are floating too: both buffers come through
-        # with their bits (moved to the new device), only the bias follows the activations
-        codes, scales = self.weight, self.weight_scale
-        super()._apply(fn, *args, **kwargs)
-        self.weight, self.weight_scale = codes.to(self.weight.device), scales.to(self.weight_scale.device)
-        return self

@@ -24,7 +24,7 @@ from __future__ import annotations
 import torch
 
 from ._abi import MXVL_W_INT4
-from .quant_linear import QuantLinear
+from .quant_linear import QuantLinear, dequant_result
 
 GROUP = 128
 FP16_MAX = 65504.0
@@ -87,11 +87,7 @@ def dequantize_int4(codes, scales, dtype, out=None):
     N, K = codes.shape[0], codes.shape[1] * 2
     q, z, s = unpack_int4(codes, scales)
     w = ((q - z.repeat_interleave(GROUP, dim=1)).float().reshape(N, K // GROUP, GROUP) * s.float()[:, :, None]).reshape(N, K)
-    if out is None:
-        return w.to(dtype)
-    view = out[:N * K].view(N, K)
-    view.copy_(w)
-    return view
+    return dequant_result(w, dtype, out)
 
 
 def check_gptq_config(qc):
@@ -153,7 +149,7 @@ class Int4GroupLinear(QuantLinear):
     optional `bias` (activation dtype): the state-dict keys.  A GPTQ state dict (`qweight`, `qzeros`, `scales`, optional `g_idx`)
     is repacked on load, read by `gptq_config` (the checkpoint's `quantization_config`; None: format "gptq", 4 bits, group 128);
     a 16-bit `weight` is quantised on load."""
-    CODES, SCALES, KIND, W_FLAG = "qcodes", "qscale_zero", "int4-g128", MXVL_W_INT4
+    NAME, CODES, SCALES, KIND, W_FLAG, K_MULTIPLE = "int4", "qcodes", "qscale_zero", "int4-g128", MXVL_W_INT4, 128
     quantize, dequantize_into = staticmethod(quantize_int4), staticmethod(dequantize_int4)
     gptq_config = None
 

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 
 from ._abi import MXVL_W_INT8
-from .quant_linear import DequantScratch, QuantLinear      # (DequantScratch: re-exported, it used to live here)
+from .quant_linear import DequantScratch, QuantLinear, dequant_result      # (DequantScratch: re-exported, it used to live here)
 
 
 def quantize_rowwise_int8(W):
@@ -29,28 +29,16 @@ def quantize_rowwise_int8(W):
 
 def dequantize_rowwise_int8(cb, scb, dtype, out=None):
     """dtype(CB.float() * (SCB / 127)), written into `out` (a flat buffer of at least N * K elements of `dtype`) when given."""
-    w = cb.float() * (scb / 127.0)[:, None]
-    if out is None:
-        return w.to(dtype)
-    view = out[:cb.numel()].view(cb.shape)
-    view.copy_(w)
-    return view
+    return dequant_result(cb.float() * (scb / 127.0)[:, None], dtype, out)
 
 
 class Int8Linear(QuantLinear):
     """nn.Linear with a frozen row-wise int8 weight.  Buffers `weight` (int8, (N, K)), `SCB` (fp32, (N)), optional `bias` (activation
     dtype) -- the state-dict keys of bitsandbytes' Linear8bitLt, whose checkpoints load (its `weight_format` entry is ignored);
     a 16-bit `weight` in a state dict is quantised on load."""
-    CODES, SCALES, KIND, W_FLAG, IGNORED_KEYS = "weight", "SCB", "int8 row-wise", MXVL_W_INT8, ("weight_format",)
+    NAME, CODES, SCALES, KIND, W_FLAG, IGNORED_KEYS = "int8", "weight", "SCB", "int8 row-wise", MXVL_W_INT8, ("weight_format",)
     quantize, dequantize_into = staticmethod(quantize_rowwise_int8), staticmethod(dequantize_rowwise_int8)
 
     @staticmethod
     def buffers(N, K):
         return ((N, K), torch.int8), ((N,), torch.float32)
-
-    def _apply(self, fn, *args, **kwargs):
-        # .to(dtype) / .half() leave the int8 codes alone but would cast the scales: SCB stays fp32 (only the bias follows the activations)
-        scb = self.SCB
-        super()._apply(fn, *args, **kwargs)
-        self.SCB = scb.to(self.SCB.device)
-        return self

@@ -36,7 +36,9 @@ import torch.nn.functional as F
 from . import checkpoint_compat as compat
 from . import report_metrics
 from .models_mamba import arm_base_pz16, arm_large_pz16
+from .int4_linear import Int4GroupLinear
 from .report_decoder import ReportDecoder
+from .weight_formats import WEIGHT_FORMATS, low_resource_format
 
 LLAMA2_7B = dict(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=32, num_attention_heads=32,
                  num_key_value_heads=32, rms_norm_eps=1e-5, rope_theta=10000.0, max_position_embeddings=4096)
@@ -51,11 +53,12 @@ def _get(args, name, default=None):
 
 def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
-    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: int8 layer projections (quantize_int8_) after loading, "mxfp4": MXFP4 ones (quantize_mxfp4_),
-    "fp8": row-wise E4M3 ones (quantize_fp8_), "int4": group-wise int4 ones (quantize_int4_); every other truthy value is int8.
+    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: the name of a quantised format (WEIGHT_FORMATS) the
+    layer projections are stored in after loading (ReportDecoder.quantize_); every other truthy value is int8 (low_resource_format).
     A checkpoint directory whose config.json carries `quantization_config.quant_method == "gptq"` is loaded AS int4 (prepare_int4_
     swaps the layer projections before the load; the codes are repacked, not re-quantised): low_resource must then be falsy or "int4"."""
     sd = gptq = None
+    fmt = low_resource_format(low_resource)
     if source is None or source == "llama2-7b":
         cfg = dict(LLAMA2_7B)
     elif source == "qwen1.5-1.8b":
@@ -68,7 +71,7 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         cfg = {k: raw[k] for k in _CFG_KEYS if k in raw}
         qc = raw.get("quantization_config") or {}
         if qc.get("quant_method") == "gptq":
-            if low_resource and low_resource != "int4":
+            if fmt not in (None, Int4GroupLinear.NAME):
                 raise ValueError(f"{source}: a GPTQ checkpoint decodes as int4; low_resource={low_resource!r} would need the 16-bit weights it does not hold")
             gptq = qc
         from safetensors.torch import load_file
@@ -87,14 +90,8 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         if "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
             sd["lm_head.weight"] = sd["model.embed_tokens.weight"]          # tied embeddings
         llm.load_hf_state_dict(sd)
-    if low_resource == "mxfp4":
-        llm.quantize_mxfp4_()
-    elif low_resource == "fp8":
-        llm.quantize_fp8_()
-    elif low_resource == "int4":
-        llm.quantize_int4_()                # (a GPTQ checkpoint is int4 already: nothing to do)
-    elif low_resource:
-        llm.quantize_int8_()
+    if fmt is not None and llm.weight_format() is not WEIGHT_FORMATS[fmt]:         # (a GPTQ checkpoint is int4 already: nothing to do)
+        llm.quantize_(fmt)
     return llm
 
 
@@ -171,18 +168,9 @@ class MambaXrayVLDownStream(nn.Module):
                           cross_attn_implementation=_get(args, "cross_attn_implementation", "text-only-vanilla"),
                           cross_attn_gating_type=_get(args, "cross_attn_gating_type", "channel-wise-dynamic-sigmoid"))
         self.llama_model = llm if llm is not None else build_report_decoder(source, **hybrid)
-        low = _get(args, "low_resource", False)
-        if low == "mxfp4":                      # OCP MXFP4 layer projections (mxfp4_linear.py)
-            if not self.llama_model.is_mxfp4():
-                self.llama_model.quantize_mxfp4_()
-        elif low == "fp8":                      # row-wise E4M3 layer projections (fp8_linear.py)
-            if not self.llama_model.is_fp8():
-                self.llama_model.quantize_fp8_()
-        elif low == "int4":                     # group-wise int4 layer projections (int4_linear.py); every other truthy value is the reference's int8
-            if not self.llama_model.is_int4():
-                self.llama_model.quantize_int4_()
-        elif low and not self.llama_model.is_int8():
-            self.llama_model.quantize_int8_()
+        fmt = low_resource_format(_get(args, "low_resource", False))          # a quantised format of the layer projections (WEIGHT_FORMATS), or None
+        if fmt is not None and self.llama_model.weight_format() is not WEIGHT_FORMATS[fmt]:
+            self.llama_model.quantize_(fmt)
         self.llama_tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(_get(args, "llama_model"))
         self.llama_tokenizer.pad_token_id = 0
         if iu:

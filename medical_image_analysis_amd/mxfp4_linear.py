@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 
 from ._abi import MXVL_W_MXFP4
-from .quant_linear import QuantLinear
+from .quant_linear import QuantLinear, dequant_result
 
 BLOCK = 32
 FP16_X_RANGE = (-15, 13)                                        # 0.5 * 2^-15 = fp16's 2^-16 (subnormal, exact) .. 6 * 2^13 = 49152
@@ -57,17 +57,13 @@ def dequantize_mxfp4(packed, scale, dtype, out=None):
     m = code & 7
     mag = torch.where(m < 2, 0.5 * m, torch.ldexp(1.0 + 0.5 * (m & 1), (m >> 1) - 1))
     w = torch.ldexp(torch.where(code >= 8, -mag, mag), (scale.int() - 127)[:, :, None]).reshape(N, K)
-    if out is None:
-        return w.to(dtype)
-    view = out[:N * K].view(N, K)
-    view.copy_(w)
-    return view
+    return dequant_result(w, dtype, out)
 
 
 class MxFp4Linear(QuantLinear):
     """nn.Linear with a frozen MXFP4 weight.  Buffers `weight_packed` (uint8, (N, K / 2)), `weight_scale` (uint8 E8M0, (N, K / 32)),
     optional `bias` (activation dtype): the state-dict keys.  A 16-bit `weight` in a state dict is quantised on load."""
-    CODES, SCALES, KIND, W_FLAG = "weight_packed", "weight_scale", "mxfp4", MXVL_W_MXFP4
+    NAME, CODES, SCALES, KIND, W_FLAG = "mxfp4", "weight_packed", "weight_scale", "mxfp4", MXVL_W_MXFP4
     quantize, dequantize_into = staticmethod(quantize_mxfp4), staticmethod(dequantize_mxfp4)
 
     @staticmethod

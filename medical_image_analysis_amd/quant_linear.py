@@ -1,5 +1,4 @@
-"""What the quantised Linear modules of the frozen report LLM share (int8_linear.Int8Linear, mxfp4_linear.MxFp4Linear, fp8_linear.Fp8Linear,
-int4_linear.Int4GroupLinear): the decode step
+"""What the quantised Linear modules of the frozen report LLM share (the classes of weight_formats.WEIGHT_FORMATS): the decode step
 reads their codes and scales directly (mxvl_decode_gemv with the class's ABI flag); the multi-token paths -- prompt prefill, stage-3
 training through the frozen LLM -- dequantise one weight at a time into a scratch buffer shared by every layer of a decoder and run
 F.linear on it: eager torch on purpose, it runs once per generate / training step and layer, not once per token."""
@@ -31,6 +30,16 @@ class DequantScratch:
         return buf
 
 
+def dequant_result(w, dtype, out=None):
+    """The tail of every dequantiser: the fp32 (N, K) weight `w` as `dtype`, written into the head of `out` (a flat buffer of at least
+    N * K elements of `dtype`) when given."""
+    if out is None:
+        return w.to(dtype)
+    view = out[:w.numel()].view(w.shape)
+    view.copy_(w)
+    return view
+
+
 class _QuantLinearFn(torch.autograd.Function):
     """F.linear on the dequantised weight; saves codes and scales only (never the 16-bit weight), backward re-creates it:
     dx = dy @ Wdq.  The weight gets no gradient."""
@@ -52,13 +61,15 @@ class _QuantLinearFn(torch.autograd.Function):
 class QuantLinear(nn.Module):
     """nn.Linear with a frozen quantised weight.  A subclass declares
         CODES, SCALES       the names of its two buffers (its state-dict keys beside `bias`)
+        NAME                its name in weight_formats.WEIGHT_FORMATS (and as a `low_resource` value)
         W_FLAG              the weight-format bit of mxvl_gemv_desc.dtype its buffers are read with
+        K_MULTIPLE          what the decode kernel of the format needs every in_features to be a multiple of
         KIND                the word of extra_repr
         buffers(N, K)       -> (codes, scales) shapes and dtypes as (shape, dtype) pairs
         quantize(W)         -> (codes, scales);  dequantize_into(codes, scales, dtype, out=None) -> (N, K) weight
     A 16-bit `weight` in a state dict is quantised on load."""
-    CODES = SCALES = KIND = None
-    W_FLAG = 0
+    CODES = SCALES = KIND = NAME = None
+    W_FLAG, K_MULTIPLE = 0, 64
     IGNORED_KEYS = ()               # state-dict entries of a foreign checkpoint format that are dropped on load
 
     def __init__(self, in_features, out_features, bias=False, dtype=torch.float16, device=None, scratch=None):
@@ -89,6 +100,14 @@ class QuantLinear(nn.Module):
         if lin.bias is not None:
             m.bias = lin.bias.detach().clone()
         return m
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to(dtype) / .half() / .float() cast every floating buffer, and scales (fp8: the codes too) are floating: both buffers come
+        # through with their bits (moved to the new device), only the bias follows the activations
+        codes, scales = self.codes, self.scales
+        super()._apply(fn, *args, **kwargs)
+        self.set_quantized(codes.to(self.codes.device), scales.to(self.scales.device))
+        return self
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         local = {k: v for k, v in state_dict.items() if k.startswith(prefix) and k[len(prefix):] not in self.IGNORED_KEYS}

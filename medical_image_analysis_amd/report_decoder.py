@@ -32,10 +32,11 @@ import torch.nn as nn
 from . import _abi
 from .hybrid_decoder_layer import Qwen2HybridDecoderLayer, Qwen2RMSNorm, Qwen2RotaryEmbedding
 from .fp8_linear import Fp8Linear
-from .int4_linear import GROUP as INT4_GROUP, Int4GroupLinear, check_gptq_config
+from .int4_linear import Int4GroupLinear, check_gptq_config
 from .int8_linear import Int8Linear
 from .mxfp4_linear import MxFp4Linear
 from .quant_linear import DequantScratch, QuantLinear
+from .weight_formats import WEIGHT_FORMATS
 
 
 # ---- kv_cache_dtype="fp8": the quantisation contract of the E4M3 KV cache (include/mxvl.h MXVL_KV_FP8), restated with torch ops ----
@@ -624,10 +625,9 @@ class _KernelStepper(_Stepper):
         mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and cfg.hidden_size <= 16384
         fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
             (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
-        if model.weight_format() is not None and (cfg.hidden_size % 64 or cfg.intermediate_size % 64 or (cfg.num_attention_heads * D) % 64):
-            return False         # int8 / mxfp4 / fp8 projections (MXVL_W_INT8, MXVL_W_MXFP4, MXVL_W_FP8): K % 64 == 0 on the one kernel each has
-        if model.weight_format() is Int4GroupLinear and (cfg.hidden_size % INT4_GROUP or cfg.intermediate_size % INT4_GROUP or (cfg.num_attention_heads * D) % INT4_GROUP):
-            return False         # int4 projections (MXVL_W_INT4): whole 128-column groups, K % 128 == 0
+        fmt = model.weight_format()
+        if fmt is not None and any(k % fmt.K_MULTIPLE for k in (cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads * D)):
+            return False         # a quantised format (WEIGHT_FORMATS) has one kernel: every projection width in whole K_MULTIPLE columns
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
                 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0 and fits)
@@ -658,11 +658,10 @@ class _KernelStepper(_Stepper):
         # rows > 8 need the matrix-core projections; below that they are still ~3 % faster per token than the GEMV kernels wherever
         # their LDS-DMA form applies (K % 64 == 0: every real decoder width) -- 5.2-6.2 TB/s against 4.4-5 of the weight stream
         self.batched = rows > 8 or (self.hidden % 64 == 0 and self.inter % 64 == 0 and (self.H * self.D) % 64 == 0)
-        # int8 layer projections (ReportDecoder.quantize_int8_): the matrix-core kernel at every row count, explicit norm launches
-        # ("split" mode) -- there is no int8 form of the fused RMSNorm; lm_head and the embedding stay 16-bit
-        # mxfp4 / fp8 / int4 layer projections (ReportDecoder.quantize_mxfp4_, quantize_fp8_, quantize_int4_) take the same route with
-        # MXVL_W_MXFP4 / MXVL_W_FP8 / MXVL_W_INT4
-        self.wfmt = model.weight_format()                # None, Int8Linear, MxFp4Linear, Fp8Linear or Int4GroupLinear
+        # layer projections in a quantised format (WEIGHT_FORMATS, ReportDecoder.quantize_): the matrix-core kernel at every row count with
+        # the format's W_FLAG, explicit norm launches ("split" mode) -- there is no quantised form of the fused RMSNorm; lm_head and the
+        # embedding stay 16-bit
+        self.wfmt = model.weight_format()                # None or a class of WEIGHT_FORMATS
         self.quantised = self.wfmt is not None
         # rows <= 8: RMSNorm fused into the MFMA projection that consumes the rows (csrc/decode_gemm.h NORM, K % 64 == 0): no
         # mxvl_decode_rmsnorm launches (65 of a token's 229), o_proj / down_proj add their residual in their own epilogue instead of
@@ -796,8 +795,7 @@ class _KernelStepper(_Stepper):
     def _gemv(self, x, W, y, K, N, norm=None, eps=0.0, W2=None, bias=None, res=None, out_f32=False, split=0, scale=None, scale2=None):
         d = _abi.GemvDesc()
         d.rows, d.K, d.N, d.dtype = self.rows, K, N, self.dt
-        if scale is not None:                   # W / W2 are int8 codes + row-wise absmax (SCB), packed E2M1 codes + E8M0 block scales, E4M3 codes + row scales,
-                                                # or packed int4 codes + (fp16 scale | zero point) group words
+        if scale is not None:                   # W / W2 are the codes of a quantised format (WEIGHT_FORMATS), scale / scale2 its scales
             d.dtype |= self.wfmt.W_FLAG
             d.w_scale, d.w2_scale = scale.data_ptr(), _abi.ptr(scale2)
         d.swiglu, d.out_f32, d.eps = int(W2 is not None), int(out_f32), eps
@@ -972,7 +970,7 @@ class ReportDecoder(nn.Module):
                 b = torch.cat([at.q_proj.bias, at.k_proj.bias, at.v_proj.bias], dim=0).contiguous()
                 nq, nk = w0.shape[0], _codes(at.k_proj).shape[0]
                 if isinstance(at.q_proj, QuantLinear):
-                    # int8 / mxfp4 / fp8 / int4: the codes' rows and the per-row (per-block, per-group) scales concatenate exactly; the buffers become views of
+                    # a quantised format (WEIGHT_FORMATS): the codes' rows and the per-row (per-block, per-group) scales concatenate exactly; the buffers become views of
                     # the fused ones (assigned, not .data: the unfused storage is released, no second copy of the bytes)
                     S = torch.cat([lin.scales for lin in qkv], dim=0).contiguous()
                     for lin, lo, hi in ((at.q_proj, 0, nq), (at.k_proj, nq, nq + nk), (at.v_proj, nq + nk, W.shape[0])):
@@ -987,9 +985,58 @@ class ReportDecoder(nn.Module):
     _INT8_TARGETS = (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj")))
 
     def weight_format(self):
-        """None (16-bit), Int8Linear, MxFp4Linear, Fp8Linear or Int4GroupLinear: the class of the layer projections"""
+        """None (16-bit) or a class of WEIGHT_FORMATS: the class of the layer projections"""
         cls = type(self.model.layers[0].mlp.down_proj)
         return cls if issubclass(cls, QuantLinear) else None
+
+    def _refuse_other_format(self, cls):
+        """Formats do not mix on one decoder: a quantised decoder's 16-bit weights are gone, and codes are not re-quantised."""
+        cur = self.weight_format()
+        if cur is not None and cur is not cls:
+            raise RuntimeError(f"quantize_{cls.NAME}_() on an {cur.NAME} decoder: quantise the 16-bit weights, not their {cur.NAME} codes")
+
+    def _swap_projections(self, cls, make):
+        """The one walk over the layer projections: each that is not a `cls` yet becomes make(lin, scratch).  Returns them all."""
+        self._refuse_other_format(cls)
+        scratch, done = DequantScratch(), []
+        for layer in self.model.layers:
+            at = layer.self_attn
+            at.qkv_weight = at.qkv_bias = at.qkv_scale = None           # a fused 16-bit buffer would keep the old bytes alive
+            for owner, names in self._INT8_TARGETS:
+                mod = getattr(layer, owner)
+                for name in names:
+                    lin = getattr(mod, name)
+                    if not isinstance(lin, cls):
+                        lin = make(lin, scratch)
+                        setattr(mod, name, lin)
+                    scratch.reserve(lin.in_features * lin.out_features)        # the buffer is sized once, for the largest weight
+                    done.append(lin)
+        self.__dict__.pop("_steppers", None)                            # captured steps name the old weights
+        self.__dict__.pop("_autocast_shadows", None)
+        return done
+
+    def quantize_(self, fmt):
+        """`low_resource`: q/k/v/o_proj and gate/up/down_proj of every layer become WEIGHT_FORMATS[fmt] modules (the reference's
+        load_in_8bit=True is int8: row-wise absmax, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head
+        (HF's 8-bit loader skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The
+        layers share one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly.  A
+        decoder in another quantised format is refused; what the format itself refuses -- an in_features that is no multiple of its
+        block, an fp16 weight outside its exact range -- raises from its quantiser (<fmt>_linear.py)."""
+        cls = WEIGHT_FORMATS[fmt]
+        self._swap_projections(cls, cls.from_linear)
+        return self
+
+    def quantize_int8_(self):
+        return self.quantize_(Int8Linear.NAME)
+
+    def quantize_mxfp4_(self):
+        return self.quantize_(MxFp4Linear.NAME)
+
+    def quantize_fp8_(self):
+        return self.quantize_(Fp8Linear.NAME)
+
+    def quantize_int4_(self):
+        return self.quantize_(Int4GroupLinear.NAME)
 
     def is_int8(self):
         return self.weight_format() is Int8Linear
@@ -1003,26 +1050,8 @@ class ReportDecoder(nn.Module):
     def is_int4(self):
         return self.weight_format() is Int4GroupLinear
 
-    _FORMAT_NAMES = {Int8Linear: "int8", MxFp4Linear: "mxfp4", Fp8Linear: "fp8", Int4GroupLinear: "int4"}
-
-    def _refuse_other_format(self, cls):
-        """Formats do not mix on one decoder: a quantised decoder's 16-bit weights are gone, and codes are not re-quantised."""
-        cur = self.weight_format()
-        if cur is not None and cur is not cls:
-            new, old = self._FORMAT_NAMES[cls], self._FORMAT_NAMES[cur]
-            raise RuntimeError(f"quantize_{new}_() on an {old} decoder: quantise the 16-bit weights, not their {old} codes")
-
-    def quantize_int4_(self):
-        """`low_resource="int4"`: the projections quantize_int8_ covers become Int4GroupLinear (unsigned 4-bit codes, one fp16 scale and
-        one zero point per 128 along K -- the arithmetic of GPTQ checkpoints, here by plain round-to-nearest; int4_linear.py) and
-        their 16-bit storage is released; the same modules stay 16-bit.  Every in_features must be a multiple of 128.  A decoder in
-        another quantised format is refused: its 16-bit weights are gone."""
-        self._refuse_other_format(Int4GroupLinear)
-        self._quantize_layers(Int4GroupLinear)
-        return self
-
     def prepare_int4_(self, quantization_config=None):
-        """Ahead of loading a GPTQ state dict: the projections quantize_int8_ covers become EMPTY Int4GroupLinear modules (zero codes,
+        """Ahead of loading a GPTQ state dict: the projections quantize_ covers become EMPTY Int4GroupLinear modules (zero codes,
         their 16-bit weights are dropped unread) that repack `qweight` / `qzeros` / `scales` / `g_idx` on load, read by the
         checkpoint's `quantization_config` (checkpoint_format "gptq" when absent; bits != 4, group_size != 128 and desc_act raise a
         ValueError here).  lm_head, the embedding, the norms and the cross-attention projections stay 16-bit, as in the checkpoints."""
@@ -1032,63 +1061,12 @@ class ReportDecoder(nn.Module):
         for owner, names in self._INT8_TARGETS:                         # (before anything is swapped: a width the format refuses raises here)
             for name in names:
                 Int4GroupLinear.buffers(1, getattr(getattr(self.model.layers[0], owner), name).in_features)
-        scratch = DequantScratch()
-        for layer in self.model.layers:
-            at = layer.self_attn
-            at.qkv_weight = at.qkv_bias = at.qkv_scale = None
-            for owner, names in self._INT8_TARGETS:
-                mod = getattr(layer, owner)
-                for name in names:
-                    lin = getattr(mod, name)
-                    if not isinstance(lin, Int4GroupLinear):
-                        w = lin.weight
-                        lin = Int4GroupLinear(lin.in_features, lin.out_features, bias=lin.bias is not None, dtype=w.dtype, device=w.device, scratch=scratch)
-                        setattr(mod, name, lin)
-                    lin.gptq_config = qc
-                    scratch.reserve(lin.in_features * lin.out_features)
-        self.__dict__.pop("_steppers", None)
-        self.__dict__.pop("_autocast_shadows", None)
-        return self
 
-    def quantize_fp8_(self):
-        """`low_resource="fp8"`: the projections quantize_int8_ covers become Fp8Linear (OCP E4M3 codes, one fp32 scale per output
-        row; fp8_linear.py) and their 16-bit storage is released; the same modules stay 16-bit.  The bytes of int8, on the 8-bit
-        format gfx950 converts in one instruction per two codes.  An int8 or mxfp4 decoder is refused: its 16-bit weights are gone."""
-        self._refuse_other_format(Fp8Linear)
-        self._quantize_layers(Fp8Linear)
-        return self
-
-    def quantize_mxfp4_(self):
-        """`low_resource="mxfp4"`: the projections quantize_int8_ covers become MxFp4Linear (OCP MXFP4: E2M1 codes, one E8M0 scale
-        per 32 along K; mxfp4_linear.py) and their 16-bit storage is released; the same modules stay 16-bit.  Every in_features
-        must be a multiple of 32; an fp16 weight outside fp16's exact range raises (quantize_mxfp4).  An int8 or fp8 decoder is
-        refused: its 16-bit weights are gone."""
-        self._refuse_other_format(MxFp4Linear)
-        self._quantize_layers(MxFp4Linear)
-        return self
-
-    def _quantize_layers(self, cls):
-        scratch = DequantScratch()
-        for layer in self.model.layers:
-            at = layer.self_attn
-            at.qkv_weight = at.qkv_bias = at.qkv_scale = None           # a fused 16-bit buffer would keep the old bytes alive
-            for owner, names in self._INT8_TARGETS:
-                mod = getattr(layer, owner)
-                for name in names:
-                    lin = getattr(mod, name)
-                    if not isinstance(lin, cls):
-                        setattr(mod, name, cls.from_linear(lin, scratch))
-                    scratch.reserve(lin.in_features * lin.out_features)        # the buffer is sized once, for the largest weight
-        self.__dict__.pop("_steppers", None)                            # captured steps name the old weights
-        self.__dict__.pop("_autocast_shadows", None)
-
-    def quantize_int8_(self):
-        """The reference's `low_resource` (load_in_8bit=True): q/k/v/o_proj and gate/up/down_proj of every layer become Int8Linear
-        (row-wise absmax int8, bitsandbytes' Int8Params storage) and their 16-bit storage is released; lm_head (HF's 8-bit loader
-        skips it too), embed_tokens, the norms and the hybrid layers' cross-attention projections stay 16-bit.  The layers share
-        one dequantisation scratch buffer for the multi-token paths; the decode step reads the codes directly."""
-        self._refuse_other_format(Int8Linear)
-        self._quantize_layers(Int8Linear)
+        def empty(lin, scratch):
+            w = lin.weight
+            return Int4GroupLinear(lin.in_features, lin.out_features, bias=lin.bias is not None, dtype=w.dtype, device=w.device, scratch=scratch)
+        for lin in self._swap_projections(Int4GroupLinear, empty):
+            lin.gptq_config = qc
         return self
 
     def get_input_embeddings(self):
