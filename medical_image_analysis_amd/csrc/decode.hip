@@ -278,10 +278,10 @@ constexpr int kAttnWaves = 8;    // (16 waves x 8 positions per group -- one tri
 // One workgroup per (head, row), for either cache format KV (decode_elt.h).  A cached K or V line of D elements is read by
 // LPR = D/EPL lanes with one 16-byte load each (EPL = 8 elements of 16 bits, 16 of the E4M3 cache), so a wave covers 64/LPR
 // positions per load and the workgroup NW x 64/LPR; K and V of a position are loaded together and folded into a running
-// (max, sum, out[EPL]) per lane group (one-pass softmax), merged once at the end.  decode_attn_kernel / decode_attn_kv8_kernel
-// are this body over Kv16 / KvE4m3 (p by value: taken by reference, every instantiation compiled ten instructions longer).
+// (max, sum, out[EPL]) per lane group (one-pass softmax), merged once at the end.  KV = Kv16<E> / KvE4m3<E> is a parameter of the
+// kernel itself, as in the beams kernel below.
 template <typename E, typename KV, int D, int NW, int DEPTH>
-__device__ __forceinline__ void decode_attn_body(const AttnArgs p) {
+__global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) {
   typedef typename KV::cache_t cache_t;
   constexpr int EPL = KV::EPL, LPR = D / EPL, RPW = 64 / LPR, NG = NW * RPW;
   static_assert((DEPTH & (DEPTH - 1)) == 0, "ring slots are picked with a mask");
@@ -338,11 +338,10 @@ __device__ __forceinline__ void decode_attn_body(const AttnArgs p) {
     else sq[d] = qr * p.scale;
     if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
     // the new K / V as cache bits, and as the values those bits stand for: a position is seen as the cache holds it from this step on
-    float kval, vval;
-    const uint32_t ck = KV::encode(kr, pow2_recip(sK), kval);
-    sk[d] = kval;
-    const uint32_t cv = KV::encode(E::f(rv), pow2_recip(sV), vval);
-    sv[d] = vval;
+    const uint32_t ck = KV::encode(kr, pow2_recip(sK));
+    sk[d] = KV::value(ck, kr);
+    const uint32_t cv = KV::encode(E::f(rv), pow2_recip(sV));
+    sv[d] = KV::value(cv, E::f(rv));
     if (h % group == 0) {  // one head of the group appends to the cache (slot m owns position pos of beam m)
       const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
       kc[o] = (cache_t)ck;
@@ -435,10 +434,6 @@ __device__ __forceinline__ void decode_attn_body(const AttnArgs p) {
     else p.out[(size_t)m * p.H * D + (size_t)h * D + tid] = E::r(num / den);
   }
 }
-template <typename E, int D, int NW, int DEPTH>
-__global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const AttnArgs p) { decode_attn_body<E, Kv16<E>, D, NW, DEPTH>(p); }
-template <typename E, int D, int NW, int DEPTH>
-__global__ __launch_bounds__(NW * 64) void decode_attn_kv8_kernel(const AttnArgs p) { decode_attn_body<E, KvE4m3<E>, D, NW, DEPTH>(p); }
 
 // The same step for the nb beams of ONE sample in one workgroup (grid: head x sample).  Beams continue a common ancestor: the prompt
 // (whose slots the stepper points at one physical copy) and usually the first generated tokens name the SAME cache lines for every
@@ -462,41 +457,56 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kv8_kernel(const AttnArgs
 // four q (two ds_bpermute).  P is rounded to bf16 before the second product, as the modules' softmax(...).to(bf16) @ V does.
 // A wave owns whole tiles (tile k -> wave k % NW): ns tiles over the positions every beam shares, then nt per beam over its own
 // positions (only column `beam` of those is kept).  K and V tiles arrive by LDS-DMA into a two-stage ring per wave, XOR-swizzled
-// on the SOURCE address (the DMA writes LDS linearly) so that both the 16-byte fragment reads and the transpose reads spread over
-// the banks; explicit vmcnt waits (the compiler cannot see the DMA).  The fresh position of every beam (its K / V are in LDS, not
-// in the cache yet for the other heads of a KV group) is one more partial in the final merge.
-template <int D> __device__ __forceinline__ int attn_tile_key(int row) {
-  constexpr int UPR = D / 8;
-  return UPR == 8 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)) : UPR == 16 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (row & (UPR - 1));
-}
-template <int D> __device__ __forceinline__ int attn_tile_off(int row, int unit) { return row * (D * 2) + ((unit ^ attn_tile_key<D>(row)) << 4); }
-
-template <typename E, int D, int NB, int NW>
+// on the SOURCE address (the DMA writes LDS linearly) so that the fragment reads spread over the banks; explicit vmcnt waits (the
+// compiler cannot see the DMA).  The fresh position of every beam (its K / V are in LDS, not in the cache yet for the other heads
+// of a KV group) is one more partial in the final merge.
+// One kernel for both cache formats KV (decode_elt.h); a tile is 16 positions x D elements:
+//   Kv16     rows of 2 D bytes.  K: one 16-byte read per lane and kk; V^T: ds_read_b64_tr_b16.  The swizzle key (KV::tile_key) spreads
+//            both the 16-byte fragment reads and the transpose reads over the banks.
+//   KvE4m3   rows of D bytes, one power-of-two scale per tensor: half the DMA instructions and half the LDS.  Both products stay on
+//            the 16-bit matrix cores, P rounded to 16 bits: a fragment becomes 16-bit elements AFTER its LDS read (a code's value is
+//            exact in bf16 and fp16, so the MFMA operands are plain code values; the scales enter as in the per-row kernel).
+//              K: lane (pos = l16, q4) reads the 8 bytes K[pos][32 kk + 8 q4 .. + 8) with one ds_read_b64 and widens them to an A operand;
+//              V: lane (d = 16 dt + l16, q4) reads the four bytes V[4 q4 .. 4 q4 + 3][d] one by one (DESIGN.md 4.7 on the 8-bit transpose read).
+//            Rows D bytes apart share banks every 256 / D rows; XOR-ing the unit index with (row >> 2) & 3 (D = 64) / (row >> 1) & 7
+//            (D = 128) spreads the 16 rows of a K read over all 64 banks twice (the minimum for 512 bytes) and gives the four rows of a
+//            V byte read (4 q4 + i) four different units.
+// KV is a parameter of the __global__ function itself: behind a __forceinline__ body and per-format wrappers hipcc compiled the 16-bit
+// instantiations differently and serialised the slot sweep's waits again.
+template <typename E, typename KV, int D, int NB, int NW>
 __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const AttnArgs p) {
   typedef short s16x4 __attribute__((ext_vector_type(4)));
   typedef elt_u32x4 bf16x8;      // eight 16-bit elements of a lane (E decides what they mean)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
-  constexpr int UPR = D / 8, RPI = 64 / UPR;     // 16-byte units per cache row; rows per DMA instruction (1 KB)
-  constexpr int TILE = 16, NI = TILE / RPI;      // positions per tile; DMA instructions per K (or V) tile
-  constexpr int TB = TILE * D * 2, STAGE = 2 * TB, NST = 2, OPS = 2 * NI;
+  typedef typename KV::cache_t cache_t;
+  static_assert(!KV::scaled || D == 64 || D == 128, "the fp8 cache serves head_dim 64 and 128");
+  constexpr int EB = sizeof(cache_t);                 // bytes per cache element
+  constexpr int UPR = D * EB / 16, RPI = 64 / UPR;    // 16-byte units per cache row; rows per DMA instruction (1 KB)
+  constexpr int TILE = 16, NI = TILE / RPI;           // positions per tile; DMA instructions per K (or V) tile
+  constexpr int TB = TILE * D * EB, STAGE = 2 * TB, NST = 2, OPS = 2 * NI;
   constexpr int NKK = D / 32, NDT = D / 16, NT = NW * 64, NWP = NW + 1;
   static_assert(OPS <= 31, "vmcnt immediate");
+  static_assert(NW * NST * STAGE >= NB * NWP * D * 4, "wo reuses the ring");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int T = p.max_len;
   char* ring_all = (char*)sm;                                   // [NW][NST][K tile | V tile]; after the loop: wo [NB][NWP][D] fp32
-  uint16_t* sqb = (uint16_t*)(ring_all + NW * NST * STAGE);     // [16][D] rotated queries, bf16 (rows nb .. 15 zero)
-  float* sq = (float*)(sqb + 16 * D);                           // [NB][D] rotated, scaled queries (fresh position)
-  float* sk = sq + NB * D;                                      // [NB][D] rotated new keys
-  float* sv = sk + NB * D;                                      // [NB][D] new values
+  uint16_t* sqb = (uint16_t*)(ring_all + NW * NST * STAGE);     // [16][D] rotated queries, 16-bit (rows nb .. 15 zero)
+  float* sq = (float*)(sqb + 16 * D);                           // [NB][D] rotated queries x softmax scale (x K scale) (fresh position)
+  float* sk = sq + NB * D;                                      // [NB][D] rotated new keys, as the values of their cache bits
+  float* sv = sk + NB * D;                                      // [NB][D] new values, as the values of their cache bits
   float* wm = sv + NB * D;                                      // [NB][NWP] partial maxima
   float* wl = wm + NB * NWP;                                    // [NB][NWP] partial sums
   int* ssl = (int*)(wl + NB * NWP);                             // [NB][T] slot of each position, -1 = masked
   float* wo = (float*)ring_all;
   __shared__ int s_nsh;
+  cache_t* const kc = (cache_t*)p.kc;
+  cache_t* const vc = (cache_t*)p.vc;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = blockIdx.x, m0 = blockIdx.y * NB;
   const int group = p.H / p.Hkv, hk = h / group;
   const int pos = (int)*p.pos;         // (first USED behind the loads below: the scalar load overlaps them)
+  float sK = 1.0f, sV = 1.0f;
+  if constexpr (KV::scaled) { sK = p.kvs[0]; sV = p.kvs[1]; }
   // raw RoPE operands of this thread's (row, dim) items: unconditional loads (clamped index), consumed after the slot sweep
   constexpr int RI = (NB * D + NT - 1) / NT;
   uint16_t rope_q[RI], rope_qo[RI], rope_k[RI], rope_ko[RI], rope_v[RI];
@@ -553,7 +563,8 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
     const unsigned long long differ = __ballot(!same && t < pos);
     if (differ != 0 && lane == __ffsll(differ) - 1) atomicMin(&s_nsh, t);
   }
-  // RoPE (hybrid_decoder_layer.py:284-322) of the nb rows' q / k, cache append by one head of each KV group
+  // RoPE (hybrid_decoder_layer.py:284-322) of the nb rows' q / k, the new K / V as cache bits, cache append by one head of each KV group
+  const float rK = pow2_recip(sK), rV = pow2_recip(sV);
 #pragma unroll
   for (int it = 0; it < RI; ++it) {
     const int i = tid + it * NT;
@@ -564,15 +575,19 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
       const float kd = E::f(rope_k[it]), ko = d < half ? -E::f(rope_ko[it]) : E::f(rope_ko[it]);
       const float qr = E::rr(E::rr(qd * c) + E::rr(qo * sn));
       const float kr = E::rr(E::rr(kd * c) + E::rr(ko * sn));
-      sq[i] = qr * p.scale;
+      const uint32_t ck = KV::encode(kr, rK);
+      uint32_t cv = rope_v[it];                              // a 16-bit V is copied as it is
+      if constexpr (KV::scaled) cv = KV::encode(E::f(rope_v[it]), rV);
+      if constexpr (KV::scaled) sq[i] = qr * p.scale * sK;   // the K scale rides on the query
+      else sq[i] = qr * p.scale;
       sqb[i] = E::r(qr);
       if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
-      sk[i] = kr;
-      sv[i] = E::f(rope_v[it]);
+      sk[i] = KV::value(ck, kr);
+      sv[i] = KV::value(cv, E::f(rope_v[it]));
       if (h % group == 0) {
         const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
-        p.kc[o] = E::r(kr);
-        p.vc[o] = rope_v[it];
+        kc[o] = (cache_t)ck;
+        vc[o] = (cache_t)cv;
       }
     }
   }
@@ -610,11 +625,11 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
       const bool in = t < lim;
       const int sl = sp[in ? t : 0];
       const bool live = in && sl >= 0;
-      const uint32_t off = (live ? (uint32_t)sl * c1 + (uint32_t)t * D + hk_off : dummy) + (((lane % UPR) ^ attn_tile_key<D>(row)) << 3);
+      const uint32_t off = (live ? (uint32_t)sl * c1 + (uint32_t)t * D + hk_off : dummy) + (((lane % UPR) ^ KV::template tile_key<D>(row)) * KV::EPL);
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
                    "s_add_u32 m0, m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(dst + ii * 1024), "v"(p.kc + off), "v"(p.vc + off), "n"(TB) : "memory", "scc");
+                   : "=&s"(keep) : "s"(dst + ii * 1024), "v"(kc + off), "v"(vc + off), "n"(TB) : "memory", "scc");
     }
   };
   // B operand of the first product: lane (beam = l16, q4) owns Q[beam][32 kk + 8 q4 .. + 8)
@@ -625,6 +640,8 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   float m_run = -1e30f, l_run = 0.0f;            // this lane's beam column; l_run sums this lane's four rows only until the end
+  float sscale = p.scale;
+  if constexpr (KV::scaled) sscale *= sK;
   Tile ti, tc;
   tile_first(ti);
   tc = ti;
@@ -639,289 +656,27 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_mfma_kernel(const A
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const char* kt = ring + stage * STAGE;
     const char* vt = kt + TB;
-    typedef __attribute__((address_space(3))) s16x4 lds4;
-    bf16x8 kf[NKK];
-    s16x4 vf[NDT];
+    typename KV::kraw_t kraw[NKK];
+    typename KV::vraw_t vraw[NDT];
+    if constexpr (!KV::scaled) {
+      typedef __attribute__((address_space(3))) s16x4 lds4;
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) kf[kk] = *(const bf16x8*)(kt + attn_tile_off<D>(l16, kk * 4 + q4));
-    // V^T: within a 16-lane group lane t' supplies the address of row (t' >> 2), columns 4 (t' & 3) .. + 3 of a [4][16] block and
-    // receives column t' of its 4 rows -> lane (d = 16 dt + l16, q4) gets V[4 q4 .. 4 q4 + 3][d]
+      for (int kk = 0; kk < NKK; ++kk) kraw[kk] = *(const bf16x8*)(kt + kv_tile_off<KV, D>(l16, kk * 4 + q4));
+      // V^T: within a 16-lane group lane t' supplies the address of row (t' >> 2), columns 4 (t' & 3) .. + 3 of a [4][16] block and
+      // receives column t' of its 4 rows -> lane (d = 16 dt + l16, q4) gets V[4 q4 .. 4 q4 + 3][d]
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      const int col = dt * 16 + 4 * (l16 & 3);
-      vf[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(vt + attn_tile_off<D>(q4 * 4 + (l16 >> 2), col >> 3) + (col & 7) * 2));
-    }
-    const int t0 = tc.r < 0 ? tc.k * TILE : nsh + tc.i * TILE, lim = tc.r < 0 ? nsh : pos;
-    const int* sp = ssl + (tc.r < 0 ? 0 : tc.r) * T;
-    bool ok[4];
-    const bool colok = l16 < NB && (tc.r < 0 || l16 == tc.r);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int t = t0 + q4 * 4 + i;
-      ok[i] = colok && t < lim && sp[t < lim ? t : 0] >= 0;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every fragment of the stage is in registers: it may be refilled
-    issue(ti, stage);
-    tile_next(ti);
-    f32x4 sc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) sc = E::mfma32(kf[kk], qb[kk], sc);
-    float s[4], tmax = -1e30f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      s[i] = sc[i] * p.scale;
-      tmax = ok[i] ? fmaxf(tmax, s[i]) : tmax;
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mn = fmaxf(m_run, tmax), corr = fast_exp(m_run - mn);
-    m_run = mn;
-    float pr[4], psum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      pr[i] = ok[i] ? fast_exp(s[i] - mn) : 0.0f;
-      psum += pr[i];
-    }
-    l_run = fmaf(l_run, corr, psum);
-    s16x4 pb;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pb[i] = (short)E::r(pr[i]);
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) oacc[dt][i] *= corr;
-      oacc[dt] = E::mfma16(vf[dt], pb, oacc[dt]);
-    }
-  }
-  if (MXVL_ABL(p.ablate == 3)) return;      // + every cached position
-  // ---- merge: the q-lanes of a column by shuffles, the waves (+ the fresh position as partial NW) through LDS ----------------------
-  l_run += __shfl_xor(l_run, 16, 64);
-  l_run += __shfl_xor(l_run, 32, 64);
-  __syncthreads();                          // every wave is done with its ring: wo reuses the memory
-  if (l16 < NB) {
-    if (q4 == 0) { wm[l16 * NWP + wave] = m_run; wl[l16 * NWP + wave] = l_run; }
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-      *(f32x4*)(wo + (l16 * NWP + wave) * D + dt * 16 + q4 * 4) = oacc[dt];
-  }
-  for (int r = wave; r < NB; r += NW) {     // the fresh position of beam r: score by one wave
-    float part = 0.0f;
-    for (int d = lane; d < D; d += 64) part = fmaf(sq[r * D + d], sk[r * D + d], part);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-    const bool live = ssl[r * T + pos] >= 0;
-    if (lane == 0) { wm[r * NWP + NW] = live ? part : -1e30f; wl[r * NWP + NW] = live ? 1.0f : 0.0f; }
-    for (int d = lane; d < D; d += 64) wo[(r * NWP + NW) * D + d] = live ? sv[r * D + d] : 0.0f;
-  }
-  __syncthreads();
-  for (int i = tid; i < NB * D; i += NT) {
-    const int r = i / D, d = i - r * D;
-    float gmax = -1e30f;
-#pragma unroll
-    for (int w = 0; w < NWP; ++w) gmax = fmaxf(gmax, wm[r * NWP + w]);
-    float num = 0.0f, den = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NWP; ++w) {
-      const float c = fast_exp(wm[r * NWP + w] - gmax);
-      num = fmaf(c, wo[(r * NWP + w) * D + d], num);
-      den = fmaf(c, wl[r * NWP + w], den);
-    }
-    p.out[(size_t)(m0 + r) * p.H * D + (size_t)h * D + d] = E::r(num / den);
-  }
-}
-
-// decode_attn_beams_mfma_kernel over the E4M3 cache (bytes, one power-of-two scale per tensor: KvE4m3 in decode_elt.h): shared positions read once, both
-// products on the 16-bit matrix cores (16x16x32 for K Q^T, 16x16x16 for V^T P), P rounded to 16 bits.  A tile is 16 positions x D
-// bytes -- half the DMA instructions and half the LDS of the twin -- and a fragment becomes 16-bit elements AFTER its LDS read (a
-// code's value is exact in bf16 and fp16, so the MFMA operands are plain code values; the scales enter as in the per-row kernel).
-//   K: lane (pos = l16, q4) reads the 8 bytes K[pos][32 kk + 8 q4 .. + 8) with one ds_read_b64 and widens them to an A operand;
-//   V: lane (d = 16 dt + l16, q4) reads the four bytes V[4 q4 .. 4 q4 + 3][d] one by one (DESIGN.md 4.7 on the 8-bit transpose read).
-// The DMA writes LDS linearly, so the swizzle is on the source address, per 16-byte unit: rows D bytes apart share banks every
-// 256 / D rows; XOR-ing the unit index with (row >> 2) & 3 (D = 64) / (row >> 1) & 7 (D = 128) spreads the 16 rows of a K read over
-// all 64 banks twice (the minimum for 512 bytes) and gives the four rows of a V byte read (4 q4 + i) four different units.
-template <int D> __device__ __forceinline__ int attn_tile8_key(int row) { return D == 64 ? ((row >> 2) & 3) : ((row >> 1) & 7); }
-template <int D> __device__ __forceinline__ int attn_tile8_off(int row, int unit) { return row * D + ((unit ^ attn_tile8_key<D>(row)) << 4); }
-
-template <typename E, int D, int NB, int NW>
-__global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const AttnArgs p) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef elt_u32x4 bf16x8;      // eight 16-bit elements of a lane (E decides what they mean)
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  static_assert(D == 64 || D == 128, "the fp8 cache serves head_dim 64 and 128");
-  constexpr int UPR = D / 16, RPI = 64 / UPR;    // 16-byte units per cache row; rows per DMA instruction (1 KB)
-  constexpr int TILE = 16, NI = TILE / RPI;      // positions per tile; DMA instructions per K (or V) tile
-  constexpr int TB = TILE * D, STAGE = 2 * TB, NST = 2, OPS = 2 * NI;
-  constexpr int NKK = D / 32, NDT = D / 16, NT = NW * 64, NWP = NW + 1;
-  static_assert(NW * NST * STAGE >= NB * NWP * D * 4, "wo reuses the ring");
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = p.max_len;
-  char* ring_all = (char*)sm;                                   // [NW][NST][K tile | V tile]; after the loop: wo [NB][NWP][D] fp32
-  uint16_t* sqb = (uint16_t*)(ring_all + NW * NST * STAGE);     // [16][D] rotated queries, 16-bit (rows nb .. 15 zero)
-  float* sq = (float*)(sqb + 16 * D);                           // [NB][D] rotated queries x softmax scale x K scale (fresh position)
-  float* sk = sq + NB * D;                                      // [NB][D] rotated new keys, as the values of their codes
-  float* sv = sk + NB * D;                                      // [NB][D] new values, as the values of their codes
-  float* wm = sv + NB * D;                                      // [NB][NWP] partial maxima
-  float* wl = wm + NB * NWP;                                    // [NB][NWP] partial sums
-  int* ssl = (int*)(wl + NB * NWP);                             // [NB][T] slot of each position, -1 = masked
-  float* wo = (float*)ring_all;
-  __shared__ int s_nsh;
-  uint8_t* const kc8 = (uint8_t*)p.kc;
-  uint8_t* const vc8 = (uint8_t*)p.vc;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = blockIdx.x, m0 = blockIdx.y * NB;
-  const int group = p.H / p.Hkv, hk = h / group;
-  const int pos = (int)*p.pos;
-  const float sK = p.kvs[0], sV = p.kvs[1];
-  constexpr int RI = (NB * D + NT - 1) / NT;
-  uint16_t rope_q[RI], rope_qo[RI], rope_k[RI], rope_ko[RI], rope_v[RI];
-  float rope_c[RI], rope_s[RI];
-#pragma unroll
-  for (int it = 0; it < RI; ++it) {
-    const int i = tid + it * NT < NB * D ? tid + it * NT : 0;
-    const int r = i / D, d = i - r * D, half = D / 2, m = m0 + r;
-    const int dp = d < half ? d + half : d - half;
-    const size_t row = (size_t)m * (p.H + 2 * p.Hkv) * D;
-    const uint16_t* q = p.qkv + row + (size_t)h * D;
-    const uint16_t* kn = p.qkv + row + (size_t)(p.H + hk) * D;
-    const uint16_t* vn = p.qkv + row + (size_t)(p.H + p.Hkv + hk) * D;
-    rope_q[it] = q[d]; rope_qo[it] = q[dp]; rope_k[it] = kn[d]; rope_ko[it] = kn[dp]; rope_v[it] = vn[d];
-    rope_c[it] = p.cosv[(size_t)m * D + d]; rope_s[it] = p.sinv[(size_t)m * D + d];
-  }
-  int64_t mk0[NB];
-  int sl0[NB];
-  {
-    const int t = tid < T ? tid : T - 1;
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-      mk0[r] = p.mask[(size_t)(m0 + r) * T + t];
-      sl0[r] = p.slot[(size_t)(m0 + r) * T + t];
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  for (int i = tid; i < (16 - NB) * D; i += NT) sqb[NB * D + i] = 0;
-  if (tid == 0) s_nsh = pos;
-  __syncthreads();
-  for (int t = tid; t <= pos; t += NT) {
-    int64_t mk[NB];
-    int sl[NB];
-    if (t == tid) {
-#pragma unroll
-      for (int r = 0; r < NB; ++r) { mk[r] = mk0[r]; sl[r] = sl0[r]; }
+      for (int dt = 0; dt < NDT; ++dt) {
+        const int col = dt * 16 + 4 * (l16 & 3);
+        vraw[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(vt + kv_tile_off<KV, D>(q4 * 4 + (l16 >> 2), col >> 3) + (col & 7) * 2));
+      }
     } else {
 #pragma unroll
-      for (int r = 0; r < NB; ++r) {
-        mk[r] = p.mask[(size_t)(m0 + r) * T + t];
-        sl[r] = p.slot[(size_t)(m0 + r) * T + t];
-      }
+      for (int kk = 0; kk < NKK; ++kk) kraw[kk] = *(const uint2*)(kt + kv_tile_off<KV, D>(l16, kk * 2 + (q4 >> 1)) + (q4 & 1) * 8);
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vraw[dt].b[i] = ((const uint8_t*)vt)[kv_tile_off<KV, D>(q4 * 4 + i, dt) + l16];
     }
-    __builtin_amdgcn_sched_barrier(0);
-    bool same = true;
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-      const int v = mk[r] != 0 ? sl[r] : -1;
-      ssl[r * T + t] = v;
-      same = same && v == (mk[0] != 0 ? sl[0] : -1);
-    }
-    const unsigned long long differ = __ballot(!same && t < pos);
-    if (differ != 0 && lane == __ffsll(differ) - 1) atomicMin(&s_nsh, t);
-  }
-  // RoPE of the nb rows' q / k, encode, cache append by one head of each KV group
-  const float rK = pow2_recip(sK), rV = pow2_recip(sV);
-#pragma unroll
-  for (int it = 0; it < RI; ++it) {
-    const int i = tid + it * NT;
-    if (i < NB * D) {
-      const int r = i / D, d = i - r * D, half = D / 2, m = m0 + r;
-      const float c = E::rr(rope_c[it]), sn = E::rr(rope_s[it]);
-      const float qd = E::f(rope_q[it]), qo = d < half ? -E::f(rope_qo[it]) : E::f(rope_qo[it]);
-      const float kd = E::f(rope_k[it]), ko = d < half ? -E::f(rope_ko[it]) : E::f(rope_ko[it]);
-      const float qr = E::rr(E::rr(qd * c) + E::rr(qo * sn));
-      const float kr = E::rr(E::rr(kd * c) + E::rr(ko * sn));
-      const uint32_t ck = e4m3_encode(kr * rK), cv = e4m3_encode(E::f(rope_v[it]) * rV);
-      sq[i] = qr * p.scale * sK;
-      sqb[i] = E::r(qr);
-      if (p.q_rope) p.q_rope[(size_t)m * p.H * D + (size_t)h * D + d] = E::r(qr);
-      sk[i] = e4m3_decode(ck);
-      sv[i] = e4m3_decode(cv);
-      if (h % group == 0) {
-        const size_t o = (((size_t)m * p.Hkv + hk) * T + pos) * D + d;
-        kc8[o] = (uint8_t)ck;
-        vc8[o] = (uint8_t)cv;
-      }
-    }
-  }
-  __syncthreads();
-  if (MXVL_ABL(p.ablate == 1)) return;      // launch + slot sweep + RoPE + cache append
-  const int nsh = s_nsh;
-  const int l16 = lane & 15, q4 = lane >> 4;
-  const int ns = (nsh + TILE - 1) / TILE, nt = (pos - nsh + TILE - 1) / TILE, ntiles = ns + NB * nt;
-  // tile iterators (wave-uniform): tile k of this wave -> shared (r < 0) tile k, or tile i of beam r
-  struct Tile { int k, r, i; };
-  auto tile_first = [&](Tile& it) {
-    it.k = wave; it.r = -1; it.i = 0;
-    if (it.k >= ns && it.k < ntiles) { it.r = 0; it.i = it.k - ns; while (it.i >= nt) { it.i -= nt; ++it.r; } }
-  };
-  auto tile_next = [&](Tile& it) {
-    it.k += NW;
-    if (it.k >= ns && it.k < ntiles) {
-      if (it.r < 0) { it.r = 0; it.i = it.k - ns; } else it.i += NW;
-      while (it.i >= nt) { it.i -= nt; ++it.r; }
-    }
-  };
-  char* ring = ring_all + wave * (NST * STAGE);
-  const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
-  const uint32_t c1 = (uint32_t)p.Hkv * (uint32_t)T * D;                    // bytes per cache row (slot); 32-bit offsets: the launcher checks the cache fits
-  const uint32_t hk_off = (uint32_t)hk * (uint32_t)T * D;
-  const uint32_t dummy = (uint32_t)m0 * c1 + hk_off;                        // a masked / out-of-range row re-reads the sample's first line
-  auto issue = [&](const Tile& it, int stage) {
-    if (it.k >= ntiles) return;
-    const int t0 = it.r < 0 ? it.k * TILE : nsh + it.i * TILE, lim = it.r < 0 ? nsh : pos;
-    const int* sp = ssl + (it.r < 0 ? 0 : it.r) * T;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)stage * STAGE);
-#pragma unroll
-    for (int ii = 0; ii < NI; ++ii) {
-      const int row = ii * RPI + lane / UPR, t = t0 + row;
-      const bool in = t < lim;
-      const int sl = sp[in ? t : 0];
-      const bool live = in && sl >= 0;
-      const uint32_t off = (live ? (uint32_t)sl * c1 + (uint32_t)t * D + hk_off : dummy) + (((lane % UPR) ^ attn_tile8_key<D>(row)) << 4);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                   "s_add_u32 m0, m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "s"(dst + ii * 1024), "v"(kc8 + off), "v"(vc8 + off), "n"(TB) : "memory", "scc");
-    }
-  };
-  // B operand of the first product: lane (beam = l16, q4) owns Q[beam][32 kk + 8 q4 .. + 8)
-  bf16x8 qb[NKK];
-#pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) qb[kk] = *(const bf16x8*)(sqb + l16 * D + kk * 32 + q4 * 8);
-  f32x4 oacc[NDT];
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  float m_run = -1e30f, l_run = 0.0f;            // this lane's beam column; l_run sums this lane's four rows only until the end
-  const float sscale = p.scale * sK;
-  Tile ti, tc;
-  tile_first(ti);
-  tc = ti;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the counts below are counts of ring tiles only
-  issue(ti, 0);
-  tile_next(ti);
-  issue(ti, 1);
-  tile_next(ti);
-  int stage = 0;
-  for (; tc.k < ntiles; tile_next(tc), stage ^= 1) {
-    if (tc.k + NW < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const char* kt = ring + stage * STAGE;
-    const uint8_t* vt = (const uint8_t*)kt + TB;
-    uint2 kraw[NKK];
-    uint32_t vraw[NDT][4];
-#pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) kraw[kk] = *(const uint2*)(kt + attn_tile8_off<D>(l16, kk * 2 + (q4 >> 1)) + (q4 & 1) * 8);
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) vraw[dt][i] = vt[attn_tile8_off<D>(q4 * 4 + i, dt) + l16];
     const int t0 = tc.r < 0 ? tc.k * TILE : nsh + tc.i * TILE, lim = tc.r < 0 ? nsh : pos;
     const int* sp = ssl + (tc.r < 0 ? 0 : tc.r) * T;
     bool ok[4];
@@ -936,7 +691,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
     tile_next(ti);
     f32x4 sc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) sc = E::mfma32(e4m3_unpack8_elt<E>(kraw[kk].x, kraw[kk].y), qb[kk], sc);
+    for (int kk = 0; kk < NKK; ++kk) sc = E::mfma32(KV::k_operand(kraw[kk]), qb[kk], sc);
     float s[4], tmax = -1e30f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -962,7 +717,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
       s16x4 vf;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        vf[i] = (short)e4m3_elt_bits<E>(e4m3_decode(vraw[dt][i]));
+        vf[i] = KV::v_operand(vraw[dt], i);
         oacc[dt][i] *= corr;
       }
       oacc[dt] = E::mfma16(vf, pb, oacc[dt]);
@@ -1001,7 +756,8 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_beams_kv8_kernel(const At
       num = fmaf(c, wo[(r * NWP + w) * D + d], num);
       den = fmaf(c, wl[r * NWP + w], den);
     }
-    p.out[(size_t)(m0 + r) * p.H * D + (size_t)h * D + d] = E::r(num / den * sV);
+    if constexpr (KV::scaled) p.out[(size_t)(m0 + r) * p.H * D + (size_t)h * D + d] = E::r(num / den * sV);   // the V scale rides on the output
+    else p.out[(size_t)(m0 + r) * p.H * D + (size_t)h * D + d] = E::r(num / den);
   }
 }
 
@@ -1185,18 +941,6 @@ static int launch_gemv_rows(const GemvArgs& a, hipStream_t s) {
   }
 }
 
-// the __global__ wrapper of a kernel body for the cache format KV
-template <typename E, typename KV, int D, int NW, int DEPTH>
-static constexpr auto attn_row_kernel() {
-  if constexpr (KV::scaled) return &decode_attn_kv8_kernel<E, D, NW, DEPTH>;
-  else return &decode_attn_kernel<E, D, NW, DEPTH>;
-}
-template <typename E, typename KV, int D, int NB, int NW>
-static constexpr auto attn_beams_kernel() {
-  if constexpr (KV::scaled) return &decode_attn_beams_kv8_kernel<E, D, NB, NW>;
-  else return &decode_attn_beams_mfma_kernel<E, D, NB, NW>;
-}
-
 // per call: the dynamic-LDS attribute belongs to the (kernel, device) pair, and a process may drive several devices
 static int launch_attn(void (*kern)(const AttnArgs), dim3 grid, dim3 block, size_t lds, hipStream_t s, const AttnArgs& a) {
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
@@ -1227,7 +971,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
     const dim3 grid(a.H, a.rows / nb), block(nw * 64);
 #define MXVL_ATTN_BEAMS(DD, NB) \
-  return launch_attn(nw == 8 ? attn_beams_kernel<E, KV, DD, NB, (DD <= 128 ? 8 : 4)>() : attn_beams_kernel<E, KV, DD, NB, 4>(), grid, block, lds, s, a)
+  return launch_attn(nw == 8 ? decode_attn_beams_mfma_kernel<E, KV, DD, NB, (DD <= 128 ? 8 : 4)> : decode_attn_beams_mfma_kernel<E, KV, DD, NB, 4>, grid, block, lds, s, a)
 #define MXVL_ATTN_BEAMS_D(NB) \
   switch (a.D) { \
     case 64: MXVL_ATTN_BEAMS(64, NB); \
@@ -1258,8 +1002,8 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
   const dim3 grid(a.H, a.rows), block(nw * 64);
 #define MXVL_ATTN_ROW(DD) \
   do { \
-    void (*kern)(const AttnArgs) = depth == 4 ? attn_row_kernel<E, KV, DD, 8, 4>() : attn_row_kernel<E, KV, DD, 8, 2>(); \
-    if constexpr (kv16) if (nw == 16) kern = depth == 4 ? decode_attn_kernel<E, DD, 16, 4> : decode_attn_kernel<E, DD, 16, 2>; \
+    void (*kern)(const AttnArgs) = depth == 4 ? decode_attn_kernel<E, KV, DD, 8, 4> : decode_attn_kernel<E, KV, DD, 8, 2>; \
+    if constexpr (kv16) if (nw == 16) kern = depth == 4 ? decode_attn_kernel<E, KV, DD, 16, 4> : decode_attn_kernel<E, KV, DD, 16, 2>; \
     return launch_attn(kern, grid, block, lds, s, a); \
   } while (0)
   switch (a.D) {

@@ -110,34 +110,57 @@ template <typename E> __device__ inline elt_u32x4 e4m3_unpack8_elt(uint32_t w0, 
 // 1 / s of a power-of-two scale s (a normal fp32): exact, no divide
 __device__ inline float pow2_recip(float s) { return __builtin_bit_cast(float, 0x7f000000u - __builtin_bit_cast(uint32_t, s)); }
 
-// ---- the format of the decode KV cache as a trait: what differs between the 16-bit and the E4M3 cache in decode_attn_body -----------
-// (decode.hip).  LDS-DMA moves 16 bytes per lane, so a lane owns EPL elements of a cache row and D / EPL lanes share the row.
+// ---- the format of the decode KV cache as a trait: what differs between the 16-bit and the E4M3 cache in decode_attn_kernel and ------
+// decode_attn_beams_mfma_kernel (decode.hip).  LDS-DMA moves 16 bytes per lane, so a lane owns EPL elements of a cache row and
+// D / EPL lanes share the row.
 //   cache_t               one cache element: its size is the bytes per element
 //   scaled                one power-of-two scale per tensor: K's rides on the (already scaled) query, V's on the final output, both
 //                         exact, so what is summed are plain code values; without it (16-bit) no multiply is emitted at all
-//   encode(x, 1/s, val)   the cache bits of a new element; val = the fp32 value those bits stand for: a new K / V enters this step's
-//                         attention as the cache holds it, like every cached position (16-bit: x is already an element's value)
+//   encode(x, 1/s)        the cache bits of a new element
+//   value(bits, x)        the fp32 value those bits stand for: a new K / V enters this step's attention as the cache holds it, like
+//                         every cached position (16-bit: x is already an element's value, and no instruction)
 //   unpack(v, out)        the EPL elements of one 16-byte load as fp32
+// and, for the beams kernel's LDS tile of 16 positions x D elements:
+//   tile_key<D>(row)      the XOR key on the 16-byte unit index of a row (the swizzle is described at the kernel)
+//   kraw_t, k_operand     what a lane reads from LDS for eight K elements, and the 16x16x32 A operand made of it
+//   vraw_t, v_operand     what a lane reads from LDS for four V elements, and element i of the 16x16x16 A operand made of it
+// The reads themselves stand in the kernel, per format: as trait functions they compiled the 16-bit kernel's LDS addresses
+// differently.
+template <typename KV, int D> __device__ __forceinline__ int kv_tile_off(int row, int unit) {
+  return row * (D * (int)sizeof(typename KV::cache_t)) + ((unit ^ KV::template tile_key<D>(row)) << 4);
+}
 template <typename E> struct Kv16 {
   typedef uint16_t cache_t;
   static constexpr int EPL = 8;
   static constexpr bool scaled = false;
-  __device__ static __forceinline__ uint32_t encode(float x, float, float& val) { val = x; return E::r(x); }
+  __device__ static __forceinline__ uint32_t encode(float x, float) { return E::r(x); }
+  __device__ static __forceinline__ float value(uint32_t, float x) { return x; }
   __device__ static __forceinline__ void unpack(const uint4 v, float* out) { elt_unpack8<E>(v, out); }
+  template <int D> __device__ static __forceinline__ int tile_key(int row) {
+    constexpr int UPR = D / 8;
+    return UPR == 8 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)) : UPR == 16 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (row & (UPR - 1));
+  }
+  typedef elt_u32x4 kraw_t;
+  typedef elt_s16x4 vraw_t;
+  __device__ static __forceinline__ elt_u32x4 k_operand(kraw_t k) { return k; }
+  __device__ static __forceinline__ short v_operand(vraw_t v, int i) { return v[i]; }
 };
-// rows of D bytes: code = rne_e4m3(clamp(x / s)), widened with v_cvt_pk_f32_fp8, four codes per dword
+// rows of D bytes: code = rne_e4m3(clamp(x / s)), widened with v_cvt_pk_f32_fp8, four codes per dword.  A code's value is exact in
+// bf16 and fp16, so the MFMA operands are plain code values, made AFTER the LDS read.
 template <typename E> struct KvE4m3 {
   typedef uint8_t cache_t;
   static constexpr int EPL = 16;
   static constexpr bool scaled = true;
-  __device__ static __forceinline__ uint32_t encode(float x, float recip_scale, float& val) {
-    const uint32_t c = e4m3_encode(x * recip_scale);
-    val = e4m3_decode(c);
-    return c;
-  }
+  __device__ static __forceinline__ uint32_t encode(float x, float recip_scale) { return e4m3_encode(x * recip_scale); }
+  __device__ static __forceinline__ float value(uint32_t code, float) { return e4m3_decode(code); }
   __device__ static __forceinline__ void unpack(const uint4 v, float* out) {
     e4m3_unpack4(v.x, out); e4m3_unpack4(v.y, out + 4); e4m3_unpack4(v.z, out + 8); e4m3_unpack4(v.w, out + 12);
   }
+  template <int D> __device__ static __forceinline__ int tile_key(int row) { return D == 64 ? ((row >> 2) & 3) : ((row >> 1) & 7); }
+  typedef uint2 kraw_t;
+  struct vraw_t { uint32_t b[4]; };
+  __device__ static __forceinline__ elt_u32x4 k_operand(kraw_t k) { return e4m3_unpack8_elt<E>(k.x, k.y); }
+  __device__ static __forceinline__ short v_operand(vraw_t v, int i) { return (short)e4m3_elt_bits<E>(e4m3_decode(v.b[i])); }
 };
 
 // mxvl_dtype of a decode descriptor: 0 (what ABI <= 7 callers leave in the reserved field) means bf16

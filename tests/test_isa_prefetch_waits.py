@@ -112,21 +112,26 @@ def test_beams_attention_runs_its_products_on_the_matrix_cores(elt, suffix):
     """decode_attn_beams_mfma_kernel: K Q^T by 16x16x32 MFMA, V^T P by 16x16x16 MFMA with V^T through the transpose read, tiles by
     LDS-DMA with explicit counted waits, no scratch; the only ds_bpermute left are the per-tile max over the four q-lanes and the
     final sum (the VALU version ran four dependent ones per (position, beam)).  Round 5: the same instruction stream for the fp16
-    instantiation (csrc/decode_elt.h), which is the dtype the reference loads its LLM in."""
-    ins = _body("decode.hip", f"decode_attn_beams_mfma_kernelINS_{len(elt)}{elt}ELi128ELi3ELi8E")
+    instantiation (csrc/decode_elt.h), which is the dtype the reference loads its LLM in.
+    The E4M3-cache instantiation of the same kernel at head_dim 128, 3 beams, 8 waves: rows of 128 bytes are UPR = 8 units, so a
+    DMA instruction covers 8 rows, NI = 2 per K (or V) tile and OPS = 4 per stage -- the wait for the older of two tiles is vmcnt(4)
+    and the two stages of the prologue plus the refill hold >= 4 requests; NKK = 4 and NDT = 8 MFMAs per tile as with the 16-bit
+    cache (the products stay on the 16-bit matrix cores); V^T by byte reads, so no transpose read is asked for."""
     count = lambda pat: sum(1 for x in ins if re.match(pat, x))
-    assert count(rf"v_mfma_f32_16x16x32[_a-z0-9]*{suffix}") >= 4 and count(rf"v_mfma_f32_16x16x16[_a-z0-9]*{suffix}") >= 8
-    assert count(r"ds_read_b64_tr_b16") >= 8 and count(r"global_load_lds_dwordx4") >= 8
-    assert any(re.match(r"s_waitcnt vmcnt\(8\)", x) for x in ins), "the wait for the older of two tiles in flight"
-    assert not _scratch_ops(ins)
-    assert count(r"ds_bpermute_b32") <= 12      # 2 per tile (max over q) + 2 (final sum) + the fresh position's wave reduction
+    for kv, tr_reads, dma, ops in (("4Kv16", 8, 8, 8), ("6KvE4m3", 0, 4, 4)):
+        ins = _body("decode.hip", f"decode_attn_beams_mfma_kernelINS_{len(elt)}{elt}ENS_{kv}IS1_EELi128ELi3ELi8E")
+        assert count(rf"v_mfma_f32_16x16x32[_a-z0-9]*{suffix}") >= 4 and count(rf"v_mfma_f32_16x16x16[_a-z0-9]*{suffix}") >= 8, kv
+        assert count(r"ds_read_b64_tr_b16") >= tr_reads and count(r"global_load_lds_dwordx4") >= dma, kv
+        assert any(re.match(rf"s_waitcnt vmcnt\({ops}\)", x) for x in ins), f"{kv}: the wait for the older of two tiles in flight"
+        assert not _scratch_ops(ins), kv
+        assert count(r"ds_bpermute_b32") <= 12, kv      # 2 per tile (max over q) + 2 (final sum) + the fresh position's wave reduction
 
 
 @pytest.mark.parametrize("elt", ["EltBf16", "EltF16"])
 def test_per_row_decode_attention_sums_scores_by_dpp(elt):
     """decode_attn_kernel: the 16-lane score sum is four DPP adds; ds_bpermute only in the final merge of the lane groups (behind the
     position loop), and the cache rows arrive through the LDS ring"""
-    ins = _body("decode.hip", f"decode_attn_kernelINS_{len(elt)}{elt}ELi128ELi8ELi4E")
+    ins = _body("decode.hip", f"decode_attn_kernelINS_{len(elt)}{elt}ENS_4Kv16IS1_EELi128ELi8ELi4E")
     assert sum(1 for x in ins if x.startswith("v_add_f32_dpp")) >= 4
     assert sum(1 for x in ins if x.startswith("global_load_lds_dwordx4")) >= 4
     first_dma = next(k for k, x in enumerate(ins) if x.startswith("global_load_lds_dwordx4"))

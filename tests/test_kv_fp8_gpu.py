@@ -1,5 +1,5 @@
 """kv_cache_dtype="fp8" on the GPU: the bytes the fp8-cache attention kernels append (mxvl_decode_attn with MXVL_KV_FP8,
-csrc/decode.hip decode_attn_kv8_kernel / decode_attn_beams_kv8_kernel), their attention against a float64 softmax over the
+csrc/decode.hip decode_attn_kernel / decode_attn_beams_mfma_kernel over KvE4m3), their attention against a float64 softmax over the
 dequantised cache, guard bands, and generate() on the kernel stepper against the torch-module stepper."""
 import ctypes
 
@@ -133,7 +133,7 @@ def _check_untouched(buf, cache, before, pos_v):
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 def test_per_row_kernel_matches_float64_attention_over_the_dequantised_cache(dtype, D, H, Hkv, rows):
-    """decode_attn_kv8_kernel at pos 0, 1, one below / at / one above the positions of one workgroup trip (8 waves x 64 / (D / 16)
+    """decode_attn_kernel over KvE4m3 at pos 0, 1, one below / at / one above the positions of one workgroup trip (8 waves x 64 / (D / 16)
     lane groups), and past two trips; rows = 3: row 0 left-padded, a permuted slot table, row 2 sees only the fresh key; rows = 1:
     the only-fresh-key case at one position.  Bound: the 16-bit kernels' (an output-dtype ulp of the reference's max)."""
     NG = 8 * 64 // (D // 16)
@@ -170,15 +170,24 @@ def test_per_row_kernel_matches_float64_attention_over_the_dequantised_cache(dty
             assert torch.equal(out[2].view(H, D), fresh.repeat_interleave(H // Hkv, dim=0))
 
 
-@pytest.mark.parametrize("nsh", [0, 21, 71], ids=["shared0", "shared21", "shared_all"])
-@pytest.mark.parametrize("nb", [2, 3, 5])
-@pytest.mark.parametrize("D", [64, 128])
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
-def test_beams_kernel_matches_float64_attention_over_the_dequantised_cache(dtype, D, nb, nsh):
-    """decode_attn_beams_kv8_kernel: two samples of nb beams, pos = 71 (not a multiple of the 16-position tile), the beams' slot
-    tables equal on the first nsh positions (0, mid-tile, all), one masked prompt position in sample 0.  The same oracle and bound,
-    and the same appended bytes as the per-row kernel."""
-    B, H, Hkv, T, pos_v = 2, 4, 2, 96, 71
+_BEAMS_SHAPE = (2, 4, 2, 96, 71)             # B, H, Hkv, T, pos
+_BEAMS_CASES = [pytest.param(dtype, D, nb, nsh, _BEAMS_SHAPE, id=f"{dt_id}-{D}-{nb}-{nsh_id}")
+                for nsh, nsh_id in ((0, "shared0"), (21, "shared21"), (71, "shared_all")) for nb in (2, 3, 5) for D in (64, 128)
+                for dtype, dt_id in ((torch.bfloat16, "bf16"), (torch.float16, "fp16"))]
+_BEAMS_CASES += [pytest.param(torch.float16, 128, 4, 21, _BEAMS_SHAPE, id="fp16-128-4-shared21"),
+                 pytest.param(torch.bfloat16, 128, 5, 1003, (1, 2, 2, 4400, 4350), id="bf16-128-5-waves4")]
+
+
+@pytest.mark.parametrize("dtype,D,nb,nsh,shape", _BEAMS_CASES)
+def test_beams_kernel_matches_float64_attention_over_the_dequantised_cache(dtype, D, nb, nsh, shape):
+    """decode_attn_beams_mfma_kernel over KvE4m3: two samples of nb beams, pos = 71 (not a multiple of the 16-position tile), the
+    beams' slot tables equal on the first nsh positions (0, mid-tile, all), one masked prompt position in sample 0.  The same oracle
+    and bound, and the same appended bytes as the per-row kernel.  nb = 2, 3, 5 at every (D, dtype), nb = 4 at one.
+    waves4 is the 4-wave instantiation: the launcher's LDS need is nw * 2 * stage + 16 * D * 2 + 4 * (3 nb D + 2 nb (nw + 1) + nb T)
+    bytes with stage = 2 * 16 * D bytes of E4M3 codes; at D 128, nb 5, T 4400 that is 65536 + 4096 + 4 * (1920 + 90 + 22000) =
+    165672 with 8 waves, over the 160 KiB (163840) a workgroup may have, and 32768 + 4096 + 4 * (1920 + 50 + 22000) = 132744 with
+    4.  One sample, pos = 4350 (mid-tile), the beams agree on the first 1003 positions (mid-tile)."""
+    B, H, Hkv, T, pos_v = shape
     rows = B * nb
     g = torch.Generator().manual_seed(D + 7 * nb + nsh)
     kvs = torch.tensor([2.0 ** -4, 2.0 ** -6], dtype=torch.float32, device=DEV)
