@@ -68,6 +68,16 @@ __device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 
 constexpr float kNegInf = -__builtin_inff();
 
 // ---- operand policies -------------------------------------------------------------------------------------------------
+// XOR-swizzle key of a row of a 16-bit [rows x D] LDS tile (Pol16::unit_off; also applied on the SOURCE side of an LDS-DMA, which
+// writes LDS linearly: dma_unit64)
+template <int D> __device__ __forceinline__ int unit_key(int row) {
+  constexpr int UPR = D / 8, SH = UPR >= 16 ? 0 : (UPR == 8 ? 1 : 2);
+  // D = 128 (UPR = 16, a row is a whole bank row): rows r .. r + 3 of a transposed read must land in four different 64-byte
+  // blocks -> row bits 1..0 go to key bits 3..2; the 16 rows of a b128 group still get 16 different keys.
+  return UPR == 8 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))
+       : UPR == 16 ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> SH) & (UPR - 1));
+}
+
 template <typename E> struct Pol16 {
   static constexpr int KSTEP = 16, ESZ = 2;
   typedef uint4 Frag;
@@ -89,11 +99,7 @@ template <typename E> struct Pol16 {
   // plain key (row >> 1) & 7 those two rows read the same four units: 25 % of the forward's LDS cycles were conflicts
   // (profiles/r02_attn_pmc.txt).
   template <int D> static __device__ __forceinline__ int unit_off(int row, int u) {
-    constexpr int UPR = D / 8, SH = UPR >= 16 ? 0 : (UPR == 8 ? 1 : 2);
-    // D = 128 (UPR = 16, a row is a whole bank row): rows r .. r + 3 of a transposed read must land in four different 64-byte
-    // blocks -> row bits 1..0 go to key bits 3..2; the 16 rows of a b128 group still get 16 different keys.
-    const int key = UPR == 8 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))
-                  : UPR == 16 ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> SH) & (UPR - 1));
+    const int key = unit_key<D>(row);
     return row * (D * 2) + ((u ^ key) << 4);
   }
   // A operand, row-major rows: lane (row, hi) takes elements [16 ks + 8 hi, +8) of its row
@@ -217,6 +223,37 @@ struct Pol32 {
 
 template <typename E> struct PolOf { typedef Pol16<E> type; };
 template <> struct PolOf<float> { typedef Pol32 type; };
+
+// epilogue of a lane that owns one row (a query of O^T / dQ^T): its 4 x 4 consecutive elements of every 32-wide accumulator block, times f
+template <typename Pol, typename E, int NDT>
+__device__ __forceinline__ void store_row(E* row, const f32x16 (&acc)[NDT], int hi, float f) {
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      Pol::st4(row + 32 * dt + 8 * g + 4 * hi, acc[dt][4 * g] * f, acc[dt][4 * g + 1] * f, acc[dt][4 * g + 2] * f, acc[dt][4 * g + 3] * f);
+}
+
+// ---- LDS-DMA of head_dim-64 16-bit tiles (attn_q64_kernel: K / V; attn_bwd_dkv_kernel<DMAQ>: Q / dO) ------------------------------
+// A [64 x 64] tile is 64 rows x 128 bytes; each of the four waves moves 16 rows of it, 8 per global_load_lds_dwordx4 (lane l: row
+// l >> 3, 16-byte unit l & 7).  The DMA writes LDS linearly, so the XOR swizzle of unit_off<64> is applied on the SOURCE address:
+// element offset, inside its source row, of the unit this lane fetches for tile row `row`.
+__device__ __forceinline__ int dma_unit64(int row, int lane) { return ((lane & 7) ^ unit_key<64>(row)) * 8; }
+// The calling wave's 16 rows x 128 bytes of tile A to LDS address `dst` and of tile B to dst + 8 KB (the next tile): four transfers.
+// address = (tile base ga / gb, wave-uniform, in SGPRs) + (per-lane 32-bit byte offset: rows 0..7, rows 8..15 of A, then of B)
+__device__ __forceinline__ void dma_two_tiles(unsigned dst, const void* ga, const void* gb, unsigned a0, unsigned a1, unsigned b0, unsigned b1) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %[keep], m0\n\t"
+      "s_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o0], %[ga]\n\t"
+      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o1], %[ga]\n\t"
+      "s_add_u32 m0, m0, 0x1c00\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o2], %[gb]\n\t"
+      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o3], %[gb]\n\t"
+      "s_mov_b32 m0, %[keep]"
+      : [keep] "=&s"(keep)
+      : [dst] "s"(dst), [ga] "s"(ga), [gb] "s"(gb), [o0] "v"(a0), [o1] "v"(a1), [o2] "v"(b0), [o3] "v"(b1)
+      : "memory", "scc");
+}
 
 // Reductions over the lane pair (l, l ^ 32) that shares an MFMA column: v_permlane32_swap exchanges the upper half of its
 // first operand with the lower half of its second -- one VALU op, no LDS round trip.  Inline asm: this toolchain's
@@ -500,6 +537,8 @@ __global__ __launch_bounds__(NW * 64, (D >= 128 || sizeof(E) == 4) ? 1 : 2) void
   if constexpr (!DQ) {
     const float inv = l > 0.f ? fast_rcp(l) : 0.f;
     E* op = (E*)p.out + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs + qr * p.o_ts;
+    // (store_row(op, acc, hi, inv) written out: through the helper these loops are unrolled before hipcc orders the operands of the
+    //  products, and ten instantiations get every v_mul / v_pk_mul commuted -- the same values from a stream no profile has measured)
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -508,29 +547,27 @@ __global__ __launch_bounds__(NW * 64, (D >= 128 || sizeof(E) == 4) ? 1 : 2) void
     if (p.lse && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qr] = l > 0.f ? m + fast_log2(l) : __builtin_inff();
   } else {
     E* dqp = (E*)p.dq + (int64_t)b * p.dq_bs + (int64_t)h * p.dq_hs + qr * p.dq_ts;
-    const float sc = p.scale;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        Pol::st4(dqp + 32 * dt + 8 * g + 4 * hi, acc[dt][4 * g] * sc, acc[dt][4 * g + 1] * sc, acc[dt][4 * g + 2] * sc, acc[dt][4 * g + 3] * sc);
+    store_row<Pol>(dqp, acc, hi, p.scale);
   }
 }
 
-// ---- forward, head_dim 64, 16-bit, no key mask / bias: 64 queries per wave ----------------------------------------------------
+// ---- forward / dQ, head_dim 64, 16-bit, no key mask / bias: 64 queries per wave -------------------------------------------------
 // attn_q_kernel gives a wave 32 queries, so every wave reads the whole 64-key K and V tile from LDS (16 KB) for 16 MFMAs: 8 waves
 // keep the CU's LDS port busy 1760 cycles per round against 1024 MFMA cycles -- the LDS port, not the matrix core, was the first
-// wall (13-14 % of the MFMA peak).  Here a wave owns TWO 32-query blocks: every K fragment (ds_read_b128) and every
-// V^T fragment (ds_read_b64_tr_b16) feeds two MFMAs, 32 MFMAs per 16 KB of LDS reads.
+// wall (13-14 % of the MFMA peak).  Here a wave owns TWO 32-query blocks, so every fragment read from LDS feeds two
+// MFMAs.  The frame both passes share (DQ = false: O, lse; DQ = true: dQ, delta):
 //   * workgroup = 4 waves = 256 queries, 64-key tiles, THREE LDS stages of [K | V] (48 KB, two workgroups per CU)
-//   * K / V tiles arrive by LDS-DMA (global_load_lds_dwordx4 from inline asm, as in gemm_swiglu.hip): no staging registers, no
-//     ds_write pass; the XOR swizzle of unit_off<64> is applied on the DMA's SOURCE address (the DMA writes LDS linearly).
-//     Tile t + 2 is requested right after the barrier of tile t; the only waits are one counted vmcnt + one barrier per tile.
+//   * K / V tiles arrive by LDS-DMA (dma_two_tiles): no staging registers, no ds_write pass.  Tile t + 2 is requested right after
+//     the barrier of tile t; the only waits are one counted vmcnt + one barrier per tile.
 //     Key rows past Lk are fetched from row Lk - 1 (finite values under a zero probability), never left as stale LDS bits.
-//   * softmax: the scale rides in the exponent's FMA (exp2(s * c - m)), the row maximum is taken on the raw scores
 //   * a wave skips the arithmetic of a diagonal tile none of its 64 queries can see (it still keeps the barriers)
-template <typename E>
-__global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnArgs p) {
+// Forward: every K fragment (ds_read_b128) and every V^T fragment (ds_read_b64_tr_b16) feeds two MFMAs, 32 MFMAs per 16 KB of LDS
+// reads; the scale rides in the exponent's FMA (exp2(s * c - m)), the row maximum is taken on the raw scores.
+// dQ: per 64-key tile and wave 48 MFMAs (S^T, dP^T, dQ^T for two query blocks) against 24 KB of LDS reads (K rows, V rows, K^T);
+// attn_q_kernel<DQ> needs 40 KB for 24.  Also writes delta = rowsum(dO * O) for the dK/dV kernel.  The pass sits at the register
+// limit (256 VGPRs): two indices are re-derived behind opaque moves where keeping them alive across the key loop meant scratch.
+template <typename E, bool DQ>
+__global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs p) {
   typedef Pol16<E> Pol;
   typedef uint4 Frag;
   constexpr int D = 64, NW = 4, QT = NW * 64, KT = kKT, NKD = 4, NKR = 2, NDT = 2, TB = KT * D * 2, NST = 3;
@@ -562,16 +599,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnArgs p) {
   // ---- LDS-DMA: this wave moves rows 16 wave .. 16 wave + 15 of the K tile and of the V tile (2 x 1 KB each) ----------------
   const E* kb = (const E*)p.k + (int64_t)b * p.k_bs + (int64_t)hk * p.k_hs;
   const E* vb = (const E*)p.v + (int64_t)b * p.v_bs + (int64_t)hk * p.v_hs;
-  // address = (tile base, wave-uniform, in SGPRs) + (per-lane 32-bit byte offset, the same for every full tile)
-  auto dma_row = [&](int i) { return 16 * wave + 8 * i + (lane >> 3); };
-  auto dma_unit = [&](int row) {                      // element offset of the 16-byte unit this lane fetches (Pol16::unit_off<64>)
-    const int key = (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
-    return ((lane & 7) ^ key) * 8;
-  };
+  // per-lane 32-bit byte offsets, the same for every full tile
   unsigned offK[2], offV[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int row = dma_row(i), unit = dma_unit(row);
+    const int row = 16 * wave + 8 * i + (lane >> 3), unit = dma_unit64(row, lane);
     offK[i] = (unsigned)(((int64_t)row * p.k_ts + unit) * 2);
     offV[i] = (unsigned)(((int64_t)row * p.v_ts + unit) * 2);
   }
@@ -582,36 +614,51 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnArgs p) {
     const E* gv = vb + (int64_t)k0 * p.v_ts;
     unsigned o[4] = {offK[0], offK[1], offV[0], offV[1]};
     if (k0 + KT > p.Lk) {                            // wave-uniform: the ragged last tile re-reads row Lk - 1 for the missing rows
+      int lane_r = lane;
+      if constexpr (DQ) {                  // (re-derived behind an opaque move: kept from the top, the lane index of this once-per-kernel
+        lane_r = threadIdx.x;              //  branch was a VGPR stored before the key loop and reloaded here -- scratch)
+        asm volatile("" : "+v"(lane_r));
+        lane_r &= 63;
+      }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {      // (recomputed here: the row / unit of a lane are not worth two registers each in the loop)
-        const int row = dma_row(i), unit = dma_unit(row);
+        const int row = 16 * wave + 8 * i + (lane_r >> 3), unit = dma_unit64(row, lane_r);
         const int r = k0 + row < p.Lk ? row : p.Lk - 1 - k0;
         o[i] = (unsigned)(((int64_t)r * p.k_ts + unit) * 2);
         o[2 + i] = (unsigned)(((int64_t)r * p.v_ts + unit) * 2);
       }
     }
-    const unsigned dst = lds0 + (unsigned)((kt % NST) * 2 * TB + wave * 2048);
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %[keep], m0\n\t"
-        "s_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o0], %[gk]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o1], %[gk]\n\t"
-        "s_add_u32 m0, m0, 0x1c00\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o2], %[gv]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o3], %[gv]\n\t"
-        "s_mov_b32 m0, %[keep]"
-        : [keep] "=&s"(keep)
-        : [dst] "s"(dst), [gk] "s"(gk), [gv] "s"(gv), [o0] "v"(o[0]), [o1] "v"(o[1]), [o2] "v"(o[2]), [o3] "v"(o[3])
-        : "memory", "scc");
+    dma_two_tiles(lds0 + (unsigned)((kt % NST) * 2 * TB + wave * 2048), gk, gv, o[0], o[1], o[2], o[3]);
   };
   if (ntiles > 0) issue(0);
   if (ntiles > 1) issue(1);
 
-  Frag qf[2][NKD];
+  // ---- per-query operands: Q; dQ pass: also dO, lse and delta = rowsum(dO * O) -------------------------------------------------
+  Frag qf[2][NKD], dof[2][DQ ? NKD : 1];
+  float lse[2], delta[2];
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
-    const E* qp = (const E*)p.q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs + (int64_t)(qv[qb] ? qrow[qb] : 0) * p.q_ts;
+    const int64_t qr = qv[qb] ? qrow[qb] : 0;
+    const E* qp = (const E*)p.q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs + qr * p.q_ts;
+    if constexpr (!DQ) {
 #pragma unroll
-    for (int ks = 0; ks < NKD; ++ks) qf[qb][ks] = qv[qb] ? Pol::ldg(qp, ks, hi) : Pol::zero();
+      for (int ks = 0; ks < NKD; ++ks) qf[qb][ks] = qv[qb] ? Pol::ldg(qp, ks, hi) : Pol::zero();
+    } else {
+      const E* dop = (const E*)p.dout + (int64_t)b * p.do_bs + (int64_t)h * p.do_hs + qr * p.do_ts;
+      const E* op = (const E*)p.o + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs + qr * p.o_ts;
+      float dl = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < NKD; ++ks) {
+        qf[qb][ks] = qv[qb] ? Pol::ldg(qp, ks, hi) : Pol::zero();
+        dof[qb][ks] = qv[qb] ? Pol::ldg(dop, ks, hi) : Pol::zero();
+        const Frag of = qv[qb] ? Pol::ldg(op, ks, hi) : Pol::zero();
+        dl += Pol::dot(dof[qb][ks], of);
+      }
+      delta[qb] = pair_sum(dl);                     // rowsum(dO * O): lanes l and l ^ 32 hold the two halves of a row
+      const int64_t ro = ((int64_t)b * p.H + h) * p.Lq + qr;
+      lse[qb] = qv[qb] ? p.lse[ro] : __builtin_inff();
+      if (qv[qb] && hi == 0) p.delta[ro] = delta[qb];
+    }
   }
   f32x16 acc[2][NDT];
 #pragma unroll
@@ -620,7 +667,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnArgs p) {
     for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[qb][dt][r] = 0.f;
-  float m[2] = {kNegInf, kNegInf}, l[2] = {0.f, 0.f};
+  float m[2] = {kNegInf, kNegInf}, l[2] = {0.f, 0.f};      // forward: running maximum and sum of the online softmax
   // NOTE (profiles/r03_attn_wait_ab.txt): with the Q fragment loads still pending at the loop header, hipcc puts a
   // `s_waitcnt vmcnt(0)` in front of the first MFMA of the loop body (s_waitcnt insertion is static), i.e. behind the DMA request
   // of tile kt + 2.  Consuming the fragments before the loop removes that wait -- and measured 2 % SLOWER here and in the dQ pass
@@ -639,305 +686,168 @@ __global__ __launch_bounds__(256, 2) void attn_fwd64_kernel(const AttnArgs p) {
     if (k0 >= wkend) continue;                       // wave-uniform: nothing in this tile is visible to these 64 queries
     const char* sK = smem + (kt % NST) * 2 * TB;
     const char* sV = sK + TB;
-
-    f32x16 s[2][2];                                  // [key half][query block]
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      Frag ka[NKD];
-#pragma unroll
-      for (int ks = 0; ks < NKD; ++ks) ka[ks] = Pol::template a_row<D>(sK, 32 * h2 + j, ks, hi);
-#pragma unroll
-      for (int ks = 0; ks < NKD; ++ks)
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)   // first step: C = the inline constant 0, not 16 zeroed registers per accumulator
-          s[h2][qb] = Pol::mma(ka[ks], qf[qb][ks], ks == 0 ? zero16 : s[h2][qb]);
-    }
     const bool masked = k0 + KT > kfull;
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      if (masked) {
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = k0 + 32 * h2 + crow(r, hi);
-            s[h2][qb][r] = key < klim[qb] ? s[h2][qb][r] : kNegInf;
-          }
-      }
-      float mx = kNegInf;
-#pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[h2][qb][r]);
-      mx = pair_max(mx) * c;                         // c > 0: the maximum commutes with the scale
-      const float mn = fmaxf(m[qb], mx);
-      const float mu = (mn == kNegInf) ? 0.f : mn;
-      const float alpha = fast_exp2(m[qb] - mu);
-      float rs = 0.f;
-#pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = fast_exp2(fmaf(s[h2][qb][r], c, -mu));
-          s[h2][qb][r] = pv;
-          rs += pv;
-        }
-      rs = pair_sum(rs);
-      l[qb] = fmaf(l[qb], alpha, rs);
-      m[qb] = mn;
-      if (!__all(alpha == 1.0f)) {
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[qb][dt][r] *= alpha;
-      }
-    }
-    // O^T += V^T P^T; the V^T operands of a key half are requested together, one half ahead of their MFMAs (holding all 32
-    // registers of them across the softmax pushed the loop into scratch spills, and a spill reload waits on vmcnt = on the DMA)
-    Frag ta[2][NKR][NDT];
-#pragma unroll
-    for (int ks = 0; ks < NKR; ++ks)
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) ta[0][ks][dt] = Pol::template a_tr<D>(sV, 0, ks, hi, 32 * dt, lane);
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      if (h2 == 0) {
-#pragma unroll
-        for (int ks = 0; ks < NKR; ++ks)
-#pragma unroll
-          for (int dt = 0; dt < NDT; ++dt) ta[1][ks][dt] = Pol::template a_tr<D>(sV, 32, ks, hi, 32 * dt, lane);
-      }
-#pragma unroll
-      for (int ks = 0; ks < NKR; ++ks) {
-        Frag pb[2];
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) pb[qb] = Pol::b_from_acc(s[h2][qb], ks);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-          for (int qb = 0; qb < 2; ++qb) acc[qb][dt] = Pol::mma(ta[h2][ks][dt], pb[qb], acc[qb][dt]);
-      }
-    }
-  }
-
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    if (!qv[qb]) continue;
-    const int64_t qr = qrow[qb];
-    const float inv = l[qb] > 0.f ? fast_rcp(l[qb]) : 0.f;
-    E* op = (E*)p.out + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs + qr * p.o_ts;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        Pol::st4(op + 32 * dt + 8 * g + 4 * hi, acc[qb][dt][4 * g] * inv, acc[qb][dt][4 * g + 1] * inv, acc[qb][dt][4 * g + 2] * inv,
-                 acc[qb][dt][4 * g + 3] * inv);
-    if (p.lse && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qr] = l[qb] > 0.f ? m[qb] + fast_log2(l[qb]) : __builtin_inff();
-  }
-}
-
-// ---- dQ pass, head_dim 64, 16-bit, no key mask / bias: the same 64-queries-per-wave / LDS-DMA structure as attn_fwd64_kernel.
-// Per 64-key tile and wave 48 MFMAs (S^T, dP^T, dQ^T for two query blocks) against 24 KB of LDS reads (K rows, V rows, K^T);
-// attn_q_kernel<DQ> needs 40 KB for 24.  Also writes delta = rowsum(dO * O) for the dK/dV kernel.
-template <typename E>
-__global__ __launch_bounds__(256, 2) void attn_dq64_kernel(const AttnArgs p) {
-  typedef Pol16<E> Pol;
-  typedef uint4 Frag;
-  constexpr int D = 64, NW = 4, QT = NW * 64, KT = kKT, NKD = 4, NKR = 2, NDT = 2, TB = KT * D * 2, NST = 3;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, hi = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // grid = (heads x batch, query tiles): the dispatcher walks x fastest, so ALL workgroups of the longest query tile start
-  // first and the shortest ones fill the tail (longest-processing-time order over the whole launch, not per head)
-  const int b = (int)blockIdx.x / p.H, h = (int)blockIdx.x % p.H, hk = h / (p.H / p.Hkv);
-  const int qt = p.mask_mode ? (int)gridDim.y - 1 - (int)blockIdx.y : (int)blockIdx.y;
-  const int q0 = qt * QT, wq0 = q0 + wave * 64;
-  const float c = p.scale * kLog2e;
-
-  int qrow[2], klim[2];
-  bool qv[2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    qrow[qb] = wq0 + 32 * qb + j;
-    qv[qb] = qrow[qb] < p.Lq;
-    klim[qb] = key_limit(p, qrow[qb]);
-  }
-  const int qlast = (q0 + QT < p.Lq ? q0 + QT : p.Lq) - 1;
-  const int kend = key_limit(p, qlast);            // limits grow with the row index in every mask mode
-  const int kfull = key_limit(p, q0);              // keys below this are visible to every row of the workgroup
-  const int wlast = (wq0 + 64 < p.Lq ? wq0 + 64 : p.Lq) - 1;
-  const int wkend = wq0 < p.Lq ? key_limit(p, wlast) : 0;     // keys at or beyond this are invisible to the whole wave
-  const int ntiles = (kend + KT - 1) / KT;
-
-  // ---- LDS-DMA: this wave moves rows 16 wave .. 16 wave + 15 of the K tile and of the V tile (2 x 1 KB each) ----------------
-  const E* kb = (const E*)p.k + (int64_t)b * p.k_bs + (int64_t)hk * p.k_hs;
-  const E* vb = (const E*)p.v + (int64_t)b * p.v_bs + (int64_t)hk * p.v_hs;
-  // address = (tile base, wave-uniform, in SGPRs) + (per-lane 32-bit byte offset, the same for every full tile)
-  auto dma_row = [&](int i) { return 16 * wave + 8 * i + (lane >> 3); };
-  auto dma_unit = [&](int row) {                      // element offset of the 16-byte unit this lane fetches (Pol16::unit_off<64>)
-    const int key = (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
-    return ((lane & 7) ^ key) * 8;
-  };
-  unsigned offK[2], offV[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = dma_row(i), unit = dma_unit(row);
-    offK[i] = (unsigned)(((int64_t)row * p.k_ts + unit) * 2);
-    offV[i] = (unsigned)(((int64_t)row * p.v_ts + unit) * 2);
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)(smem);
-  auto issue = [&](int kt) {
-    const int k0 = kt * KT;
-    const E* gk = kb + (int64_t)k0 * p.k_ts;
-    const E* gv = vb + (int64_t)k0 * p.v_ts;
-    unsigned o[4] = {offK[0], offK[1], offV[0], offV[1]};
-    if (k0 + KT > p.Lk) {                            // wave-uniform: the ragged last tile re-reads row Lk - 1 for the missing rows
-      int lane_r = threadIdx.x;          // (re-derived behind an opaque move: kept from the top, the lane index of this once-per-kernel
-      asm volatile("" : "+v"(lane_r));   //  branch was a VGPR stored before the key loop and reloaded here -- scratch)
-      lane_r &= 63;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {      // (recomputed here: the row / unit of a lane are not worth two registers each in the loop)
-        const int row = 16 * wave + 8 * i + (lane_r >> 3);
-        const int unit = ((lane_r & 7) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) * 8;
-        const int r = k0 + row < p.Lk ? row : p.Lk - 1 - k0;
-        o[i] = (unsigned)(((int64_t)r * p.k_ts + unit) * 2);
-        o[2 + i] = (unsigned)(((int64_t)r * p.v_ts + unit) * 2);
-      }
-    }
-    const unsigned dst = lds0 + (unsigned)((kt % NST) * 2 * TB + wave * 2048);
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %[keep], m0\n\t"
-        "s_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o0], %[gk]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o1], %[gk]\n\t"
-        "s_add_u32 m0, m0, 0x1c00\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o2], %[gv]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o3], %[gv]\n\t"
-        "s_mov_b32 m0, %[keep]"
-        : [keep] "=&s"(keep)
-        : [dst] "s"(dst), [gk] "s"(gk), [gv] "s"(gv), [o0] "v"(o[0]), [o1] "v"(o[1]), [o2] "v"(o[2]), [o3] "v"(o[3])
-        : "memory", "scc");
-  };
-  if (ntiles > 0) issue(0);
-  if (ntiles > 1) issue(1);
-
-  Frag qf[2][NKD], dof[2][NKD];
-  float lse[2], delta[2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int64_t qr = qv[qb] ? qrow[qb] : 0;
-    const E* qp = (const E*)p.q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs + qr * p.q_ts;
-    const E* dop = (const E*)p.dout + (int64_t)b * p.do_bs + (int64_t)h * p.do_hs + qr * p.do_ts;
-    const E* op = (const E*)p.o + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs + qr * p.o_ts;
-    float dl = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NKD; ++ks) {
-      qf[qb][ks] = qv[qb] ? Pol::ldg(qp, ks, hi) : Pol::zero();
-      dof[qb][ks] = qv[qb] ? Pol::ldg(dop, ks, hi) : Pol::zero();
-      const Frag of = qv[qb] ? Pol::ldg(op, ks, hi) : Pol::zero();
-      dl += Pol::dot(dof[qb][ks], of);
-    }
-    delta[qb] = pair_sum(dl);                     // rowsum(dO * O): lanes l and l ^ 32 hold the two halves of a row
-    const int64_t ro = ((int64_t)b * p.H + h) * p.Lq + qr;
-    lse[qb] = qv[qb] ? p.lse[ro] : __builtin_inff();
-    if (qv[qb] && hi == 0) p.delta[ro] = delta[qb];
-  }
-  f32x16 acc[2][NDT];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[qb][dt][r] = 0.f;
-
-  for (int kt = 0; kt < ntiles; ++kt) {
-    const int k0 = kt * KT;
-    // tile kt has landed (this wave's share: at most tile kt + 1's four transfers may still be in flight), then everybody's has,
-    // and everybody is done reading the stage tile kt + 2 will overwrite
-    if (kt + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + 2 < ntiles) issue(kt + 2);
-    if (k0 >= wkend) continue;                       // wave-uniform: nothing in this tile is visible to these 64 queries
-    const char* sK = smem + (kt % NST) * 2 * TB;
-    const char* sV = sK + TB;
-    const bool masked = k0 + KT > kfull;
+    // first step of a product: C = the inline constant 0, not 16 zeroed registers per accumulator
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+    if constexpr (!DQ) {
+      f32x16 s[2][2];                                  // [key half][query block]
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      // P^T = exp2(K Q^T c - lse), dP^T = V dO^T, dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T -- one 32-key half at a time
-      f32x16 sc[2], dp[2];
-      {
+      for (int h2 = 0; h2 < 2; ++h2) {
         Frag ka[NKD];
 #pragma unroll
         for (int ks = 0; ks < NKD; ++ks) ka[ks] = Pol::template a_row<D>(sK, 32 * h2 + j, ks, hi);
 #pragma unroll
         for (int ks = 0; ks < NKD; ++ks)
 #pragma unroll
-          for (int qb = 0; qb < 2; ++qb) sc[qb] = Pol::mma(ka[ks], qf[qb][ks], ks == 0 ? zero16 : sc[qb]);
-      }
-      {
-        Frag va[NKD];
-#pragma unroll
-        for (int ks = 0; ks < NKD; ++ks) va[ks] = Pol::template a_row<D>(sV, 32 * h2 + j, ks, hi);
-#pragma unroll
-        for (int ks = 0; ks < NKD; ++ks)
-#pragma unroll
-          for (int qb = 0; qb < 2; ++qb) dp[qb] = Pol::mma(va[ks], dof[qb][ks], ks == 0 ? zero16 : dp[qb]);
+          for (int qb = 0; qb < 2; ++qb) s[h2][qb] = Pol::mma(ka[ks], qf[qb][ks], ks == 0 ? zero16 : s[h2][qb]);
       }
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
+      for (int qb = 0; qb < 2; ++qb) {
+        if (masked) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float pv = fast_exp2(fmaf(sc[qb][r], c, -lse[qb]));      // rows without keys: lse = +inf -> 0
-          if (masked) pv = (k0 + 32 * h2 + crow(r, hi)) < klim[qb] ? pv : 0.f;
-          sc[qb][r] = pv * (dp[qb][r] - delta[qb]);
+          for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int key = k0 + 32 * h2 + crow(r, hi);
+              s[h2][qb][r] = key < klim[qb] ? s[h2][qb][r] : kNegInf;
+            }
         }
-      Frag kt_a[NKR][NDT];
+        float mx = kNegInf;
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[h2][qb][r]);
+        mx = pair_max(mx) * c;                         // c > 0: the maximum commutes with the scale
+        const float mn = fmaxf(m[qb], mx);
+        const float mu = (mn == kNegInf) ? 0.f : mn;
+        const float alpha = fast_exp2(m[qb] - mu);
+        float rs = 0.f;
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float pv = fast_exp2(fmaf(s[h2][qb][r], c, -mu));
+            s[h2][qb][r] = pv;
+            rs += pv;
+          }
+        rs = pair_sum(rs);
+        l[qb] = fmaf(l[qb], alpha, rs);
+        m[qb] = mn;
+        if (!__all(alpha == 1.0f)) {
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[qb][dt][r] *= alpha;
+        }
+      }
+      // O^T += V^T P^T; the V^T operands of a key half are requested together, one half ahead of their MFMAs (holding all 32
+      // registers of them across the softmax pushed the loop into scratch spills, and a spill reload waits on vmcnt = on the DMA)
+      Frag ta[2][NKR][NDT];
 #pragma unroll
       for (int ks = 0; ks < NKR; ++ks)
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) kt_a[ks][dt] = Pol::template a_tr<D>(sK, 32 * h2, ks, hi, 32 * dt, lane);
+        for (int dt = 0; dt < NDT; ++dt) ta[0][ks][dt] = Pol::template a_tr<D>(sV, 0, ks, hi, 32 * dt, lane);
 #pragma unroll
-      for (int ks = 0; ks < NKR; ++ks) {
-        Frag db[2];
+      for (int h2 = 0; h2 < 2; ++h2) {
+        if (h2 == 0) {
 #pragma unroll
-        for (int qb = 0; qb < 2; ++qb) db[qb] = Pol::b_from_acc(sc[qb], ks);
+          for (int ks = 0; ks < NKR; ++ks)
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
+            for (int dt = 0; dt < NDT; ++dt) ta[1][ks][dt] = Pol::template a_tr<D>(sV, 32, ks, hi, 32 * dt, lane);
+        }
 #pragma unroll
-          for (int qb = 0; qb < 2; ++qb) acc[qb][dt] = Pol::mma(kt_a[ks][dt], db[qb], acc[qb][dt]);
+        for (int ks = 0; ks < NKR; ++ks) {
+          Frag pb[2];
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb) pb[qb] = Pol::b_from_acc(s[h2][qb], ks);
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) acc[qb][dt] = Pol::mma(ta[h2][ks][dt], pb[qb], acc[qb][dt]);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+        // P^T = exp2(K Q^T c - lse), dP^T = V dO^T, dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T -- one 32-key half at a time
+        f32x16 sc[2], dp[2];
+        {
+          Frag ka[NKD];
+#pragma unroll
+          for (int ks = 0; ks < NKD; ++ks) ka[ks] = Pol::template a_row<D>(sK, 32 * h2 + j, ks, hi);
+#pragma unroll
+          for (int ks = 0; ks < NKD; ++ks)
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) sc[qb] = Pol::mma(ka[ks], qf[qb][ks], ks == 0 ? zero16 : sc[qb]);
+        }
+        {
+          Frag va[NKD];
+#pragma unroll
+          for (int ks = 0; ks < NKD; ++ks) va[ks] = Pol::template a_row<D>(sV, 32 * h2 + j, ks, hi);
+#pragma unroll
+          for (int ks = 0; ks < NKD; ++ks)
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) dp[qb] = Pol::mma(va[ks], dof[qb][ks], ks == 0 ? zero16 : dp[qb]);
+        }
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float pv = fast_exp2(fmaf(sc[qb][r], c, -lse[qb]));      // rows without keys: lse = +inf -> 0
+            if (masked) pv = (k0 + 32 * h2 + crow(r, hi)) < klim[qb] ? pv : 0.f;
+            sc[qb][r] = pv * (dp[qb][r] - delta[qb]);
+          }
+        Frag kt_a[NKR][NDT];
+#pragma unroll
+        for (int ks = 0; ks < NKR; ++ks)
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) kt_a[ks][dt] = Pol::template a_tr<D>(sK, 32 * h2, ks, hi, 32 * dt, lane);
+#pragma unroll
+        for (int ks = 0; ks < NKR; ++ks) {
+          Frag db[2];
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb) db[qb] = Pol::b_from_acc(sc[qb], ks);
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) acc[qb][dt] = Pol::mma(kt_a[ks][dt], db[qb], acc[qb][dt]);
+        }
       }
     }
   }
 
-  // (the epilogue's row / half indices are re-derived from the work-item id behind an opaque move: as values computed at the top they were
-  //  the two VGPRs the register allocator stored before the key loop and reloaded here -- the kernel's 12 bytes of scratch, rounds 3-4)
-  int tid_e = threadIdx.x;
-  asm volatile("" : "+v"(tid_e));
-  const int lane_e = tid_e & 63, j_e = lane_e & 31, hi_e = lane_e >> 5;
-  const int wq0_e = q0 + (tid_e >> 6) * 64;
+  int j_e = j, hi_e = hi, wq0_e = wq0;
+  if constexpr (DQ) {
+    // (the epilogue's row / half indices are re-derived from the work-item id behind an opaque move: as values computed at the top they were
+    //  the two VGPRs the register allocator stored before the key loop and reloaded here -- the kernel's 12 bytes of scratch, rounds 3-4)
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    const int lane_e = tid_e & 63;
+    j_e = lane_e & 31, hi_e = lane_e >> 5, wq0_e = q0 + (tid_e >> 6) * 64;
+  }
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     const int qrow_e = wq0_e + 32 * qb + j_e;
     if (!(qrow_e < p.Lq)) continue;
-    E* dqp = (E*)p.dq + (int64_t)b * p.dq_bs + (int64_t)h * p.dq_hs + (int64_t)qrow_e * p.dq_ts;
-    const float sc2 = p.scale;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        Pol::st4(dqp + 32 * dt + 8 * g + 4 * hi_e, acc[qb][dt][4 * g] * sc2, acc[qb][dt][4 * g + 1] * sc2, acc[qb][dt][4 * g + 2] * sc2,
-                 acc[qb][dt][4 * g + 3] * sc2);
+    const int64_t qr = qrow_e;
+    if constexpr (!DQ) {
+      const float inv = l[qb] > 0.f ? fast_rcp(l[qb]) : 0.f;
+      E* op = (E*)p.out + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs + qr * p.o_ts;
+      store_row<Pol>(op, acc[qb], hi_e, inv);
+      if (p.lse && hi_e == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qr] = l[qb] > 0.f ? m[qb] + fast_log2(l[qb]) : __builtin_inff();
+    } else {
+      E* dqp = (E*)p.dq + (int64_t)b * p.dq_bs + (int64_t)h * p.dq_hs + qr * p.dq_ts;
+      store_row<Pol>(dqp, acc[qb], hi_e, p.scale);
+    }
   }
 }
 
 // ---- dK / dV ----------------------------------------------------------------------------------------------------------
 // One workgroup per 128-key tile (a lane owns a key); walks the query tiles that can see it, Q / dO tiles double-buffered.
 // DMAQ (head_dim 64, 16-bit, no key mask / bias, 16-byte aligned q / dout rows; the launcher decides): the Q / dO tile of the
-// NEXT query tile, its lse and delta rows arrive by LDS-DMA (global_load_lds_dwordx4 / _dword from inline asm, the XOR swizzle of
-// unit_off<64> on the source address as in attn_fwd64_kernel) while the current tile is multiplied; one vmcnt(0) + one barrier per
+// NEXT query tile, its lse and delta rows arrive by LDS-DMA (dma_two_tiles as in attn_q64_kernel, and a global_load_lds_dword
+// pair from inline asm) while the current tile is multiplied; one vmcnt(0) + one barrier per
 // tile.  The register-staged form below was meant to do the same, but hipcc puts `s_waitcnt vmcnt(0)` in front of the first MFMA
 // of the iteration that issued the loads (profiles/r03_attn_dkv_dma.txt): every tile's latency was exposed.
 template <typename E, int D, int NW, bool EXTRA, bool DMAQ = false>
@@ -996,10 +906,8 @@ __global__ __launch_bounds__(NW * 64, (D >= 128 || sizeof(E) == 4) ? 1 : 2) void
     }
   };
   // ---- DMAQ: this wave moves rows 16 wave .. 16 wave + 15 of the Q tile and of the dO tile (2 x 1 KB each); wave 0 also the
-  // 64 lse and delta entries.  address = (tile base, wave-uniform, SGPRs) + (per-lane 32-bit byte offset)
+  // 64 lse and delta entries.
   const int wq = __builtin_amdgcn_readfirstlane(wave);
-  auto dma_row = [&](int i) { return 16 * wq + 8 * i + (lane >> 3); };
-  auto dma_unit = [&](int row) { return ((lane & 7) ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) * 8; };   // Pol16::unit_off<64>
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)(smem);
   const unsigned ldsRow = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)((char*)sRow);
   auto issue = [&](int it) {
@@ -1009,24 +917,14 @@ __global__ __launch_bounds__(NW * 64, (D >= 128 || sizeof(E) == 4) ? 1 : 2) void
     unsigned o[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {      // rows past Lq re-read row Lq - 1 (finite values under lse = +inf, i.e. probability 0)
-      const int row = dma_row(i), unit = dma_unit(row);
+      const int row = 16 * wq + 8 * i + (lane >> 3), unit = dma_unit64(row, lane);
       const int r = q0 + row < p.Lq ? row : p.Lq - 1 - q0;
       o[i] = (unsigned)(((int64_t)r * p.q_ts + unit) * 2);
       o[2 + i] = (unsigned)(((int64_t)r * p.do_ts + unit) * 2);
     }
-    const unsigned dst = lds0 + (unsigned)(2 * buf * TB + wq * 2048);
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %[keep], m0\n\t"
-        "s_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o0], %[gq]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o1], %[gq]\n\t"
-        "s_add_u32 m0, m0, 0x1c00\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o2], %[go]\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[o3], %[go]\n\t"
-        "s_mov_b32 m0, %[keep]"
-        : [keep] "=&s"(keep)
-        : [dst] "s"(dst), [gq] "s"(gq), [go] "s"(go), [o0] "v"(o[0]), [o1] "v"(o[1]), [o2] "v"(o[2]), [o3] "v"(o[3])
-        : "memory", "scc");
+    dma_two_tiles(lds0 + (unsigned)(2 * buf * TB + wq * 2048), gq, go, o[0], o[1], o[2], o[3]);
     if (wq == 0) {
+      unsigned keep;
       const int q = q0 + lane;
       const unsigned oq = (unsigned)((q < p.Lq ? q : p.Lq - 1) * 4);
       const float* gl = p.lse + ((int64_t)b * p.H + hq) * p.Lq;
@@ -1206,20 +1104,22 @@ static int launch_q1(const AttnArgs& a, hipStream_t s) {
   return launch_status();
 }
 template <typename E, bool DQ>
-static int launch_fwd64(const AttnArgs& a, hipStream_t s) {
+static int launch_q64(const AttnArgs& a, hipStream_t s) {
   const size_t lds = 3 * 2 * (size_t)(kKT * 64 * 2);
   dim3 grid(a.H * a.batch, (a.Lq + 255) / 256, 1);
-  if constexpr (DQ) hipLaunchKernelGGL(attn_dq64_kernel<E>, grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(attn_fwd64_kernel<E>, grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_q64_kernel<E, DQ>), grid, dim3(256), lds, s, a);
   return launch_status();
+}
+// rows of a 16-bit tensor an LDS-DMA can fetch in 16-byte units: base and strides (in elements) on 16-byte boundaries
+static bool dma_rows16(const void* base, int64_t bs, int64_t hs, int64_t ts) {
+  return ts % 8 == 0 && hs % 8 == 0 && bs % 8 == 0 && (uintptr_t)base % 16 == 0;
 }
 template <typename E, int D, bool DQ>
 static int launch_q(const AttnArgs& a, hipStream_t s) {
   if constexpr (D == 64 && sizeof(E) == 2) {
-    // 16-byte aligned rows (the DMA moves 16-byte units) and no key mask / bias: the 64-queries-per-wave kernels
-    const bool aligned = a.k_ts % 8 == 0 && a.v_ts % 8 == 0 && a.k_hs % 8 == 0 && a.v_hs % 8 == 0 && a.k_bs % 8 == 0 && a.v_bs % 8 == 0 &&
-                         ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0;
-    if (!a.kmask && !a.bias && !a.drop_thresh && aligned && a.Lk > 0) return launch_fwd64<E, DQ>(a, s);
+    // K / V rows the DMA can fetch and no key mask / bias: the 64-queries-per-wave kernel
+    const bool aligned = dma_rows16(a.k, a.k_bs, a.k_hs, a.k_ts) && dma_rows16(a.v, a.v_bs, a.v_hs, a.v_ts);
+    if (!a.kmask && !a.bias && !a.drop_thresh && aligned && a.Lk > 0) return launch_q64<E, DQ>(a, s);
   }
   return (a.kmask || a.bias || a.drop_thresh) ? launch_q1<E, D, DQ, true>(a, s) : launch_q1<E, D, DQ, false>(a, s);
 }
@@ -1229,8 +1129,8 @@ static int launch_dkv1(const AttnArgs& a, hipStream_t s);
 template <typename E, int D>
 static int launch_dkv(const AttnArgs& a, hipStream_t s) {
   if constexpr (D == 64 && sizeof(E) == 2) {      // Q / dO tiles by LDS-DMA: 16-byte aligned rows, 32-bit in-tile offsets
-    const bool aligned = a.q_ts % 8 == 0 && a.do_ts % 8 == 0 && a.q_hs % 8 == 0 && a.do_hs % 8 == 0 && a.q_bs % 8 == 0 && a.do_bs % 8 == 0 &&
-                         ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.dout % 16) == 0 && a.q_ts < (1 << 24) && a.do_ts < (1 << 24);
+    const bool aligned = dma_rows16(a.q, a.q_bs, a.q_hs, a.q_ts) && dma_rows16(a.dout, a.do_bs, a.do_hs, a.do_ts) &&
+                         a.q_ts < (1 << 24) && a.do_ts < (1 << 24);
     if (!a.kmask && !a.bias && !a.drop_thresh && aligned && a.Lq > 0) return launch_dkv1<E, D, false, true>(a, s);
   }
   return (a.kmask || a.bias || a.drop_thresh) ? launch_dkv1<E, D, true>(a, s) : launch_dkv1<E, D, false>(a, s);
@@ -1261,6 +1161,13 @@ static int dispatch_attn(const AttnArgs& a, int D, int what, hipStream_t s) {   
       if constexpr (sizeof(E) == 2) { if (what == 0) return launch_q<E, 256, false>(a, s); }
       return MXVL_ERR_UNSUPPORTED;
     default: return MXVL_ERR_UNSUPPORTED;
+  }
+}
+static int dispatch_attn(int io_dtype, const AttnArgs& a, int D, int what, hipStream_t s) {   // io_dtype: checked by fill_args
+  switch (io_dtype) {
+    case MXVL_F32: return dispatch_attn<float>(a, D, what, s);
+    case MXVL_BF16: return dispatch_attn<bf16_t>(a, D, what, s);
+    default: return dispatch_attn<f16_t>(a, D, what, s);
   }
 }
 
@@ -1304,12 +1211,7 @@ extern "C" int mxvl_attn_fwd(const mxvl_attn_desc* d, void* hip_stream) {
   if (!d->out) return MXVL_ERR_NULL;
   const int64_t al = d->io_dtype == MXVL_F32 ? 4 : 8;
   if (d->o_bs % al || d->o_hs % al || d->o_ts % al || (uintptr_t)d->out % 16) return MXVL_ERR_STRIDE;
-  hipStream_t s = (hipStream_t)hip_stream;
-  switch (d->io_dtype) {
-    case MXVL_F32: return dispatch_attn<float>(a, d->head_dim, 0, s);
-    case MXVL_BF16: return dispatch_attn<bf16_t>(a, d->head_dim, 0, s);
-    default: return dispatch_attn<f16_t>(a, d->head_dim, 0, s);
-  }
+  return dispatch_attn(d->io_dtype, a, d->head_dim, 0, (hipStream_t)hip_stream);
 }
 
 extern "C" int mxvl_attn_bwd(const mxvl_attn_bwd_desc* d, void* hip_stream) {
@@ -1327,14 +1229,8 @@ extern "C" int mxvl_attn_bwd(const mxvl_attn_bwd_desc* d, void* hip_stream) {
   a.dout = d->dout; a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.delta = (float*)d->delta;
   a.do_bs = d->dout_bs; a.do_hs = d->dout_hs; a.do_ts = d->dout_ts; a.dq_bs = d->dq_bs; a.dq_hs = d->dq_hs; a.dq_ts = d->dq_ts;
   a.dk_bs = d->dk_bs; a.dk_hs = d->dk_hs; a.dk_ts = d->dk_ts; a.dv_bs = d->dv_bs; a.dv_hs = d->dv_hs; a.dv_ts = d->dv_ts;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int D = d->fwd.head_dim;
   for (int what = 1; what <= 2; ++what) {   // dQ (also writes delta) first, dK/dV second: same stream, in order
-    switch (d->fwd.io_dtype) {
-      case MXVL_F32: rc = dispatch_attn<float>(a, D, what, s); break;
-      case MXVL_BF16: rc = dispatch_attn<bf16_t>(a, D, what, s); break;
-      default: rc = dispatch_attn<f16_t>(a, D, what, s); break;
-    }
+    rc = dispatch_attn(d->fwd.io_dtype, a, d->fwd.head_dim, what, (hipStream_t)hip_stream);
     if (rc != MXVL_OK) return rc;
   }
   return MXVL_OK;

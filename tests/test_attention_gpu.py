@@ -462,6 +462,32 @@ def test_attention_rows_without_keys_forward_backward(case, dtype):
         assert bool(no_query.any()), "the geometry has keys without queries"
 
 
+# The frame attn_q64_kernel's forward and dQ pass share (head_dim 64, 16-bit, no mask tensor): 256 queries per workgroup, 64 per
+# wave; 64-key tiles through a three-stage LDS-DMA ring -- tiles 0 and 1 are requested before the loop, tile kt + 2 inside it, a
+# ragged last tile re-reads row Lk - 1.  Hkv < H everywhere: the LDS-DMA dK / dV kernel changes head between its two buffers.
+Q64_EDGES = [
+    _case(1, 2, 1, 64, 64, 64, "none"),             # one tile, no ragged row: only the first request
+    _case(1, 2, 1, 65, 65, 64, "causal"),           # two tiles, the second with one valid row; the dK / dV query tile re-reads row Lq - 1
+    _case(1, 2, 1, 70, 128, 64, "none"),            # two full tiles; wave 1 holds 6 queries, waves 2 and 3 none (they keep the barriers)
+    _case(1, 2, 1, 129, 129, 64, "block_causal"),   # three tiles: the first request inside the loop
+    _case(2, 2, 1, 70, 192, 64, "causal"),          # three full tiles, decode-style offset
+    _case(1, 2, 1, 257, 193, 64, "causal"),         # four tiles: the ring reuses stage 0; rows 0..63 have no key; a second workgroup with one query
+    _case(1, 2, 1, 257, 256, 64, "none"),           # four full tiles
+    _case(1, 4, 2, 1, 193, 64, "causal"),           # a single query row; the dK / dV double buffer walks the GQA group
+]
+
+
+@gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("case", Q64_EDGES)
+def test_attention_64_queries_per_wave_frame_edges(case, dtype):
+    """Forward and the three gradients at the edges of the shared tile walk: finite, exactly zero where nothing is permitted, the
+    fp64 reference at this file's 16-bit tolerances."""
+    x, key_mask, bias, allow, got, ref = _baseline(case, dtype)
+    no_key, _ = _check(case, dtype, allow, got, ref, f"q64-edges {case}")
+    assert bool(no_key.any()) == (case[:5] == (1, 2, 1, 257, 193)), "only the Lq = Lk + 64 causal case has rows without keys"
+
+
 @gpu
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_attention_rows_without_keys_under_dropout(dtype):

@@ -140,10 +140,12 @@ def test_per_row_decode_attention_sums_scores_by_dpp(elt):
 
 
 def test_attention_dq64_kernel_has_no_scratch():
-    """attn_dq64_kernel (the dQ pass of the 4080-token block-causal attention): rounds 3-4 carried 12 bytes of scratch -- the epilogue's row
-    indices and the ragged-tile branch's lane index, stored before the key loop and reloaded behind it; both are re-derived from the
-    work-item id now."""
-    for name in ("attn_dq64_kernelINS_6bf16_tEEE", "attn_dq64_kernelINS_5f16_tEEE"):
+    """attn_q64_kernel<E, DQ = true> (the dQ pass of the 4080-token block-causal attention; a kernel of its own before the forward and
+    the dQ pass became one body): rounds 3-4 carried 12 bytes of scratch -- the epilogue's row indices and the ragged-tile branch's lane
+    index, stored before the key loop and reloaded behind it; both are re-derived from the work-item id now.  The forward
+    instantiations of the same body never had any."""
+    for name in ("attn_q64_kernelINS_6bf16_tELb1EE", "attn_q64_kernelINS_5f16_tELb1EE",
+                 "attn_q64_kernelINS_6bf16_tELb0EE", "attn_q64_kernelINS_5f16_tELb0EE"):
         assert not _scratch_ops(_body("attn.hip", name)), name
 
 
