@@ -31,7 +31,9 @@
  * a 4-element boundary (fp32: 16 bytes) and, for the 16-bit dtypes, on a 16-byte boundary (8 elements: strides % 8 == 0,
  * pointers % 16 == 0) -- forward and backward apply the same rule; rows that are only 8-byte aligned (e.g. seqlen % 8 == 4, or a
  * view starting 4 elements into its storage) run on the element-wise kernels (same results, several times slower), and
- * MXVL_SCAN_FOLD_BATCH returns MXVL_ERR_UNSUPPORTED for them.
+ * MXVL_SCAN_FOLD_BATCH returns MXVL_ERR_UNSUPPORTED for them.  The 16-byte rule covers the rows a kernel reads eight steps at a
+ * time: u, delta, z in both directions, dout and (by LDS-DMA) B, C in the backward; out, du, ddelta, dz and the forward's B, C move
+ * in 4-element vectors and only need the 4-element boundary.  Each direction decides for itself from the tensors it touches.
  * dstate 1 without z (VMamba / R2GenCSR SS2D, vmamba.py:294-312; the vendored oflex kernels' own test configuration): forward and
  * backward have kernels of their own (csrc/scan_n1.h, scan_n1_bwd.h) -- rows of the whole launch walked as one flat sequence
  * (forward) / pass-major per wave (backward), wave-wide DPP scans, no LDS tiles.  Taken when seqlen % 4 == 0 and the rows of u,
@@ -47,11 +49,13 @@
  *     behind one call (see the entry's comment below), not as one fused kernel.  Fusing the two projections into the scan prologue
  *     would make every channel tile of the backward re-derive dB / dC contributions of the projection (3x the fp32 atomics of
  *     mxvl_scan_bwd) for a GEMM share below half a percent of the step.
- *   * Tolerance of the scan entries against the reference's selective_scan_ref (KSS/test_selective_scan_easy.py:857-922), as the
- *     parity tests assert it: fp32 io -- |got - ref| <= 1e-4 * max(1, max|ref| / 32) + 1e-5 * |ref|, i.e. north_star's flat
- *     atol 1e-4 wherever |ref| < 32 and the same bound relative to the output scale beyond (the L = 4097 golden reaches 262:
- *     the C oracle itself needs that scaling against the reference's fp32 torch loop); bf16 / fp16 io -- the reference test's own
- *     rtol / atol (test_selective_scan.py: 3e-2 / 5e-2 bf16, 3e-3 / 5e-3 fp16).  Index / ordering entries (mxvl_row_gather,
+ *   * Tolerance of the scan entries: DESIGN.md, "Scan against float64" -- every output and gradient of mxvl_scan_fwd / mxvl_scan_bwd
+ *     is held to a per-element bound derived from the kernels' operation counts against a float64 recurrence, over every
+ *     instantiation the dispatch can launch (tests/test_scan_bounds_gpu.py).  The coarse parity bound against the reference's
+ *     selective_scan_ref (KSS/test_selective_scan_easy.py:857-922) stays what tests/test_scan_gpu.py asserts: fp32 io --
+ *     |got - ref| <= 1e-4 * max(1, max|ref| / 32) + 1e-5 * |ref| (the L = 4097 golden reaches 262: the C oracle itself needs that
+ *     scaling against the reference's fp32 torch loop); bf16 / fp16 io -- the reference test's own rtol / atol
+ *     (test_selective_scan.py: 3e-2 / 5e-2 bf16, 3e-3 / 5e-3 fp16).  Index / ordering entries (mxvl_row_gather,
  *     mxvl_cross_scan / _merge, mxvl_dir_gather, mxvl_patch_cols, mxvl_image_preprocess, mxvl_beam_step's choices) are bit-exact.
  *   * mxvl_add_layernorm_fwd / _bwd serve EVERY row width: cols = 256 * k, k in {1, 2, 3, 4, 6, 8} (256 .. 2048: every width of the
  *     reference's ARM / VisionMamba / ViT-MAE factories) a row per wave in registers, the narrow rows 64, 128, 192, 384 four / two rows
@@ -454,8 +458,10 @@ int mxvl_set_decode_gemm_wide(int on);
  *                         part; dstate-1 kernel: per pass).  Needs mxvl_scan_bwd_desc.workspace of
  *                         mxvl_scan_bwd_workspace_bytes(&fwd) bytes:
  *                             dpg = dim / n_groups, tile_rows = 16, passes = 1
- *                             if not MXVL_SCAN_FOLD_BATCH and dpg % 32 == 0 and batch * n_groups * (dpg / 32) >= 256: tile_rows = 32
- *                                 (the 8-wave walk; mxvl_set_scan_variant's forced walks count: 1 << 8 -> 32, 2 << 8 -> 16)
+ *                             if not MXVL_SCAN_FOLD_BATCH and dpg % 32 == 0 and batch * n_groups * (dpg / 32) >= 256
+ *                                and dstate <= (io_dtype == MXVL_F32 ? 19 : 40): tile_rows = 32
+ *                                 (the 8-wave walk, whose 32 parked rows fit the LDS up to that dstate;
+ *                                  mxvl_set_scan_variant's forced walks count: 1 << 8 -> 32 under the same dstate limit, 2 << 8 -> 16)
  *                             if dstate == 1 and z == NULL and not MXVL_SCAN_FOLD_BATCH:
  *                                 rw = min(max(batch * dim / 8192, 8), 64); while rw > 1 and dpg % (4 rw) != 0: rw -= 1
  *                                 if dpg % (4 rw) == 0: tile_rows = min(tile_rows, 4 rw), passes = ceil(seqlen / 256)
@@ -1013,14 +1019,19 @@ int mxvl_last_hip_error(void);
  * which libraries the test processes mapped), and forcing each instantiation of the scan kernels through the public entry points
  * is how tests/test_scan_gpu.py covers every variant against the reference goldens.  Thread-local, no effect on results.
  *
- * Scan kernel selection for tests / A-B measurements.  Bits 0..7: forward kernel shape (0 = automatic, unknown ids fall
- * back to automatic); bits 8..15: backward (0 automatic, 1 = 32-row / 8-wave workgroups, 2 = 16-row / 4-wave; other
- * ids fall back to automatic).  Every choice is a correct kernel.  Thread-local: it affects only calls made by the calling thread --
+ * Scan kernel selection for tests / A-B measurements.  Bits 0..7: forward kernel shape (0 = automatic; an id the
+ * dispatch does not know runs the one-wave form of the tiled kernel, which nothing else launches); bits 8..15: backward (0 automatic, 1 = 32-row / 8-wave workgroups where their LDS fits -- dstate <= 19 with
+ * fp32 rows, <= 40 with 16-bit ones -- 2 = 16-row / 4-wave; other ids fall back to automatic).  Every choice is a correct kernel.  Thread-local: it affects only calls made by the calling thread --
  * note that autograd runs backward on its own thread.  The product library ignores bits >= 16 (measurement builds,
  * -DMXVL_ABLATE, read ablation switches there). */
 void mxvl_set_scan_variant(int variant);
 /* name of the kernel the last mxvl_scan_fwd on this thread dispatched to (static string) */
 const char *mxvl_last_scan_kernel(void);
+/* name of the instantiation the last mxvl_scan_bwd on this thread launched (static string), every template choice in it:
+ * "scan_bwd<W4|W8,vec|scalar,N16|Nrt[,fold][,dma]>" (waves per workgroup; 4-/8-element or element-wise row access; compile-time
+ * dstate 16 or the run-time count; the folded walk; rows by LDS-DMA), "scan_n1_bwd<T4|T8[,dout_f32]>",
+ * "scan_n1_short_bwd<W1|W2[,dout_f32]>"; "none" before the first call.  A test hook like the one above. */
+const char *mxvl_last_scan_bwd_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -312,6 +312,7 @@ SIGNATURES = {
     "mxvl_scan_bwd_workspace_bytes": (_I64, [_P]),
     "mxvl_set_scan_variant": (None, [_I]),
     "mxvl_last_scan_kernel": (ctypes.c_char_p, []),
+    "mxvl_last_scan_bwd_kernel": (ctypes.c_char_p, []),
     "mxvl_state_update": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     # causal conv1d
     "mxvl_conv1d_fwd": _DESC,

@@ -20,6 +20,7 @@
 // du, ddelta, dz are fully written; dA, dB, dC, dD, ddelta_bias are accumulated into caller-zeroed fp32.
 
 #include "mxvl_common.h"
+#include <string>
 #include <type_traits>
 
 namespace mxvl {
@@ -1049,12 +1050,32 @@ static int n1_bwd_rw(int batch, int dim, int G) {
 
 static bool bwd_wide(int batch, int dim, int G, int L);
 
+// dynamic LDS of scan_bwd_kernel<io_t, NWAVES, ...>; dma_bc: + the raw B/C tile of the LDS-DMA prefetch, dma_rows: + its checkpoint entries
+static size_t bwd_lds_bytes(int N, int NWAVES, size_t esz, bool dma_bc, bool dma_rows) {
+  const size_t DT = (size_t)NWAVES * 4, CH = 128, NT = (size_t)NWAVES * 64;
+  return sizeof(float) * ((size_t)2 * N * CH + DT * 2 * 2 * CH + (size_t)3 * (DT + 1) * (N + 1) + DT * (N + 1) + NT + N) + 16 +
+         (size_t)4 * NT * 8 * esz + (dma_bc ? (size_t)2 * 16 * CH * esz : 0) + (dma_rows ? NT * sizeof(float) : 0);
+}
+constexpr size_t kBwdLdsMax = 160 * 1024;
+// the 8-wave walk parks twice the rows of the 4-wave one: its LDS fits a CU up to dstate 19 with fp32 rows, 40 with 16-bit ones.
+// Beyond, the dispatch and the deterministic workspace bound take the 16-row workgroups.
+static bool bwd_w8_fits(int N, int esz) { return bwd_lds_bytes(N, 8, (size_t)esz, esz == 2 && N == 16, esz == 2 && N == 16) <= kBwdLdsMax; }
+
+// mxvl_last_scan_bwd_kernel: the instantiation the last mxvl_scan_bwd of this thread launched, every template choice in the name
+static thread_local const char* g_last_bwd_kernel = "none";
+template <int NWAVES, bool VEC, int NS, bool FOLD, bool DMAR>
+static const char* bwd_kernel_name() {
+  static const std::string name = std::string("scan_bwd<W") + (NWAVES == 8 ? "8" : "4") + (VEC ? ",vec" : ",scalar") +
+                                  (NS == 16 ? ",N16" : ",Nrt") + (FOLD ? ",fold" : "") + (DMAR ? ",dma" : "") + ">";
+  return name.c_str();
+}
+
 // upper bounds of the slot counts over every kernel the dispatch may pick for this problem (the formula of include/mxvl.h)
-static void scan_det_bound(int batch, int dim, int L, int G, int N, bool has_z, bool fold, int& tiles, int& red) {
+static void scan_det_bound(int batch, int dim, int L, int G, int N, int esz, bool has_z, bool fold, int& tiles, int& red) {
   int tile_rows = 16, passes = 1;
   if (!fold) {                                   // the 8-wave walk of the general kernels owns 32 rows (a folded call: bounded by 16)
     const int v = mxvl_scan_bwd_variant();
-    if (v == 1 || (v != 2 && bwd_wide(batch, dim, G, L))) tile_rows = 32;
+    if ((v == 1 || (v != 2 && bwd_wide(batch, dim, G, L))) && bwd_w8_fits(N, esz)) tile_rows = 32;
   }
   const int rw = (N == 1 && !has_z && !fold) ? n1_bwd_rw(batch, dim, G) : 0;
   if (rw > 0) {
@@ -1181,6 +1202,8 @@ static int try_n1_bwd(const ScanBwdArgs& a_in, hipStream_t stream, bool& taken, 
   } else {
     hipLaunchKernelGGL((scan_n1_bwd_kernel<io_t, 4, NW, false>), grid, block, lds, stream, a, gm);
   }
+  g_last_bwd_kernel = T == 8 ? (a.out_f32 ? "scan_n1_bwd<T8,dout_f32>" : "scan_n1_bwd<T8>")
+                              : (a.out_f32 && esz == 2 ? "scan_n1_bwd<T4,dout_f32>" : "scan_n1_bwd<T4>");
   taken = true;
   return launch_status();
 }
@@ -1218,6 +1241,8 @@ static int try_n1_short_bwd(const ScanBwdArgs& a_in, hipStream_t stream, bool& t
     if (two) hipLaunchKernelGGL((scan_n1_short_bwd_kernel<io_t, 2, false>), grid, block, lds, stream, a);
     else hipLaunchKernelGGL((scan_n1_short_bwd_kernel<io_t, 1, false>), grid, block, lds, stream, a);
   }
+  g_last_bwd_kernel = a.out_f32 && esz == 2 ? (two ? "scan_n1_short_bwd<W2,dout_f32>" : "scan_n1_short_bwd<W1,dout_f32>")
+                                            : (two ? "scan_n1_short_bwd<W2>" : "scan_n1_short_bwd<W1>");
   taken = true;
   return launch_status();
 }
@@ -1225,12 +1250,9 @@ static int try_n1_short_bwd(const ScanBwdArgs& a_in, hipStream_t stream, bool& t
 template <typename io_t, int NWAVES, bool VEC, int NS, bool FOLD = false, bool DMAR = false>
 static int launch_bwd1(const ScanBwdArgs& a_in, hipStream_t stream, ScanDet* det) {
   ScanBwdArgs a = a_in;
-  constexpr int DT = NWAVES * 4, CH = 128, NT = NWAVES * 64;
-  const size_t lds = sizeof(float) * ((size_t)2 * a.N * CH + (size_t)DT * 2 * 2 * CH + (size_t)3 * (DT + 1) * (a.N + 1) + (size_t)DT * (a.N + 1) +
-                                      (size_t)NT + a.N) + 16 + (size_t)4 * NT * 8 * sizeof(io_t) +
-                     ((VEC && NS == 16 && sizeof(io_t) == 2 && (!FOLD || DMAR)) ? (size_t)2 * 16 * CH * sizeof(io_t) : 0) +      // + the raw B/C tile of the LDS-DMA prefetch
-                     (DMAR ? (size_t)NT * sizeof(float) : 0);                                                           // + its checkpoint entries
-  if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
+  constexpr int DT = NWAVES * 4, NT = NWAVES * 64;
+  const size_t lds = bwd_lds_bytes(a.N, NWAVES, sizeof(io_t), VEC && NS == 16 && sizeof(io_t) == 2 && (!FOLD || DMAR), DMAR);
+  if (lds > kBwdLdsMax) return MXVL_ERR_UNSUPPORTED;
   auto kern = scan_bwd_kernel<io_t, NWAVES, VEC, NS, FOLD, DMAR>;
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
@@ -1241,6 +1263,7 @@ static int launch_bwd1(const ScanBwdArgs& a_in, hipStream_t stream, ScanDet* det
     if (rc != MXVL_OK) return rc;
   }
   hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
+  g_last_bwd_kernel = bwd_kernel_name<NWAVES, VEC, NS, FOLD, DMAR>();
   return launch_status();
 }
 // dstate 16 (every Mamba block of the reference) takes the instantiation with the unrolled state loop
@@ -1288,7 +1311,7 @@ static int dispatch_bwd(const ScanBwdArgs& a, hipStream_t stream, ScanDet* det) 
     return launch_bwd1<io_t, 4, true, 16, true>(a, stream, det);
   }
   const int variant = mxvl_scan_bwd_variant();   // tests / A-B measurements: 0 automatic
-  const bool wide = variant == 1 ? true : variant == 2 ? false : bwd_wide(a.batch, a.dim, a.G, a.L);
+  const bool wide = (variant == 1 ? true : variant == 2 ? false : bwd_wide(a.batch, a.dim, a.G, a.L)) && bwd_w8_fits(a.N, (int)sizeof(io_t));
   if (wide) return a.vec_ok ? launch_bwd<io_t, 8, true>(a, stream, det) : launch_bwd<io_t, 8, false>(a, stream, det);
   return a.vec_ok ? launch_bwd<io_t, 4, true>(a, stream, det) : launch_bwd<io_t, 4, false>(a, stream, det);
 }
@@ -1307,9 +1330,11 @@ extern "C" int64_t mxvl_scan_bwd_workspace_bytes(const mxvl_scan_desc* f) {
   if (!g_deterministic) return 0;
   if (mxvl_scan_check(f) != MXVL_OK) return -1;
   int tiles, red;
-  scan_det_bound(f->batch, f->dim, f->seqlen, f->n_groups, f->dstate, f->z != nullptr, (f->flags & MXVL_SCAN_FOLD_BATCH) != 0, tiles, red);
+  scan_det_bound(f->batch, f->dim, f->seqlen, f->n_groups, f->dstate, f->io_dtype == MXVL_F32 ? 4 : 2, f->z != nullptr, (f->flags & MXVL_SCAN_FOLD_BATCH) != 0, tiles, red);
   return 4 * scan_det_floats(f->batch, f->dim, f->seqlen, f->n_groups, f->dstate, tiles, red);
 }
+
+extern "C" const char* mxvl_last_scan_bwd_kernel(void) { return g_last_bwd_kernel; }
 
 extern "C" int mxvl_scan_bwd(const mxvl_scan_bwd_desc* d, void* hip_stream) {
   if (!d) return MXVL_ERR_NULL;
@@ -1377,7 +1402,7 @@ extern "C" int mxvl_scan_bwd(const mxvl_scan_bwd_desc* d, void* hip_stream) {
   ScanDet det{};
   const bool deterministic = g_deterministic != 0;
   if (deterministic) {     // checked before anything is enqueued
-    scan_det_bound(a.batch, a.dim, a.L, a.G, a.N, a.z != nullptr, a.fold_magic != 0, det.max_tiles, det.max_red);
+    scan_det_bound(a.batch, a.dim, a.L, a.G, a.N, f->io_dtype == MXVL_F32 ? 4 : 2, a.z != nullptr, a.fold_magic != 0, det.max_tiles, det.max_red);
     if (!d->workspace) return MXVL_ERR_NULL;
     if ((uintptr_t)d->workspace % 4 != 0) return MXVL_ERR_STRIDE;
     if (d->workspace_bytes < 4 * scan_det_floats(a.batch, a.dim, a.L, a.G, a.N, det.max_tiles, det.max_red)) return MXVL_ERR_SHAPE;

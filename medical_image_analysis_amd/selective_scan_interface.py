@@ -124,6 +124,23 @@ def _fill_fwd(desc, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, la
     desc.out, desc.last_state, desc.ckpt = _abi.ptr(out), _abi.ptr(last_state), _abi.ptr(ckpt)
 
 
+def _fill_bwd(desc, u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout, du, ddelta, dz, dA, dB, dC, dD, ddelta_bias,
+              dout_f32=False, fold=False):
+    """mxvl_scan_bwd_desc: the forward inputs (no out, no last_state) and every gradient's pointer and strides; the workspace
+    fields are the caller's"""
+    _fill_fwd(desc.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, None, None, ckpt, dout_f32, fold)
+    desc.dout_bs, desc.dout_ds = dout.stride(0), dout.stride(1)
+    desc.du_bs, desc.du_ds = du.stride(0), du.stride(1)
+    desc.ddelta_bs, desc.ddelta_ds = ddelta.stride(0), ddelta.stride(1)
+    if dz is not None:
+        desc.dz_bs, desc.dz_ds = dz.stride(0), dz.stride(1)
+    desc.dB_bs, desc.dB_gs, desc.dB_ns = dB.stride(0), dB.stride(1), dB.stride(2)
+    desc.dC_bs, desc.dC_gs, desc.dC_ns = dC.stride(0), dC.stride(1), dC.stride(2)
+    desc.dout, desc.du, desc.ddelta, desc.dz = dout.data_ptr(), du.data_ptr(), ddelta.data_ptr(), _abi.ptr(dz)
+    desc.dA, desc.dB, desc.dC = dA.data_ptr(), dB.data_ptr(), dC.data_ptr()
+    desc.dD, desc.ddelta_bias = _abi.ptr(dD), _abi.ptr(ddelta_bias)
+
+
 def _ckpt_chunks(ckpt, batch, dim):
     """checkpoints per (batch element, channel) -- for the algorithmic byte count; a folded call's tensor is (dim, slots, N)"""
     if ckpt is None:
@@ -214,17 +231,7 @@ def scan_bwd_raw(u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout
     if fold and not _rows_16b(du, ddelta, dz):
         raise RuntimeError("selective_scan backward of a folded forward needs 16-byte aligned rows for du / ddelta / dz")
     desc = _abi.ScanBwdDesc()
-    _fill_fwd(desc.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, None, None, ckpt, dout_f32, fold)
-    desc.dout_bs, desc.dout_ds = dout.stride(0), dout.stride(1)
-    desc.du_bs, desc.du_ds = du.stride(0), du.stride(1)
-    desc.ddelta_bs, desc.ddelta_ds = ddelta.stride(0), ddelta.stride(1)
-    if dz is not None:
-        desc.dz_bs, desc.dz_ds = dz.stride(0), dz.stride(1)
-    desc.dB_bs, desc.dB_gs, desc.dB_ns = dB.stride(0), dB.stride(1), dB.stride(2)
-    desc.dC_bs, desc.dC_gs, desc.dC_ns = dC.stride(0), dC.stride(1), dC.stride(2)
-    desc.dout, desc.du, desc.ddelta, desc.dz = dout.data_ptr(), du.data_ptr(), ddelta.data_ptr(), _abi.ptr(dz)
-    desc.dA, desc.dB, desc.dC = dA.data_ptr(), dB.data_ptr(), dC.data_ptr()
-    desc.dD, desc.ddelta_bias = _abi.ptr(dD), _abi.ptr(dbias)
+    _fill_bwd(desc, u, delta, A, B, C, D, z, delta_bias, delta_softplus, ckpt, dout, du, ddelta, dz, dA, dB, dC, dD, dbias, dout_f32, fold)
     desc.workspace, desc.workspace_bytes = None, 0     # default mode: ignored (dB / dC leave as fp32 atomics)
     nbytes = _abi.det_workspace_bytes("mxvl_scan_bwd_workspace_bytes", desc.fwd)
     if nbytes:       # deterministic mode: private slots + a fold in index order (include/mxvl.h mxvl_set_deterministic)

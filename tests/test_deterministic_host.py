@@ -116,7 +116,7 @@ def _scan_ws_formula(batch, dim, L, N, G, z, fold):
     """the formula of include/mxvl.h (mxvl_set_deterministic), restated"""
     dpg = dim // G
     tile_rows, passes = 16, 1
-    if not fold and dpg % 32 == 0 and batch * G * (dpg // 32) >= 256:
+    if not fold and dpg % 32 == 0 and batch * G * (dpg // 32) >= 256 and N <= 40:    # 16-bit rows (_scan_desc): dstate <= 40
         tile_rows = 32
     if N == 1 and not z and not fold:
         rw = min(max(batch * dim // 8192, 8), 64)
@@ -131,6 +131,8 @@ def _scan_ws_formula(batch, dim, L, N, G, z, fold):
 SCAN_SHAPES = [(3, 192, 300, 16, 2, True, False),                 # multi-tile, multi-batch, grouped: 6 tiles of 16 rows per group
                (16, 2048, 4080, 16, 1, True, False),              # the ARM-large step: the 8-wave walk, 64 tiles of 32 rows
                (2, 2048, 4096, 16, 1, True, False),               # 128 32-row tiles: too few for the 8-wave walk, 128 tiles of 16 rows
+               (16, 2048, 200, 40, 1, True, False),               # the last dstate whose 32 parked rows fit the LDS: the 8-wave walk
+               (16, 2048, 200, 48, 1, True, False),               # the 8-wave walk's LDS does not fit: 128 tiles of 16 rows
                (18, 96, 200, 16, 1, True, True),                  # folded
                (3, 96, 1100, 1, 1, False, False),                 # dstate 1 without z: rw 8, 16-row bound, 5 passes of 256 steps
                (2, 24, 520, 1, 2, False, False),                  # dstate 1, 12 channels per group: rw 3 -> 12-row tiles
