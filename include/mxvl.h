@@ -359,9 +359,31 @@ typedef struct mxvl_decode_attn_desc {
                                (the prompt, the common generated prefix) are read once for all of them; both products run on the
                                matrix cores and the probabilities are rounded to bf16 before the second one (softmax(...).to(bf16) @ V
                                of the modules); needs rows * n_kv_heads * max_len * head_dim < 2^31 (32-bit cache offsets) */
-  int32_t dtype;            /* ABI v8: mxvl_dtype of qkv, the caches, out, q_rope (0 = MXVL_BF16); | MXVL_KV_FP8: the caches are E4M3 bytes */
+  int32_t dtype;            /* ABI v8: mxvl_dtype of qkv, the caches, out, q_rope (0 = MXVL_BF16); | MXVL_KV_FP8: the caches are E4M3 bytes;
+                               | MXVL_QK_NORM: the descriptor is the head of a mxvl_decode_attn_qknorm_desc and qkv is normalised in place */
   const void *kv_scale;     /* with MXVL_KV_FP8 only (never read otherwise): device, two fp32 -- the K scale and the V scale of this layer */
 } mxvl_decode_attn_desc;
+/* QK-norm (Qwen3): `dtype | MXVL_QK_NORM`.  The new token's q and k heads pass through a per-head RMSNorm over head_dim before the
+ * rotation, with the rounding points of Qwen2RMSNorm / mxvl_decode_rmsnorm -- per (row, head):
+ *   y = dtype( dtype( x * rsqrt(mean_fp32(x^2) + qk_norm_eps) ) * weight ),   weight = q_norm_weight (q heads) / k_norm_weight (k heads)
+ * v is untouched; RoPE, the cache append and the attention then run on y exactly as they run on x without the flag (with
+ * MXVL_KV_FP8: the normalised, rotated key is what gets encoded; the scale rule is unchanged).  The entry launches one small kernel
+ * in front of the attention kernel -- a wave per (row, head), 16-byte accesses -- that normalises the q and k segments of `qkv` IN
+ * PLACE: with the flag `qkv` is read AND written (the caller's scratch row; afterwards it holds y | y | v), and the attention kernels
+ * are the ones of the unflagged call, bit for bit.  Both launches go to `hip_stream`, nothing is synchronised: capturable as before.
+ * The three fields TRAIL the descriptor: a caller that sets the flag passes the longer mxvl_decode_attn_qknorm_desc declared below through the same
+ * pointer, its first member being the descriptor; they are read only behind the flag, so every caller built against
+ * mxvl_decode_attn_desc alone stays valid as it is (the argument of kv_scale above), and no ABI version is spent.
+ * A NULL q_norm_weight / k_norm_weight is MXVL_ERR_NULL, qkv or a weight that is not 16-byte aligned MXVL_ERR_UNSUPPORTED; `dtype &
+ * ~(MXVL_KV_FP8 | MXVL_QK_NORM)` is validated as `dtype` was, so the flag beside a weight-format flag is MXVL_ERR_DTYPE -- all before
+ * any launch.  Every other decode entry refuses the flag with MXVL_ERR_DTYPE (in mxvl_gemv_desc.dtype the bit is no weight format). */
+#define MXVL_QK_NORM 0x2000
+typedef struct mxvl_decode_attn_qknorm_desc {
+  mxvl_decode_attn_desc attn;    /* dtype carries MXVL_QK_NORM; qkv is overwritten in its q and k segments */
+  const void *q_norm_weight;     /* (head_dim) in the activation dtype: self_attn.q_norm.weight */
+  const void *k_norm_weight;     /* (head_dim) in the activation dtype: self_attn.k_norm.weight */
+  float qk_norm_eps;
+} mxvl_decode_attn_qknorm_desc;
 
 /*
  * mxvl_decode_cross_attn (ABI v3): the gated image cross-attention of a hybrid decoder layer for one new token per row --

@@ -23,6 +23,7 @@ MXVL_W_MXFP4 = 0x200     # mxvl_gemv_desc.dtype flag: W / W2 are packed E2M1 cod
 MXVL_W_FP8 = 0x800       # mxvl_gemv_desc.dtype flag: W / W2 are OCP E4M3 codes (N, K), w_scale / w2_scale their fp32 row scales (N)
 MXVL_W_INT4 = 0x1000     # mxvl_gemv_desc.dtype flag: W / W2 are packed unsigned int4 codes (N, K / 2), w_scale / w2_scale (N, K / 128) words: fp16 group scale | zero point << 16
 MXVL_KV_FP8 = 0x400     # mxvl_decode_attn_desc.dtype flag: k_cache / v_cache are OCP E4M3 bytes, kv_scale their two power-of-two scales
+MXVL_QK_NORM = 0x2000   # mxvl_decode_attn_desc.dtype flag: the descriptor heads a DecodeAttnQkNormDesc; q / k heads are RMS-normalised in place in qkv
 SCAN_DELTA_SOFTPLUS = 1
 SCAN_OUT_F32 = 2          # out / dout fp32 whatever io_dtype is (the oflex i16o32 mode)
 SCAN_FOLD_BATCH = 4       # the batch folded into the sequence (short rows; ask mxvl_scan_fold_ok)
@@ -161,6 +162,11 @@ class DecodeAttnDesc(ctypes.Structure):
         ("beams", c_int32), ("dtype", c_int32),
         ("kv_scale", c_void_p),
     ]
+
+
+class DecodeAttnQkNormDesc(ctypes.Structure):
+    """mxvl_decode_attn_qknorm_desc: what mxvl_decode_attn reads through its descriptor pointer when attn.dtype carries MXVL_QK_NORM"""
+    _fields_ = [("attn", DecodeAttnDesc), ("q_norm_weight", c_void_p), ("k_norm_weight", c_void_p), ("qk_norm_eps", ctypes.c_float)]
 
 
 GATE_TANH, GATE_WARM_TANH = 1, 2

@@ -941,17 +941,77 @@ static int launch_gemv_rows(const GemvArgs& a, hipStream_t s) {
   }
 }
 
+// MXVL_QK_NORM: the per-head RMSNorm of the new token's q and k heads (Qwen3Attention's q_norm / k_norm), in place in the qkv row and
+// in front of the attention kernel -- y = dtype( dtype(x * rsqrt(mean(x^2) + eps)) * g ), the rounding points of decode_rmsnorm_kernel
+// (decode_gemm.h) over head_dim columns.  A pass of its own, not a branch of the attention kernels: those stay the instruction
+// streams they are (the beams kernel has no registers to spare), and a k head is normalised once here, not once per query head of
+// its group.  One wave per (row, head) over the H + Hkv heads that take a gain (the k heads follow the q heads in the row, so
+// head h starts at column h * D either way); lane l < D / 8 owns columns 8 l .. 8 l + 7 with one 16-byte load and one 16-byte
+// store, the other lanes add zeros to the 64-lane butterfly.  Four waves per workgroup, no LDS, no barrier.
+struct QkNormArgs {
+  int rows, H, Hkv;
+  float eps;
+  uint16_t* qkv;             // (rows, (H + 2*Hkv) * D): q and k segments rewritten, v left alone
+  const uint16_t *qg, *kg;   // (D) gains of the q heads / the k heads
+};
+constexpr int kQkNormWaves = 4;
+template <typename E, int D>
+__global__ __launch_bounds__(kQkNormWaves * 64) void decode_qk_norm_kernel(const QkNormArgs p) {
+  constexpr int LPR = D / 8;
+  const int lane = threadIdx.x & 63, heads = p.H + p.Hkv;
+  const int unit = blockIdx.x * kQkNormWaves + (threadIdx.x >> 6);   // (row, head): the same for every lane of a wave
+  if (unit >= p.rows * heads) return;
+  const int m = unit / heads, h = unit - m * heads;
+  const bool on = lane < LPR;
+  const int c = on ? lane * 8 : 0;                                   // unconditional loads (clamped): nothing waits behind a branch
+  uint16_t* x = p.qkv + (size_t)m * (p.H + 2 * p.Hkv) * D + (size_t)h * D;
+  const uint4 xr = *(const uint4*)(x + c);
+  const uint4 gr = *(const uint4*)((h < p.H ? p.qg : p.kg) + c);
+  const uint32_t w[4] = {xr.x, xr.y, xr.z, xr.w}, gw[4] = {gr.x, gr.y, gr.z, gr.w};
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float a = E::f((uint16_t)w[j]), b = E::f((uint16_t)(w[j] >> 16));
+    s = fmaf(a, a, fmaf(b, b, s));
+  }
+  s = on ? s : 0.0f;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  const float rstd = rsqrtf(s / (float)D + p.eps);
+  if (on) {
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float a = E::rr(E::f((uint16_t)w[j]) * rstd) * E::f((uint16_t)gw[j]);
+      const float b = E::rr(E::f((uint16_t)(w[j] >> 16)) * rstd) * E::f((uint16_t)(gw[j] >> 16));
+      o[j] = (uint32_t)E::r(a) | ((uint32_t)E::r(b) << 16);
+    }
+    *(uint4*)(x + c) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // per call: the dynamic-LDS attribute belongs to the (kernel, device) pair, and a process may drive several devices
-static int launch_attn(void (*kern)(const AttnArgs), dim3 grid, dim3 block, size_t lds, hipStream_t s, const AttnArgs& a) {
+// `pre` (MXVL_QK_NORM; else null): the in-place q/k norm, enqueued here -- behind every check that can still refuse the call -- and
+// ahead of the attention kernel on the same stream
+static int launch_attn(void (*kern)(const AttnArgs), dim3 grid, dim3 block, size_t lds, hipStream_t s, const AttnArgs& a,
+                       void (*pre)(const QkNormArgs) = nullptr, const QkNormArgs* qn = nullptr) {
   if (lds > 64 * 1024 && hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != MXVL_OK)
     return MXVL_ERR_LAUNCH;
+  if (pre) {
+    const int units = qn->rows * (qn->H + qn->Hkv);
+    hipLaunchKernelGGL(pre, dim3((units + kQkNormWaves - 1) / kQkNormWaves), dim3(kQkNormWaves * 64), 0, s, *qn);
+    if (const int rc = launch_status(); rc != MXVL_OK) return rc;
+  }
   hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   return launch_status();
 }
 
 // KV = Kv16<E> or KvE4m3<E>.  head_dim 256 is instantiated for the 16-bit cache only (mxvl_decode_attn refuses it for the E4M3 cache).
+// qn (MXVL_QK_NORM; else null): the q/k norm that goes in front of whichever attention kernel is picked
 template <typename E, typename KV>
-static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
+static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s, const QkNormArgs* qn = nullptr) {
+  void (*pre)(const QkNormArgs) = nullptr;
+  if (qn) pre = a.D == 64 ? decode_qk_norm_kernel<E, 64> : a.D == 128 ? decode_qk_norm_kernel<E, 128> : decode_qk_norm_kernel<E, 256>;
   constexpr bool kv16 = !KV::scaled;
   constexpr size_t EB = sizeof(typename KV::cache_t);    // bytes per cache element
   if (!kv16 && a.D == 256) return MXVL_ERR_UNSUPPORTED;
@@ -971,7 +1031,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
     if (lds > 160 * 1024) return MXVL_ERR_UNSUPPORTED;
     const dim3 grid(a.H, a.rows / nb), block(nw * 64);
 #define MXVL_ATTN_BEAMS(DD, NB) \
-  return launch_attn(nw == 8 ? decode_attn_beams_mfma_kernel<E, KV, DD, NB, (DD <= 128 ? 8 : 4)> : decode_attn_beams_mfma_kernel<E, KV, DD, NB, 4>, grid, block, lds, s, a)
+  return launch_attn(nw == 8 ? decode_attn_beams_mfma_kernel<E, KV, DD, NB, (DD <= 128 ? 8 : 4)> : decode_attn_beams_mfma_kernel<E, KV, DD, NB, 4>, grid, block, lds, s, a, pre, qn)
 #define MXVL_ATTN_BEAMS_D(NB) \
   switch (a.D) { \
     case 64: MXVL_ATTN_BEAMS(64, NB); \
@@ -1004,7 +1064,7 @@ static int launch_decode_attn(const AttnArgs& a, int beams, hipStream_t s) {
   do { \
     void (*kern)(const AttnArgs) = depth == 4 ? decode_attn_kernel<E, KV, DD, 8, 4> : decode_attn_kernel<E, KV, DD, 8, 2>; \
     if constexpr (kv16) if (nw == 16) kern = depth == 4 ? decode_attn_kernel<E, KV, DD, 16, 4> : decode_attn_kernel<E, KV, DD, 16, 2>; \
-    return launch_attn(kern, grid, block, lds, s, a); \
+    return launch_attn(kern, grid, block, lds, s, a, pre, qn); \
   } while (0)
   switch (a.D) {
     case 64: MXVL_ATTN_ROW(64);
@@ -1067,14 +1127,18 @@ int mxvl_decode_gemv(const mxvl_gemv_desc* d, void* hip_stream) {
 int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
   if (!d || !d->qkv || !d->cos || !d->sin || !d->k_cache || !d->v_cache || !d->slot_table || !d->pos || !d->mask || !d->out)
     return MXVL_ERR_NULL;
-  // MXVL_KV_FP8 is the one flag this entry knows: a weight flag (or anything else) beside it leaves a value no dtype check accepts
+  // MXVL_KV_FP8 and MXVL_QK_NORM are the flags this entry knows: a weight flag (or anything else) beside them leaves a value no dtype check accepts
   const bool kv8 = (d->dtype & MXVL_KV_FP8) != 0;         // kv_scale exists in the caller's struct only behind the flag
-  const int32_t dt = d->dtype & ~MXVL_KV_FP8;
+  const bool qkn = (d->dtype & MXVL_QK_NORM) != 0;        // ... and so do the fields that trail the descriptor (mxvl_decode_attn_qknorm_desc)
+  const int32_t dt = d->dtype & ~(MXVL_KV_FP8 | MXVL_QK_NORM);
   if (!decode_dtype_ok(dt)) return MXVL_ERR_DTYPE;
   if (kv8 && !d->kv_scale) return MXVL_ERR_NULL;
+  const mxvl_decode_attn_qknorm_desc* const dq = qkn ? (const mxvl_decode_attn_qknorm_desc*)d : nullptr;
+  if (qkn && (!dq->q_norm_weight || !dq->k_norm_weight)) return MXVL_ERR_NULL;
   if (d->rows <= 0 || d->n_heads <= 0 || d->n_kv_heads <= 0 || d->n_heads % d->n_kv_heads != 0) return MXVL_ERR_SHAPE;
   if (d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256) return MXVL_ERR_UNSUPPORTED;
   if (kv8 && d->head_dim == 256) return MXVL_ERR_UNSUPPORTED;   // no fp8-cache kernel at head_dim 256
+  if (qkn && (((uintptr_t)d->qkv | (uintptr_t)dq->q_norm_weight | (uintptr_t)dq->k_norm_weight) & 15)) return MXVL_ERR_UNSUPPORTED;   // 16-byte accesses
   AttnArgs a;
   a.rows = d->rows; a.H = d->n_heads; a.Hkv = d->n_kv_heads; a.D = d->head_dim; a.max_len = d->max_len;
   a.scale = d->scale; a.qkv = (const uint16_t*)d->qkv; a.cosv = (const float*)d->cos; a.sinv = (const float*)d->sin;
@@ -1083,10 +1147,16 @@ int mxvl_decode_attn(const mxvl_decode_attn_desc* d, void* hip_stream) {
   a.q_rope = (uint16_t*)d->q_rope;
   a.ablate = MXVL_ABL_ENV("MXVL_ATTN_ABLATE");
   a.kvs = kv8 ? (const float*)d->kv_scale : nullptr;
+  QkNormArgs n;
+  if (qkn) {
+    n.rows = d->rows; n.H = d->n_heads; n.Hkv = d->n_kv_heads; n.eps = dq->qk_norm_eps;
+    n.qkv = (uint16_t*)d->qkv; n.qg = (const uint16_t*)dq->q_norm_weight; n.kg = (const uint16_t*)dq->k_norm_weight;
+  }
+  const QkNormArgs* const qn = qkn ? &n : nullptr;
   const hipStream_t s = (hipStream_t)hip_stream;
   const bool f16 = decode_dtype(dt) == MXVL_F16;
-  if (kv8) return f16 ? launch_decode_attn<EltF16, KvE4m3<EltF16>>(a, d->beams, s) : launch_decode_attn<EltBf16, KvE4m3<EltBf16>>(a, d->beams, s);
-  return f16 ? launch_decode_attn<EltF16, Kv16<EltF16>>(a, d->beams, s) : launch_decode_attn<EltBf16, Kv16<EltBf16>>(a, d->beams, s);
+  if (kv8) return f16 ? launch_decode_attn<EltF16, KvE4m3<EltF16>>(a, d->beams, s, qn) : launch_decode_attn<EltBf16, KvE4m3<EltBf16>>(a, d->beams, s, qn);
+  return f16 ? launch_decode_attn<EltF16, Kv16<EltF16>>(a, d->beams, s, qn) : launch_decode_attn<EltBf16, Kv16<EltBf16>>(a, d->beams, s, qn);
 }
 
 int mxvl_decode_prologue(const mxvl_decode_prologue_desc* d, void* hip_stream) {

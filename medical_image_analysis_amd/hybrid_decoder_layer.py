@@ -53,20 +53,46 @@ class Qwen2RMSNorm(nn.Module):
         return f"{tuple(self.weight.shape)}, eps={self.variance_epsilon}"
 
 
+def _llama3_inv_freq(inv_freq, scaling):
+    """The `llama3` frequency scaling (Llama-3.1 / 3.2), HF modeling_rope_utils._compute_llama3_parameters restated operation for
+    operation so that the result is HF's bits: wavelengths above original_max / low_freq_factor are divided by `factor`, those below
+    original_max / high_freq_factor stay, the band between is interpolated."""
+    import math
+    factor, low, high = scaling["factor"], scaling["low_freq_factor"], scaling["high_freq_factor"]
+    old_len = scaling["original_max_position_embeddings"]
+    low_wavelen, high_wavelen = old_len / low, old_len / high
+    wavelen = 2 * math.pi / inv_freq
+    scaled = torch.where(wavelen > low_wavelen, inv_freq / factor, inv_freq)
+    smooth = (old_len / wavelen - low) / (high - low)
+    smoothed = (1 - smooth) * scaled / factor + smooth * scaled
+    medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+    return torch.where(medium, smoothed, scaled)
+
+
 class Qwen2RotaryEmbedding(nn.Module):
-    """Default (unscaled) RoPE: inv_freq = theta^(-2i/d); returns cos/sin of shape (B, T, head_dim)."""
+    """RoPE: inv_freq = theta^(-2i/d), unscaled (`rope_scaling` None / "default") or with the `llama3` scaling; returns cos/sin of
+    shape (B, T, head_dim).  attention_scaling is 1.0 for both."""
 
     def __init__(self, dim=None, max_position_embeddings=2048, base=10000, device=None, config=None):
         super().__init__()
+        rope_type, scaling = "default", None
         if config is not None:
             base = getattr(config, "rope_theta", base)
             dim = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
             max_position_embeddings = config.max_position_embeddings
             scaling = getattr(config, "rope_scaling", None)
-            if scaling is not None and scaling.get("rope_type", scaling.get("type", "default")) != "default":
-                raise NotImplementedError("only the default RoPE is built (the reference's launch configs use it)")
+            if scaling is not None:
+                rope_type = scaling.get("rope_type", scaling.get("type", "default"))
+            if rope_type not in ("default", "llama3"):
+                raise NotImplementedError(f"rope_scaling type {rope_type!r}: only the default RoPE and the llama3 scaling are built")
         self.max_seq_len_cached = max_position_embeddings
+        self.rope_type = rope_type
         inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64).float().to(device) / dim))
+        if rope_type == "llama3":
+            missing = [k for k in ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings") if k not in scaling]
+            if missing:
+                raise ValueError(f"rope_scaling of type 'llama3' lacks {missing}")
+            inv_freq = _llama3_inv_freq(inv_freq, scaling)
         self.register_buffer("inv_freq", inv_freq, persistent=False)
         self.attention_scaling = 1.0
 
@@ -162,14 +188,14 @@ class Qwen2HybridAttention(nn.Module):
         self.layer_idx = layer_idx
         self.hidden_size = config.hidden_size
         self.num_heads = config.num_attention_heads
-        self.head_dim = self.hidden_size // self.num_heads
+        self.head_dim = getattr(config, "head_dim", None) or self.hidden_size // self.num_heads
         self.num_key_value_heads = config.num_key_value_heads
         self.num_key_value_groups = self.num_heads // self.num_key_value_heads
         self.max_position_embeddings = config.max_position_embeddings
         self.rope_theta = getattr(config, "rope_theta", 10000.0)
         self.is_causal = True
         self.attention_dropout = getattr(config, "attention_dropout", 0.0)
-        if self.head_dim * self.num_heads != self.hidden_size:
+        if getattr(config, "head_dim", None) is None and self.head_dim * self.num_heads != self.hidden_size:
             raise ValueError(f"hidden_size must be divisible by num_heads (got `hidden_size`: {self.hidden_size}"
                              f" and `num_heads`: {self.num_heads}).")
         self.q_proj = nn.Linear(self.hidden_size, self.num_heads * self.head_dim, bias=True)
@@ -177,13 +203,17 @@ class Qwen2HybridAttention(nn.Module):
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=True)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
         self.rotary_emb = Qwen2RotaryEmbedding(config=config)
+        if getattr(config, "qk_norm", False):
+            # Qwen3: RMSNorm over head_dim on every q and k head, ahead of the rotation (HF Qwen3Attention's keys)
+            self.q_norm = Qwen2RMSNorm(self.head_dim, eps=config.rms_norm_eps)
+            self.k_norm = Qwen2RMSNorm(self.head_dim, eps=config.rms_norm_eps)
         self.is_hyper_enabled = is_hyper_enabled
         if is_hyper_enabled:
             self.gating_type = gating_type
             self.cross_attention_implementation = cross_attn_implementation
             self.cross_attn_kv_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim * 2, bias=True)
             if gating_type.startswith("whole-dynamic"):
-                layers = [nn.Linear(self.hidden_size, 1)]
+                layers = [nn.Linear(self.num_heads * self.head_dim, 1)]     # the attention output's width (= hidden_size unless head_dim is given)
                 if "tanh" in gating_type:
                     layers.append(nn.Tanh())
                 self.cross_attn_gate_proj = nn.Sequential(*layers)
@@ -251,12 +281,24 @@ class Qwen2HybridAttention(nn.Module):
         ext[text_mask] = ctx[valid] * gate
         return text_state + ext
 
+    @staticmethod
+    def _qk_norm(norm, x):
+        """q_norm / k_norm on the (B, T, heads, head_dim) view.  With a frozen gain a HIP device runs it through the frozen-weight
+        kernel (csrc/llm_ops.hip: prompt prefill, forward under grad -- it has a backward --, forward_frozen_autocast, where it
+        returns the dtype the attention reads); the CPU, and a gain that trains, keep the module expression."""
+        if fused_ops.rms_norm_supported(x, norm.weight):
+            return fused_ops.rms_norm_frozen(x, norm.weight, norm.variance_epsilon)
+        return norm(x)
+
     def forward(self, hidden_states, visual_hidden_states=None, token_type=None, attention_mask=None,
                 text2visual_attention_mask=None, position_ids=None, past_key_value=None, output_attentions=False,
                 use_cache=False, cache_position=None, position_embeddings: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         bsz, q_len, _ = hidden_states.shape
-        q = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
-        k = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
+        q = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim)
+        k = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        if hasattr(self, "q_norm"):
+            q, k = self._qk_norm(self.q_norm, q), self._qk_norm(self.k_norm, k)
+        q, k = q.transpose(1, 2), k.transpose(1, 2)
         v = self.v_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
         if position_embeddings is None:
             if position_ids is None:
@@ -289,7 +331,7 @@ class Qwen2HybridAttention(nn.Module):
                 raise RuntimeError("Qwen2HybridAttention: pass the (B, kv_len) padding mask; an additive 4-D mask has no HIP kernel")
             km = None if attention_mask is None else attention_mask[:, :kv_len].bool()
             attn = flash.attention(q, k, v, mask="causal", key_mask=km, dropout_p=p_drop)
-            attn_output = attn.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
+            attn_output = attn.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)
             return self._finish(attn_output, q, visual_hidden_states, token_type, text2visual_attention_mask, past_key_value)
         # CPU tensors only (host-side tests): the reference expression
         kf, vf = repeat_kv(k, self.num_key_value_groups), repeat_kv(v, self.num_key_value_groups)
@@ -302,7 +344,7 @@ class Qwen2HybridAttention(nn.Module):
             else:  # additive 4-D mask from HF: 0 = keep
                 mask = mask & (attention_mask[:, :, :, :kv_len] == 0)
         attn = F.scaled_dot_product_attention(q, kf, vf, attn_mask=mask, dropout_p=p_drop)
-        attn_output = attn.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
+        attn_output = attn.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)
         return self._finish(attn_output, q, visual_hidden_states, token_type, text2visual_attention_mask, past_key_value)
 
     def _finish(self, attn_output, q, visual_hidden_states, token_type, text2visual_attention_mask, past_key_value):

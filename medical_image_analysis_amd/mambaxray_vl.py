@@ -51,9 +51,52 @@ def _get(args, name, default=None):
     return getattr(args, name, default)
 
 
+_MOE_MODEL_TYPES = ("qwen2_moe", "qwen3_moe", "qwen3_next", "mixtral", "llama4", "deepseek_v2", "deepseek_v3")
+_ROPE_KEYS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
+
+
+def _family_config(raw, where):
+    """What a published `config.json` says beyond _CFG_KEYS, as ReportDecoder arguments: `head_dim` (Qwen3: 128 whatever hidden_size /
+    num_attention_heads is), `model_type` "qwen3" -> qk_norm, and the RoPE scaling in either spelling -- `rope_scaling` (transformers 4)
+    or `rope_parameters` (transformers 5, which also carries `rope_theta`).  A config that asks for something this build does not
+    implement raises and names the key: loading it anyway would decode on the kernels, fluently and wrong."""
+    out = {}
+    model_type = raw.get("model_type")
+    if model_type in _MOE_MODEL_TYPES or raw.get("num_experts") or raw.get("num_local_experts"):
+        raise NotImplementedError(f"{where}: config.json `model_type` {model_type!r} is a mixture-of-experts family; the report decoder builds dense decoders only")
+    if raw.get("use_sliding_window"):
+        raise NotImplementedError(f"{where}: config.json `use_sliding_window` is true; sliding-window attention is not built")
+    qk_norm = model_type == "qwen3"
+    if qk_norm and raw.get("attention_bias"):
+        raise NotImplementedError(f"{where}: config.json `attention_bias` is true on a QK-norm model (`model_type` 'qwen3'): the combination is not built")
+    if qk_norm:
+        out["qk_norm"] = True
+    if raw.get("head_dim") is not None:
+        out["head_dim"] = int(raw["head_dim"])
+    for key in ("rope_parameters", "rope_scaling"):
+        rope = raw.get(key)
+        if not rope:
+            continue
+        if any(isinstance(v, dict) for v in rope.values()):
+            raise NotImplementedError(f"{where}: config.json `{key}` holds one RoPE per layer type; one RoPE for all layers is built")
+        if key == "rope_parameters" and rope.get("rope_theta") is not None:
+            out["rope_theta"] = float(rope["rope_theta"])
+        rope_type = rope.get("rope_type", rope.get("type", "default"))
+        if rope_type == "default":
+            continue
+        if rope_type != "llama3":
+            raise NotImplementedError(f"{where}: config.json `{key}` asks for RoPE type {rope_type!r}; the default RoPE and 'llama3' are built")
+        missing = [k for k in _ROPE_KEYS if k not in rope]
+        if missing:
+            raise ValueError(f"{where}: config.json `{key}` of type 'llama3' lacks {missing}")
+        out["rope_scaling"] = dict({k: rope[k] for k in _ROPE_KEYS}, rope_type="llama3")
+    return out
+
+
 def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, **overrides):
     """`source`: None / "llama2-7b" / "qwen1.5-1.8b" (random init at the published shapes), a dict of config values, or
-    a local HF checkpoint directory (config.json + *.safetensors).  low_resource: the name of a quantised format (WEIGHT_FORMATS) the
+    a local HF checkpoint directory (config.json + *.safetensors; Llama-2 / Llama-3.x / Qwen1.5 / Qwen2 / Qwen3 -- _family_config
+    reads `head_dim`, `model_type` and the RoPE scaling and refuses what is not built).  low_resource: the name of a quantised format (WEIGHT_FORMATS) the
     layer projections are stored in after loading (ReportDecoder.quantize_); every other truthy value is int8 (low_resource_format).
     A checkpoint directory whose config.json carries `quantization_config.quant_method == "gptq"` is loaded AS int4 (prepare_int4_
     swaps the layer projections before the load; the codes are repacked, not re-quantised): low_resource must then be falsy or "int4"."""
@@ -69,6 +112,7 @@ def build_report_decoder(source=None, dtype=torch.float16, low_resource=False, *
         with open(os.path.join(source, "config.json")) as f:
             raw = json.load(f)
         cfg = {k: raw[k] for k in _CFG_KEYS if k in raw}
+        cfg.update(_family_config(raw, source))
         qc = raw.get("quantization_config") or {}
         if qc.get("quant_method") == "gptq":
             if fmt not in (None, Int4GroupLinear.NAME):

@@ -6,7 +6,8 @@ Replaces, for the MambaXray-VL report path, what the reference de
                                 min_new_tokens=80, max_new_tokens=120, repetition_penalty=2.0, length_penalty=2.0, ...)
 `ReportDecoder` has HF Llama-2 / Qwen2 parameter names (`model.embed_tokens`, `model.layers.{i}.self_attn.{q,k,v,o}_proj`,
 `mlp.{gate,up,down}_proj`, `input_layernorm`, `post_attention_layernorm`, `model.norm`, `lm_head`), so an HF
-state_dict loads directly (absent q/k/v biases = 0, i.e. Llama).  Layers listed in `hybrid_layers` are
+state_dict loads directly (absent q/k/v biases = 0, i.e. Llama).  Llama-3.x (`rope_scaling` of type "llama3") and Qwen3 (`head_dim`
+apart from hidden_size / heads, `qk_norm`: `self_attn.q_norm` / `k_norm`) are constructor arguments.  Layers listed in `hybrid_layers` are
 `Qwen2HybridDecoderLayer`s with the gated image cross-attention enabled (EMRRG installer,
 MambaXrayVL_DownStream.py:176-208); `condition_vis_x` / `clear_vis_x` fan out to them.
 
@@ -24,6 +25,7 @@ from __future__ import annotations
 from types import SimpleNamespace
 from typing import Iterable, Optional
 
+import gc
 import math
 
 import torch
@@ -173,8 +175,19 @@ class _Stepper:
         out = out if out is None else out.clone()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body(*args)
+        # No cyclic garbage collection inside the capture: a dead model <-> stepper cycle (model._steppers / stepper.model) owns
+        # CUDAGraphs, and destroying a graph is not a call a capturing stream allows -- the collector running at that moment aborts
+        # the process.  torch.cuda.graph() used to collect on entry; torch 2.10 does so only under torch.compiler.config.force_cudagraph_gc,
+        # so it is done here, and the collector stays off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph):
+                body(*args)
+        finally:
+            if gc_was_on:
+                gc.enable()
         setattr(self, slot, graph)
         return out
 
@@ -195,7 +208,7 @@ class _GraphStepper(_Stepper):
         self.P = prompt_mask.shape[1]
         self.max_len = self.P + max_new
         self.cache = StaticKVCache(cfg.num_hidden_layers, rows, cfg.num_key_value_heads, self.max_len,
-                                   cfg.hidden_size // cfg.num_attention_heads, dtype, dev, kv_dtype)
+                                   cfg.head_dim, dtype, dev, kv_dtype)
         self.mask = torch.zeros(rows, self.max_len, dtype=torch.long, device=dev)
         self.n_real = torch.zeros(rows, 1, dtype=torch.long, device=dev)
         self.tok = torch.zeros(rows, dtype=torch.long, device=dev)
@@ -604,7 +617,7 @@ class _KernelStepper(_Stepper):
         if torch.device(device).type == "cuda":
             _abi.load()          # a missing libmxvl.so is an error on a GPU box, never a silent torch path
         cfg = model.config
-        D = cfg.hidden_size // cfg.num_attention_heads
+        D = cfg.head_dim
         if _kv_mode(kv_dtype) == "fp8" and D == 256:
             return False         # the fp8-cache attention kernels (MXVL_KV_FP8) are built for head_dim 64 and 128
         for i in _KernelStepper._cond_layers(model):
@@ -622,11 +635,12 @@ class _KernelStepper(_Stepper):
         # rows <= 8: GEMV kernels with the activations of all rows in LDS; 9..80 rows (the reference's decode batches: 6 x 3,
         # 8 x 3, 16 x 3, 16 x 5 -- launch/*.sh, configs/config.py:11-12,50): MFMA projections (csrc/decode_gemm.h)
         # (rows <= 8 on the MFMA kernels as well wherever every K is a multiple of 64: no LDS bound on the activations there)
-        mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and cfg.hidden_size <= 16384
-        fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size) * 2 <= 150 * 1024) if rows <= 8 else \
-            (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size) >= 32 and cfg.hidden_size <= 16384)
+        HD = cfg.num_attention_heads * D          # o_proj's K (= hidden_size unless head_dim is given)
+        mfma8 = cfg.hidden_size % 64 == 0 and cfg.intermediate_size % 64 == 0 and HD % 64 == 0 and cfg.hidden_size <= 16384
+        fits = (mfma8 or rows * max(cfg.hidden_size, cfg.intermediate_size, HD) * 2 <= 150 * 1024) if rows <= 8 else \
+            (rows <= 80 and min(cfg.hidden_size, cfg.intermediate_size, HD) >= 32 and cfg.hidden_size <= 16384)
         fmt = model.weight_format()
-        if fmt is not None and any(k % fmt.K_MULTIPLE for k in (cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads * D)):
+        if fmt is not None and any(k % fmt.K_MULTIPLE for k in (cfg.hidden_size, cfg.intermediate_size, HD)):
             return False         # a quantised format (WEIGHT_FORMATS) has one kernel: every projection width in whole K_MULTIPLE columns
         # bf16, or fp16 -- the dtype the reference loads its LLM in (MambaXrayVL_DownStream.py:72,85,92); csrc/decode_elt.h
         return (torch.device(device).type == "cuda" and dtype in (torch.bfloat16, torch.float16) and D in (64, 128, 256)
@@ -638,7 +652,8 @@ class _KernelStepper(_Stepper):
         self.model, self.rows = model, rows
         self.kv8 = _kv_mode(kv_dtype) == "fp8"
         self.H, self.Hkv = cfg.num_attention_heads, cfg.num_key_value_heads
-        self.D = cfg.hidden_size // self.H
+        self.D = cfg.head_dim
+        self.qk_norm = bool(cfg.qk_norm)          # Qwen3: mxvl_decode_attn normalises the new q / k heads (MXVL_QK_NORM) -- in place in self.qkv
         self.hidden, self.inter, self.V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
         self.P = prompt_mask.shape[1]
         self.max_len = self.P + max_new
@@ -845,9 +860,11 @@ class _KernelStepper(_Stepper):
     def _body(self, tok, beam, cur):
         m = self.model
         self._prologue(tok, beam, cur)
-        a = _abi.DecodeAttnDesc()
+        # Qwen3 (config.qk_norm): the descriptor heads the longer one that carries the layer's q_norm / k_norm gains
+        aq = _abi.DecodeAttnQkNormDesc() if self.qk_norm else None
+        a = aq.attn if self.qk_norm else _abi.DecodeAttnDesc()
         a.rows, a.n_heads, a.n_kv_heads, a.head_dim, a.max_len = self.rows, self.H, self.Hkv, self.D, self.max_len
-        a.scale, a.dtype = self.D ** -0.5, self.dt | (_abi.MXVL_KV_FP8 if self.kv8 else 0)
+        a.scale, a.dtype = self.D ** -0.5, self.dt | (_abi.MXVL_KV_FP8 if self.kv8 else 0) | (_abi.MXVL_QK_NORM if self.qk_norm else 0)
         # the beams of a sample share a workgroup (and the cache lines they have in common) once head x sample workgroups fill the
         # chip; below that a workgroup per (head, row) keeps more requests in flight (batch 1 x beam 3: 9 vs 15 us per layer)
         a.beams = self.beams if (2 <= self.beams <= 5 and self.H * (self.rows // self.beams) >= 128 and self._beams_attn_fits()) else 0
@@ -868,7 +885,9 @@ class _KernelStepper(_Stepper):
             a.k_cache, a.v_cache = self.kc[i].data_ptr(), self.vc[i].data_ptr()
             a.kv_scale = self.kv_scale[i].data_ptr() if self.kv8 else None
             a.q_rope = self.q_rope.data_ptr() if i in self.cond else None
-            _abi.launch("mxvl_decode_attn", a, device=self.x.device)
+            if self.qk_norm:
+                aq.q_norm_weight, aq.k_norm_weight, aq.qk_norm_eps = at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.variance_epsilon
+            _abi.launch("mxvl_decode_attn", aq if self.qk_norm else a, device=self.x.device)
             att = self.att
             if i in self.cond:                       # gated image cross-attention on the rotated query, before o_proj
                 self._cross_attn(i)
@@ -930,14 +949,20 @@ class ReportDecoder(nn.Module):
     def __init__(self, vocab_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads,
                  num_key_value_heads=None, rms_norm_eps=1e-6, rope_theta=10000.0, max_position_embeddings=4096,
                  hybrid_layers: Iterable[int] = (), cross_attn_implementation="vanilla",
-                 cross_attn_gating_type="whole-dynamic-tanh-warmup"):
+                 cross_attn_gating_type="whole-dynamic-tanh-warmup", head_dim=None, qk_norm=False, rope_scaling=None):
+        """head_dim: None = hidden_size // num_attention_heads (Llama, Qwen2); Qwen3 publishes 128 at every size.  qk_norm: Qwen3's
+        per-head RMSNorm of q and k ahead of the rotation (`self_attn.q_norm` / `k_norm`).  rope_scaling: None or an HF dict
+        (`rope_type` "default" / "llama3" with its four parameters); every other type raises NotImplementedError."""
         super().__init__()
         self.config = SimpleNamespace(
             vocab_size=vocab_size, hidden_size=hidden_size, intermediate_size=intermediate_size,
             num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
             num_key_value_heads=num_key_value_heads or num_attention_heads, rms_norm_eps=rms_norm_eps,
             rope_theta=rope_theta, max_position_embeddings=max_position_embeddings, attention_dropout=0.0,
-            rope_scaling=None, hidden_act="silu", _attn_implementation="sdpa")
+            rope_scaling=None if rope_scaling is None else dict(rope_scaling), hidden_act="silu", _attn_implementation="sdpa",
+            head_dim=int(head_dim) if head_dim is not None else hidden_size // num_attention_heads, qk_norm=bool(qk_norm))
+        if head_dim is None and self.config.head_dim * num_attention_heads != hidden_size:
+            raise ValueError(f"hidden_size must be divisible by num_heads (got `hidden_size`: {hidden_size} and `num_heads`: {num_attention_heads}).")
         self.hybrid_layers = tuple(hybrid_layers)
         self.model = _Stack(self.config, set(self.hybrid_layers), cross_attn_implementation, cross_attn_gating_type)
         self.lm_head = nn.Linear(hidden_size, vocab_size, bias=False)
@@ -1326,7 +1351,7 @@ class ReportDecoder(nn.Module):
                             f"report decoding on {dev}: the HIP decode kernels serve bf16 / fp16 models with head_dim 64/128/256 "
                             f"(64/128 with kv_cache_dtype=\"fp8\") and "
                             f"batch * beams <= 80 (got rows={B * nb}, dtype={inputs_embeds.dtype}, head_dim="
-                            f"{self.config.hidden_size // self.config.num_attention_heads}, kv_cache_dtype={kv_cache_dtype!r}); pass use_graph=\"torch\" for the "
+                            f"{self.config.head_dim}, kv_cache_dtype={kv_cache_dtype!r}); pass use_graph=\"torch\" for the "
                             f"torch-module stepper or use_graph=False for the eager loop")
                     cls = _KernelStepper
                 stepper = cls(self, B * nb, attention_mask, cache, max_new_tokens, inputs_embeds.dtype, kv_dtype)
