@@ -303,7 +303,8 @@ extern "C" int mxvl_patch_cols(const void* img, void* cols, int N, int C, int H,
                                void* hip_stream) {
   if (!img || !cols) return MXVL_ERR_NULL;
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || patch <= 0 || H % patch != 0 || W % patch != 0) return MXVL_ERR_SHAPE;
-  if (patch % 4 != 0 || 256 % patch != 0 || N > 65535 || C > 65535) return MXVL_ERR_UNSUPPORTED;
+  // patch in {4, 8, 16, 32, 64} (mxvl.h): the tile is patch rows of 260 floats, and at 256 rows it is larger than a workgroup's LDS
+  if (patch % 4 != 0 || 256 % patch != 0 || patch > 64 || N > 65535 || C > 65535) return MXVL_ERR_UNSUPPORTED;
   auto ok = [](int d) { return d == MXVL_F32 || d == MXVL_BF16 || d == MXVL_F16; };
   if (!ok(in_dtype) || !ok(out_dtype)) return MXVL_ERR_DTYPE;
   if (in_dtype != out_dtype && in_dtype != MXVL_F32) return MXVL_ERR_DTYPE;      // a copy, or the autocast down-cast of an fp32 image

@@ -177,7 +177,7 @@ def window_cols(x_nhwc, k, relu=False):
 
 def patch_cols_supported(img, patch):
     return (img.is_cuda and img.dim() == 4 and img.is_contiguous() and img.dtype in (torch.float32, torch.float16, torch.bfloat16)
-            and patch % 4 == 0 and 256 % patch == 0 and img.shape[2] % patch == 0 and img.shape[3] % patch == 0
+            and patch % 4 == 0 and 256 % patch == 0 and patch <= 64 and img.shape[2] % patch == 0 and img.shape[3] % patch == 0
             and img.shape[0] <= 65535 and img.shape[1] <= 65535 and img.data_ptr() % 16 == 0)
 
 

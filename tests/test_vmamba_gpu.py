@@ -25,8 +25,9 @@ def test_cross_scan_merge_bit_exact_golden():
         assert torch.equal(vm.CrossMerge.apply(ys).float().cpu(), g[ky])
 
 
-# planes held in the LDS (flat kernels: several planes per workgroup, a ragged last group, V = 4 and V = 1) and planes that only
-# the 32 x 32 tiles can take (128 x 96 in fp32)
+# planes held in the LDS (flat kernels, V = 4 and V = 1) and planes that only the 32 x 32 tiles can take (128 x 96 in fp32).  Every
+# shape here runs ONE plane per workgroup: cross_planes_per_wg() keeps P > 1 only from 1024 workgroups on.  Several planes per workgroup,
+# the ragged last group, the quotients of cross_div and unaligned bases are in test_cross_scan_gpu.py, which proves its case list on the CPU.
 @pytest.mark.parametrize("shape", [(2, 96, 56, 56), (3, 7, 33, 65), (1, 5, 1, 70), (2, 4, 31, 1), (1, 2, 128, 96),
                                    (3, 70, 14, 14), (2, 37, 7, 7), (2, 19, 28, 28), (1, 3, 12, 20), (1, 1030, 14, 14)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
